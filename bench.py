@@ -8,11 +8,17 @@
 A "step" is one denoiser training step of BASELINE.json configs[1]: zero_grad + forward (bf16
 autocast) + backward + AdamW + EMA on 512 points x 128-d latents, width 1024 / 24 layers / 16 heads,
 GLOBAL batch 64 (strong scaling: 64/N samples per GPU, gradients averaged with an RCCL all-reduce).
-Rank 0 prints ONE JSON line.  `value` = denoiser train steps/s of the whole job; the renderer half of
-the BASELINE metric (rays/s for 128x128 views, k=8, 128 depth samples) is measured in its own timed
-region and reported under "render".
+Rank 0 prints ONE JSON line.  `value` = denoiser train steps/s of the whole job, `ms_per_step` = wall time of
+one timed step.  A plain run does only that: set up, warm up, time --steps steps, print the line.
+--full adds everything else the benchmark measures or checks, after the timed steps: per-kernel
+rooflines and clock samples of the timed region, the strong-scaling proxy, the renderer half of the
+BASELINE metric (rays/s for 128x128 views, k=8, 128 depth samples, under "render"), stage 1, the
+configs[4] step, the sampler, the evaluation loop, the CPU baseline + full-width parity against the
+oracle and, for N > 1, the communication record (`comm`); the --no-* switches drop single legs of it.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs()).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -63,6 +69,29 @@ def synthetic_batch(global_batch, rank, world, device):
     per = global_batch // world
     sl = slice(rank * per, (rank + 1) * per)
     return coords[sl].to(device), feats[sl].to(device)
+
+
+DUMP_SAMPLE = 1 << 20          # entries drawn from each flat state buffer by --dump-outputs (4 MiB of float32 each)
+
+
+def dump_outputs(out_dir, trainer, loss, sub, rank):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, as DIR/<name>.npy in float32 -- the
+    loss and its two terms, and the training state the step left behind: parameters, first Adam moment (the gradients' trace)
+    and EMA, each as the same seeded sample of DUMP_SAMPLE positions of the flat buffer (310.8 M entries), and the positions
+    (sample_index, float64); 20 MiB in all.  Collective for N > 1 (the sharded optimizer's state is gathered first); rank 0 writes."""
+    import numpy as np
+    trainer.gather_state()                         # (waits for pending parameter gathers; a no-op on one GPU)
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    n = trainer.flat.numel
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(0)).sort().values
+    idx = idx.to(trainer.flat.flat.device)
+    arrays = {"loss": loss.reshape(1), **{k: v.detach().reshape(1) for k, v in sub.items()},
+              "params_sample": trainer.flat.flat[idx], "exp_avg_sample": trainer.exp_avg[idx], "ema_sample": trainer.ema[idx]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.cpu().double().numpy())     # (float64: exact up to 2^53)
 
 
 def query_roofline(S, query_ms, launches, clock_ghz=None):
@@ -708,128 +737,9 @@ def strong_scaling_proxy(trainer, coords, feats, steps=8, warmup=3):
     return out
 
 
-def spawn_ranks(n):
-    """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
-    --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a child process and relay its output: stdout
-    lines pass through unchanged (exactly one JSON line, printed by rank 0), stderr is inherited.  Called BEFORE any GPU call
-    of this process; returns the launcher's exit code."""
-    import socket
-    import subprocess
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC only on these hosts (RCCL needs it across processes)
-    env.setdefault("OMP_NUM_THREADS", "8")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    print(f"bench.py: no WORLD_SIZE in the environment, starting {n} ranks: {' '.join(cmd)}", file=sys.stderr, flush=True)
-    child = subprocess.Popen(cmd, stdout=subprocess.PIPE, env=env, text=True, bufsize=1)
-    try:
-        for line in child.stdout:
-            sys.stdout.write(line)
-            sys.stdout.flush()
-        return child.wait()
-    except BaseException:
-        child.terminate()
-        try:
-            child.wait(timeout=30)
-        except Exception:           # noqa: BLE001
-            child.kill()
-        raise
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-render", action="store_true")
-    ap.add_argument("--no-proxy", action="store_true", help="skip the one-GPU strong-scaling proxy (per-GPU batch 64/32/16/8)")
-    ap.add_argument("--no-cfg5", action="store_true", help="skip the BASELINE configs[4] step (2048 points x 256-d, per-GPU batch 32)")
-    ap.add_argument("--no-sampler", action="store_true", help="skip the DDPM reverse-step timing (SURVEY 8(f) rank 1)")
-    ap.add_argument("--eval-loop-fp32-class", action="store_true", help="also run the generate -> render evaluation loop in the reference's numerics class (~10 s more)")
-    ap.add_argument("--rccl-algo", default=None, help="NCCL_ALGO for RCCL (e.g. Ring, Tree); default: RCCL's own choice")
-    ap.add_argument("--rccl-proto", default=None, help="NCCL_PROTO for RCCL (e.g. Simple, LL, LL128); default: RCCL's own choice")
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: start the N ranks ourselves (a CHILD process, never an exec; nothing in this
-        # process has touched the GPU yet), relay rank 0's JSON line and leave with the launcher's return code
-        raise SystemExit(spawn_ranks(args.gpus))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus} "
-                         f"(or unset WORLD_SIZE and bench.py starts its own ranks)")
-    # NPCD_BENCH_DRYRUN_ONE_GPU=1 (tests only): all ranks share cuda:0 and talk through gloo, so that the multi-rank code path
-    # of this script can be exercised on a one-GPU box (RCCL refuses two ranks on one device)
-    dryrun = bool(os.environ.get("NPCD_BENCH_DRYRUN_ONE_GPU"))
-    if dryrun:
-        local_rank = 0
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    if args.rccl_algo:
-        os.environ["NCCL_ALGO"] = args.rccl_algo            # (read by RCCL at communicator creation)
-    if args.rccl_proto:
-        os.environ["NCCL_PROTO"] = args.rccl_proto
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if dryrun:
-            dist.init_process_group("gloo", rank=rank, world_size=world)
-        else:
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)     # "nccl" is RCCL on ROCm
-    if CFG["global_batch"] % world:
-        raise SystemExit("global batch 64 must be divisible by the number of GPUs")
-    per = CFG["global_batch"] // world
-
-    # hipBLASLt / rocBLAS solution choices recorded once with PyTorch TunableOp (tools/tune_gemms.py) for the GEMM shapes
-    # of this step; loaded with tuning DISABLED (shapes not in the file use the library default).  NPCD_NO_TUNED_GEMM=1 skips it.
-    tuned = os.environ.get("NPCD_TUNED_CSV") or os.path.join(ROOT, "profiles", "tunableop_gfx950.csv")      # (the variable: A/B of tuning recipes)
-    use_tuned = os.path.exists(tuned) and not os.environ.get("NPCD_NO_TUNED_GEMM")
-    if use_tuned:
-        import torch.cuda.tunable as tun
-        tun.enable(True)
-        tun.tuning_enable(False)
-        tun.record_untuned_enable(False) if hasattr(tun, "record_untuned_enable") else None
-        tun.set_filename(os.path.join("/tmp", f"npcd_tunableop_unused_{rank}.csv"))    # never overwrite the committed file
-        use_tuned = bool(tun.read_file(tuned))
-
-    from npcd.hip import attention as hattn
-    from npcd.hip import elementwise as hew
-    trainer = build_trainer(device, per)
-    coords, feats = synthetic_batch(CFG["global_batch"], rank, world, device)
-    # weights are identical on every rank (seed above); the per-step draws (timesteps, noise) are not: seed + rank, as a
-    # DistributedSampler-style job would (SURVEY 8(e))
-    torch.manual_seed(42 + rank)
-    torch.cuda.manual_seed(42 + rank)
-
-    def barrier():
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    for _ in range(args.warmup):
-        trainer.step(coords, feats)
-    barrier()
-    hattn.KERNEL_EVENTS = {k: [] for k in hattn.KERNEL_TAGS}
-    hew.KERNEL_EVENTS = {"add_ln_fwd": [], "ln_bwd": [], "gelu_fwd": [], "gelu_bwd": []}
-    with ClockSampler(local_rank) as clocks:
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss, _ = trainer.step(coords, feats)
-        barrier()
-        elapsed = time.perf_counter() - t0
-    events, hattn.KERNEL_EVENTS = hattn.KERNEL_EVENTS, None
-    ew_events, hew.KERNEL_EVENTS = hew.KERNEL_EVENTS, None
-    if world > 1:
-        tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt)
-    assert torch.isfinite(loss), "training diverged"
-
+def timed_region_rooflines(per, events, ew_events):
+    """--full: the attention and elementwise kernels of the timed region against their rooflines, from the HIP events that the
+    kernels' wrappers record on the launch stream while KERNEL_EVENTS is set (a plain run leaves it unset)."""
     # ---- attention roofline (MFMA-bound), on the ALGORITHMIC FLOPs of SURVEY 8(d) ---------------------------------------
     # unit U = one B x H x n x n x d product = 2 B H n^2 d FLOP.  Forward = 2 U (QK^T, PV).  Backward = 5 U (S, dP, dV, dK, dQ)
     # however many products the kernels execute: a two-pass backward (dq pass: S, dP, dQ; dk/dv pass: S, dP, dV, dK)
@@ -912,6 +822,138 @@ def main():
                "traffic": htraffic, "traffic_source": f"profiles/{hfile}" if htraffic else None, "stale_counters": bool(hstale),
                "algorithmic_bytes_per_launch": ew_bytes[dom], "avg_ms": ew_ms[dom], "launches": len(ew_events[dom]),
                "all_elementwise_kernels_ms": ew_ms, "all_elementwise_kernels_gbs": gbs}
+    return roofline, hbm
+
+
+def spawn_ranks(n):
+    """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
+    --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a child process and relay its output: stdout
+    lines pass through unchanged (exactly one JSON line, printed by rank 0), stderr is inherited.  Called BEFORE any GPU call
+    of this process; returns the launcher's exit code."""
+    import socket
+    import subprocess
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC only on these hosts (RCCL needs it across processes)
+    env.setdefault("OMP_NUM_THREADS", "8")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    print(f"bench.py: no WORLD_SIZE in the environment, starting {n} ranks: {' '.join(cmd)}", file=sys.stderr, flush=True)
+    child = subprocess.Popen(cmd, stdout=subprocess.PIPE, env=env, text=True, bufsize=1)
+    try:
+        for line in child.stdout:
+            sys.stdout.write(line)
+            sys.stdout.flush()
+        return child.wait()
+    except BaseException:
+        child.terminate()
+        try:
+            child.wait(timeout=30)
+        except Exception:           # noqa: BLE001
+            child.kill()
+        raise
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-render", action="store_true")
+    ap.add_argument("--no-proxy", action="store_true", help="skip the one-GPU strong-scaling proxy (per-GPU batch 64/32/16/8)")
+    ap.add_argument("--no-cfg5", action="store_true", help="skip the BASELINE configs[4] step (2048 points x 256-d, per-GPU batch 32)")
+    ap.add_argument("--no-sampler", action="store_true", help="skip the DDPM reverse-step timing (SURVEY 8(f) rank 1)")
+    ap.add_argument("--eval-loop-fp32-class", action="store_true", help="also run the generate -> render evaluation loop in the reference's numerics class (~10 s more)")
+    ap.add_argument("--rccl-algo", default=None, help="NCCL_ALGO for RCCL (e.g. Ring, Tree); default: RCCL's own choice")
+    ap.add_argument("--rccl-proto", default=None, help="NCCL_PROTO for RCCL (e.g. Simple, LL, LL128); default: RCCL's own choice")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other measurement and check of the benchmark "
+                                                        "(rooflines, clock, proxy, render, stage 1, cfg5, sampler, CPU baseline + parity, comm); "
+                                                        "the --no-* switches drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32; the sample positions float64)")
+    args = ap.parse_args()
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # plain `python bench.py --gpus N`: start the N ranks ourselves (a CHILD process, never an exec; nothing in this
+        # process has touched the GPU yet), relay rank 0's JSON line and leave with the launcher's return code
+        raise SystemExit(spawn_ranks(args.gpus))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus} "
+                         f"(or unset WORLD_SIZE and bench.py starts its own ranks)")
+    # NPCD_BENCH_DRYRUN_ONE_GPU=1 (tests only): all ranks share cuda:0 and talk through gloo, so that the multi-rank code path
+    # of this script can be exercised on a one-GPU box (RCCL refuses two ranks on one device)
+    dryrun = bool(os.environ.get("NPCD_BENCH_DRYRUN_ONE_GPU"))
+    if dryrun:
+        local_rank = 0
+    torch.cuda.set_device(local_rank)
+    device = torch.device("cuda", local_rank)
+    if args.rccl_algo:
+        os.environ["NCCL_ALGO"] = args.rccl_algo            # (read by RCCL at communicator creation)
+    if args.rccl_proto:
+        os.environ["NCCL_PROTO"] = args.rccl_proto
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if dryrun:
+            dist.init_process_group("gloo", rank=rank, world_size=world)
+        else:
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)     # "nccl" is RCCL on ROCm
+    if CFG["global_batch"] % world:
+        raise SystemExit("global batch 64 must be divisible by the number of GPUs")
+    per = CFG["global_batch"] // world
+
+    # hipBLASLt / rocBLAS solution choices recorded once with PyTorch TunableOp (tools/tune_gemms.py) for the GEMM shapes
+    # of this step; loaded with tuning DISABLED (shapes not in the file use the library default).  NPCD_NO_TUNED_GEMM=1 skips it.
+    tuned = os.environ.get("NPCD_TUNED_CSV") or os.path.join(ROOT, "profiles", "tunableop_gfx950.csv")      # (the variable: A/B of tuning recipes)
+    use_tuned = os.path.exists(tuned) and not os.environ.get("NPCD_NO_TUNED_GEMM")
+    if use_tuned:
+        import torch.cuda.tunable as tun
+        tun.enable(True)
+        tun.tuning_enable(False)
+        tun.record_untuned_enable(False) if hasattr(tun, "record_untuned_enable") else None
+        tun.set_filename(os.path.join("/tmp", f"npcd_tunableop_unused_{rank}.csv"))    # never overwrite the committed file
+        use_tuned = bool(tun.read_file(tuned))
+
+    from npcd.hip import attention as hattn
+    from npcd.hip import elementwise as hew
+    trainer = build_trainer(device, per)
+    coords, feats = synthetic_batch(CFG["global_batch"], rank, world, device)
+    # weights are identical on every rank (seed above); the per-step draws (timesteps, noise) are not: seed + rank, as a
+    # DistributedSampler-style job would (SURVEY 8(e))
+    torch.manual_seed(42 + rank)
+    torch.cuda.manual_seed(42 + rank)
+
+    def barrier():
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    for _ in range(args.warmup):
+        trainer.step(coords, feats)
+    barrier()
+    if args.full:       # per-kernel HIP events and the clock datum of the timed region: --full only
+        hattn.KERNEL_EVENTS = {k: [] for k in hattn.KERNEL_TAGS}
+        hew.KERNEL_EVENTS = {"add_ln_fwd": [], "ln_bwd": [], "gelu_fwd": [], "gelu_bwd": []}
+    clocks = ClockSampler(local_rank) if args.full else contextlib.nullcontext()
+    with clocks:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            loss, sub = trainer.step(coords, feats)
+        barrier()
+        elapsed = time.perf_counter() - t0
+    events, hattn.KERNEL_EVENTS = hattn.KERNEL_EVENTS, None
+    ew_events, hew.KERNEL_EVENTS = hew.KERNEL_EVENTS, None
+    if world > 1:
+        tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt)
+    assert torch.isfinite(loss), "training diverged"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer, loss, sub, rank)
 
     result = {
         "metric": "denoiser train steps/sec (+ rendered rays/sec under 'render'), SRN-Cars 512pt x 128d",
@@ -926,13 +968,13 @@ def main():
         "step_tflops": denoiser_flops_per_sample() * CFG["global_batch"] / (elapsed / args.steps) / 1e12,
         "step_frac_of_bf16_mfma_peak": denoiser_flops_per_sample() * CFG["global_batch"] / (elapsed / args.steps) / 1e12
                                        / (PEAK_BF16_TFLOPS * world),
-        "roofline": roofline,
-        "roofline_hbm": hbm,
         "loss": float(loss),
         "tuned_gemm_file": (os.path.relpath(tuned, ROOT) if os.path.abspath(tuned).startswith(ROOT + os.sep) else tuned) if use_tuned else None,
-        "clock": clocks.summary(),
     }
-    if world > 1:
+    if args.full:
+        result["roofline"], result["roofline_hbm"] = timed_region_rooflines(per, events, ew_events)
+        result["clock"] = clocks.summary()
+    if world > 1 and args.full:
         # what went over the wire in the last step, and proof that the ranks still hold the same model
         trainer.wait_params()
         # elementwise: rank 0's flat parameter buffer is broadcast and every rank reports max |p - p_rank0| (0.0 = bit-identical
@@ -954,13 +996,13 @@ def main():
         comm["launched_by"] = os.environ.get("TORCHELASTIC_RUN_ID") and "torch.distributed.run" or "external launcher"
         comm["rccl_env"] = {k: os.environ[k] for k in ("NCCL_ALGO", "NCCL_PROTO", "NCCL_MIN_NCHANNELS", "NCCL_MAX_NCHANNELS") if k in os.environ}
         result["comm"] = comm
-    if world == 1 and not args.no_proxy:
+    if world == 1 and args.full and not args.no_proxy:
         try:
             result["strong_scaling_proxy"] = strong_scaling_proxy(trainer, coords, feats)
         except Exception as e:                      # noqa: BLE001
             result["strong_scaling_proxy"] = {"error": f"{type(e).__name__}: {e}"}
     # the secondary measurements must never take the headline line down with them
-    if not args.no_render:
+    if args.full and not args.no_render:
         try:
             r = bench_render(device)
         except Exception as e:                      # noqa: BLE001
@@ -993,17 +1035,17 @@ def main():
             result["stage1_pointnerf_training"] = s1
         except Exception as e:                      # noqa: BLE001
             result["stage1_pointnerf_training"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_cfg5:
+    if world == 1 and args.full and not args.no_cfg5:
         try:
             result["cfg5_stress_step"] = bench_cfg5(device)
         except Exception as e:                      # noqa: BLE001
             result["cfg5_stress_step"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_sampler:
+    if world == 1 and args.full and not args.no_sampler:
         try:
             result["sampler_reverse_step"] = bench_sampler(device)
         except Exception as e:                      # noqa: BLE001
             result["sampler_reverse_step"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_sampler and not args.no_render:
+    if world == 1 and args.full and not args.no_sampler and not args.no_render:
         try:
             result["sample_and_render"] = bench_sample_and_render(device)
         except Exception as e:                      # noqa: BLE001
@@ -1014,7 +1056,7 @@ def main():
             except Exception as e:                  # noqa: BLE001
                 result["sample_and_render_fp32_class"] = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"], ref = cpu_baseline()
                 result["gpu_over_cpu"] = {"denoiser_steps": result["value"] / result["cpu_baseline"]["value"]}
@@ -1031,6 +1073,7 @@ def main():
                     result["parity_full_width"] = {"error": f"{type(e).__name__}: {e}", "ok": False}
         print(json.dumps(result), flush=True)
     if world > 1:
+        trainer.wait_params()               # (parameter gathers of the last step still in flight)
         dist.destroy_process_group()
 
 

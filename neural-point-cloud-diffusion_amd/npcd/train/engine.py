@@ -345,7 +345,7 @@ class DiffusionTrainer:
         return (_none, ())
 
     def comm_stats(self):
-        """Communication bookkeeping of the LAST step of this rank (bench.py puts it into the line for n_gpus > 1, DESIGN.md
+        """Communication bookkeeping of the LAST step of this rank (bench.py --full puts it into the line for n_gpus > 1, DESIGN.md
         section 6): bytes handed to the gradient collectives, bytes of the parameter all-gather, number of collectives, and how many
         gradient collectives were still running when the backward had finished (the exposed ones)."""
         red = self.reducer
