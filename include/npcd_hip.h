@@ -386,6 +386,49 @@ int npcd_adamw_ema_dt(float* p, float* g, float* m, float* v, float* ema, void* 
                       float ema_decay, int zero_grad, void* stream);
 int npcd_cast_f32_dt(const float* src, void* dst, int64_t numel, int dtype, void* stream);
 
+/* ---- loss scaling and gradient clipping on the device (the reference's GradScaler + clip_grad_norm_,
+ * train/diffusion_training.py:62,156-174): the overflow check, the global norm, the skip decision, the scale
+ * update and the AdamW step count live in a control record in device memory that the optimizer kernel reads,
+ * so that no step waits for the GPU.  Per step:
+ *   npcd_grad_stats (per gradient range, into its own slot)  [-> all-reduce(SUM) of the slots across ranks]
+ *   -> npcd_scaler_finalize (reads the slots, updates the record) -> npcd_adamw_ema_gated (per range).
+ *
+ * Control record, 64 bytes (16 x 4-byte words), every field written by npcd_scaler_finalize only; the host
+ * initialises it and may overwrite loss_scale / step / skipped between steps:
+ *   word 0  found_inf       int32  1 when the last finalized gradient held an inf / nan (the step is skipped)
+ *   word 1  step            int32  AdamW steps applied (t); +1 per finalize without overflow
+ *   word 2  growth_tracker  int32  clean steps since the last scale change
+ *   word 3  skipped         int32  steps skipped so far
+ *   word 4  loss_scale      float  scale of the NEXT backward (a power of two)
+ *   word 5  inv_scale       float  1 / the scale the finalized gradient carries
+ *   word 6  grad_norm       float  global L2 norm of the UNSCALED gradient, +inf when it overflowed
+ *   word 7  clip_coef       float  min(max_norm / (grad_norm + 1e-6), 1) (torch's formula); 1 without clipping
+ *   word 8  bc1             float  (float)(1 - beta1^step), double-precision pow, as npcd_adamw_ema_dt computes it
+ *   word 9  bc2_sqrt        float  (float)sqrt(1 - beta2^step)
+ *   words 10-15 reserved (zero) */
+typedef struct NpcdScalerCtl {
+    int32_t found_inf, step, growth_tracker, skipped;
+    float loss_scale, inv_scale, grad_norm, clip_coef, bc1, bc2_sqrt;
+    int32_t reserved[6];
+} NpcdScalerCtl;
+/* Statistics of the fp32 range g[0, n): out[0] = sum of g^2 over the finite elements (fp64 accumulation), out[1] = number
+ * of inf / nan elements.  `work`: 2 * npcd_grad_stats_blocks() doubles.  Two launches (per-workgroup partials, then
+ * their sum in a fixed order), no atomics: the same data gives the same bits on every run.  g 16-byte aligned, any n >= 1. */
+int npcd_grad_stats_blocks(void);
+int npcd_grad_stats(const float* g, int64_t n, double* work, double* out, void* stream);
+/* One workgroup: sums stats[0 .. nslots) in slot order, then updates the record.  scaling = 0: no loss scaling (found_inf
+ * stays 0, inv_scale 1, the scale is not touched); otherwise GradScaler's dynamic scale: x backoff on overflow (step skipped,
+ * growth tracker reset), x growth after growth_interval clean steps.  clip = 0: clip_coef = 1. */
+int npcd_scaler_finalize(const double* stats, int nslots, NpcdScalerCtl* ctl, int scaling, int clip, float max_norm,
+                         float beta1, float beta2, float growth_factor, float backoff_factor, int growth_interval, void* stream);
+/* npcd_adamw_ema_dt on the gradient (g * ctl->inv_scale) * ctl->clip_coef with ctl->bc1 / ctl->bc2_sqrt as bias corrections.
+ * When ctl->found_inf is set, p, m, v and the shadow are left untouched; the EMA still moves towards p (the reference updates it
+ * every iteration) and g is still zeroed when zero_grad is set.  EMA weight: 1 - (float)ema_decay on an applied step (as
+ * npcd_adamw_ema_dt), (float)(1 - ema_decay) on a skipped one (torch's lerp_ weight, as the host-side loss scaler moves it). */
+int npcd_adamw_ema_gated(float* p, float* g, float* m, float* v, float* ema, void* shadow, int shadow_dtype, int64_t numel,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, double ema_decay, int zero_grad,
+                         const NpcdScalerCtl* ctl, void* stream);
+
 /* Weight gradient of a Linear layer (the nn.Linear weight gradients of transformer.py:67-72, :107-115, :118-137, which autograd
  * computes in the reference): dW [N, K] fp32 = dy[T, N]^T x[T, K], dy / x row-major in the 16-bit `dtype`, fp32 accumulation and
  * output; N % 256 == 0, K % 256 == 0, any T.  The token range is split over npcd_wgrad_slices(T, N, K) workgroup slices that write

@@ -9,6 +9,7 @@
 //   GELU(erf) forward / backward (+ bias-gradient column sum)     -> gelu_fwd / gelu_bwd
 //   column sum of a bf16 matrix (bias gradient of c_qkv)          -> colsum
 //   AdamW + EMA + bf16 weight shadow + gradient zeroing           -> adamw_ema (1 pass over 310 M params)
+//   GradScaler + clip_grad_norm_ bookkeeping on the device        -> grad_stats, scaler_finalize, adamw_ema_gated
 // All are pure streaming kernels: 16-byte accesses per lane, fp32 math, no LDS except the cross-wave
 // reduction of column partials.  Roofline: HBM.
 #include <math.h>
@@ -489,15 +490,45 @@ __device__ __forceinline__ void adamw_one(f32x4& pp, const f32x4 gg, f32x4& mm, 
 
 // Two float4 per thread and trip: all ten loads of a trip are issued before the first dependent use (the kernel is a pure
 // stream of 5 reads + 6 writes per element; more bytes in flight per wave is the only lever).
-template <class E>
-__global__ __launch_bounds__(256) void adamw_ema_kernel(f32x4* __restrict__ p, f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
-                                                        f32x4* __restrict__ ema, typename V<E>::x4* __restrict__ shadow, int64_t n4, AdamArgs a, int zero_grad) {
+// GATED (npcd_adamw_ema_gated, a separate kernel; the plain one compiles without any of it): the gradient is (g * inv_scale) *
+// clip_coef and the bias corrections come from the loss-scaler control record; an overflowed step only moves the EMA.
+template <class E, bool GATED>
+__device__ __forceinline__ void adamw_ema_body(f32x4* __restrict__ p, f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
+                                               f32x4* __restrict__ ema, typename V<E>::x4* __restrict__ shadow, int64_t n4, AdamArgs a,
+                                               int zero_grad, const NpcdScalerCtl* __restrict__ ctl, float skip_ema_w) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float gs = 1.f, gc = 1.f;
+    if constexpr (GATED) {
+        if (ctl->found_inf) {               // skipped step (uniform over the grid): EMA towards the unchanged p, gradient zeroing
+            for (; i < n4; i += stride) {
+                if (ema) {
+                    const f32x4 e = ema[i], pp = p[i];
+                    ema[i] = e + (pp - e) * skip_ema_w;
+                }
+                if (zero_grad) g[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            return;
+        }
+        gs = ctl->inv_scale;
+        gc = ctl->clip_coef;
+        a.bc1 = ctl->bc1;
+        a.bc2_sqrt = ctl->bc2_sqrt;
+    }
+    // (two multiplies in this order, as the host path's unscale mul_ and clip mul_; exact for a power-of-two scale).  The empty asm
+    // hands the product to adamw_one as an opaque value, like the loaded gradient of the plain kernel: the compiler then contracts
+    // the moment updates into the same fused multiply-adds in both kernels, so that the gated update is the plain one bit for bit.
+    auto grad = [&](f32x4 x) -> f32x4 {
+        if constexpr (GATED) {
+            x = (x * gs) * gc;
+            asm volatile("" : "+v"(x));
+        }
+        return x;
+    };
     for (; i + stride < n4; i += 2 * stride) {
         const int64_t k = i + stride;
         f32x4 p0 = p[i], p1 = p[k];
-        const f32x4 g0 = g[i], g1 = g[k];
+        const f32x4 g0 = grad(g[i]), g1 = grad(g[k]);
         f32x4 m0 = m[i], m1 = m[k], v0 = v[i], v1 = v[k];
         f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = e0;
         if (ema) { e0 = ema[i]; e1 = ema[k]; }
@@ -512,7 +543,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(f32x4* __restrict__ p, f
     }
     if (i < n4) {
         f32x4 pp = p[i];
-        const f32x4 gg = g[i];
+        const f32x4 gg = grad(g[i]);
         f32x4 mm = m[i], vv = v[i];
         adamw_one(pp, gg, mm, vv, a);
         p[i] = pp;
@@ -525,6 +556,108 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(f32x4* __restrict__ p, f
         if (shadow) shadow[i] = from_f32<E>(pp);
         if (zero_grad) g[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(f32x4* __restrict__ p, f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
+                                                        f32x4* __restrict__ ema, typename V<E>::x4* __restrict__ shadow, int64_t n4, AdamArgs a, int zero_grad) {
+    adamw_ema_body<E, false>(p, g, m, v, ema, shadow, n4, a, zero_grad, nullptr, 0.f);
+}
+template <class E>
+__global__ __launch_bounds__(256) void adamw_ema_gated_kernel(f32x4* __restrict__ p, f32x4* __restrict__ g, f32x4* __restrict__ m,
+                                                              f32x4* __restrict__ v, f32x4* __restrict__ ema, typename V<E>::x4* __restrict__ shadow,
+                                                              int64_t n4, AdamArgs a, int zero_grad, const NpcdScalerCtl* __restrict__ ctl,
+                                                              float skip_ema_w) {
+    adamw_ema_body<E, true>(p, g, m, v, ema, shadow, n4, a, zero_grad, ctl, skip_ema_w);
+}
+
+// ============================================================================================
+// Gradient statistics for loss scaling / clipping: sum of squares of the finite elements (fp64) and the number of inf / nan.
+// Stage 1: a grid-stride stream of 16-byte loads (two per trip), per-workgroup partials; stage 2: one workgroup adds them in a
+// fixed order.  The grid depends on n only: bitwise reproducible from run to run and from rank to rank.
+// ============================================================================================
+constexpr int kStatBlocks = 512;
+
+__device__ __forceinline__ void stat_one(float x, double& s, uint32_t& bad) {
+    const bool ok = fabsf(x) <= 3.402823466e38f;     // false for +-inf and nan
+    const double d = ok ? (double)x : 0.0;
+    s = fma(d, d, s);
+    bad += ok ? 0u : 1u;
+}
+__device__ __forceinline__ void stat_four(f32x4 x, double& s, uint32_t& bad) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) stat_one(x[j], s, bad);
+}
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+// (s, c) of the 256 threads -> thread 0, fixed order
+__device__ __forceinline__ void block_sum2(double& s, double& c) {
+    __shared__ double red[2][4];
+    s = wave_sum_f64(s);
+    c = wave_sum_f64(c);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = c; }
+    __syncthreads();
+    s = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    c = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+}
+
+__global__ __launch_bounds__(256) void grad_stats_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * 256, gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double s = 0.0;
+    uint32_t bad = 0;
+    int64_t i = gid;
+    for (; i + stride < n4; i += 2 * stride) {
+        const f32x4 x0 = g4[i], x1 = g4[i + stride];
+        stat_four(x0, s, bad);
+        stat_four(x1, s, bad);
+    }
+    if (i < n4) stat_four(g4[i], s, bad);
+    if (gid < n - 4 * n4) stat_one(g[4 * n4 + gid], s, bad);     // the n % 4 tail
+    double c = (double)bad;
+    block_sum2(s, c);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = s; part[2 * blockIdx.x + 1] = c; }
+}
+__global__ __launch_bounds__(256) void grad_stats_sum_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out) {
+    double s = 0.0, c = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) { s += part[2 * b]; c += part[2 * b + 1]; }
+    block_sum2(s, c);
+    if (threadIdx.x == 0) { out[0] = s; out[1] = c; }
+}
+
+// GradScaler.unscale_ / step / update and clip_grad_norm_'s coefficient on the record (one thread; plain stores)
+__global__ __launch_bounds__(64) void scaler_finalize_kernel(const double* __restrict__ stats, int nslots, NpcdScalerCtl* __restrict__ ctl,
+                                                             int scaling, int clip, float max_norm, float beta1, float beta2, float growth,
+                                                             float backoff, int interval) {
+    if (threadIdx.x != 0) return;
+    double sumsq = 0.0, bad = 0.0;
+    for (int k = 0; k < nslots; ++k) { sumsq += stats[2 * k]; bad += stats[2 * k + 1]; }
+    NpcdScalerCtl c = *ctl;
+    const float inv = scaling ? 1.f / c.loss_scale : 1.f;
+    c.inv_scale = inv;
+    c.found_inf = (scaling && bad > 0.0) ? 1 : 0;
+    // the scale is a power of two: sqrt(sumsq) * inv is the norm of the unscaled gradient up to the final rounding
+    const float norm = bad > 0.0 ? INFINITY : (float)(sqrt(sumsq) * (double)inv);
+    c.grad_norm = norm;
+    // torch: max_norm / (norm + 1e-6) evaluates as reciprocal(norm + 1e-6) * max_norm in fp32, then clamp(max=1)
+    c.clip_coef = clip ? fminf((1.f / (norm + 1e-6f)) * max_norm, 1.f) : 1.f;
+    if (c.found_inf) {
+        c.loss_scale *= backoff;
+        c.growth_tracker = 0;
+        c.skipped += 1;
+    } else {
+        c.step += 1;
+        c.bc1 = (float)(1.0 - pow((double)beta1, (double)c.step));
+        c.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)c.step));
+        if (scaling && ++c.growth_tracker == interval) {
+            c.loss_scale *= growth;
+            c.growth_tracker = 0;
+        }
+    }
+    *ctl = c;
 }
 
 template <class E>
@@ -830,6 +963,57 @@ extern "C" int npcd_adamw_ema_dt(float* p, float* g, float* m, float* v, float* 
 extern "C" int npcd_adamw_ema(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t numel, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int step, float ema_decay, int zero_grad, void* stream) {
     return npcd_adamw_ema_dt(p, g, m, v, ema, shadow_bf16, NPCD_BF16, numel, lr, beta1, beta2, eps, weight_decay, step, ema_decay, zero_grad, stream);
+}
+
+extern "C" int npcd_adamw_ema_gated(float* p, float* g, float* m, float* v, float* ema, void* shadow, int shadow_dtype, int64_t numel, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, double ema_decay, int zero_grad,
+                                    const NpcdScalerCtl* ctl, void* stream) {
+    if (!p || !g || !m || !v || !ctl || numel <= 0) return NPCD_ERR_ARG;
+    if (numel % 4 != 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v) || (ema && !al16(ema)) || (reinterpret_cast<uintptr_t>(ctl) & 15) ||
+        (shadow && ((reinterpret_cast<uintptr_t>(shadow) & 7) || !dt16(shadow_dtype))))
+        return NPCD_ERR_UNSUPPORTED;
+    AdamArgs a;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+    a.bc1 = 1.f; a.bc2_sqrt = 1.f;          // (from the record)
+    a.ema_w = 1.f - (float)ema_decay;       // an applied step: the plain kernel's weight
+    const float skip_w = (float)(1.0 - ema_decay);     // a skipped step: torch's lerp_(p, 1 - decay) weight, as the host path moves it
+    const int64_t n4 = numel / 4;
+    const int grid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (shadow && shadow_dtype == NPCD_F16)
+        hipLaunchKernelGGL(adamw_ema_gated_kernel<_Float16>, dim3(grid), dim3(256), 0, st, reinterpret_cast<f32x4*>(p), reinterpret_cast<f32x4*>(g),
+                           reinterpret_cast<f32x4*>(m), reinterpret_cast<f32x4*>(v), reinterpret_cast<f32x4*>(ema),
+                           static_cast<V<_Float16>::x4*>(shadow), n4, a, zero_grad, ctl, skip_w);
+    else
+        hipLaunchKernelGGL(adamw_ema_gated_kernel<__bf16>, dim3(grid), dim3(256), 0, st, reinterpret_cast<f32x4*>(p), reinterpret_cast<f32x4*>(g),
+                           reinterpret_cast<f32x4*>(m), reinterpret_cast<f32x4*>(v), reinterpret_cast<f32x4*>(ema),
+                           static_cast<V<__bf16>::x4*>(shadow), n4, a, zero_grad, ctl, skip_w);
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
+}
+
+extern "C" int npcd_grad_stats_blocks(void) { return kStatBlocks; }
+
+extern "C" int npcd_grad_stats(const float* g, int64_t n, double* work, double* out, void* stream) {
+    if (!g || !work || !out || n <= 0) return NPCD_ERR_ARG;
+    if (!al16(g) || (reinterpret_cast<uintptr_t>(work) & 7) || (reinterpret_cast<uintptr_t>(out) & 7)) return NPCD_ERR_UNSUPPORTED;
+    const int64_t n4 = n / 4, want = (n4 + 511) / 512;         // >= two 16-byte loads per thread before a second workgroup
+    const int grid = (int)(want < 1 ? 1 : want < kStatBlocks ? want : kStatBlocks);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(grad_stats_kernel, dim3(grid), dim3(256), 0, st, g, n, work);
+    hipLaunchKernelGGL(grad_stats_sum_kernel, dim3(1), dim3(256), 0, st, work, grid, out);
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
+}
+
+extern "C" int npcd_scaler_finalize(const double* stats, int nslots, NpcdScalerCtl* ctl, int scaling, int clip, float max_norm, float beta1,
+                                    float beta2, float growth_factor, float backoff_factor, int growth_interval, void* stream) {
+    if (!stats || !ctl || nslots <= 0 || growth_interval <= 0) return NPCD_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(stats) & 7) || (reinterpret_cast<uintptr_t>(ctl) & 15)) return NPCD_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(scaler_finalize_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), stats, nslots, ctl, scaling, clip, max_norm,
+                       beta1, beta2, growth_factor, backoff_factor, growth_interval);
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
 }
 
 extern "C" int npcd_ddpm_reverse_step(const float* x_t, const void* eps, int eps_dtype, const float* noise, float* x_prev, float* x0_out,

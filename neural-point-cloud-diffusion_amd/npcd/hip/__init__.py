@@ -6,7 +6,7 @@ non-GPU tensor, a RuntimeError is raised.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 import torch
 
@@ -101,6 +101,10 @@ SIGNATURES = {
     "npcd_colsum_dt": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "npcd_adamw_ema_dt": (c_int, [_P] * 6 + [c_int, c_int64] + [c_float] * 5 + [c_int, c_float, c_int, _P]),
     "npcd_cast_f32_dt": (c_int, [_P, _P, c_int64, c_int, _P]),
+    "npcd_grad_stats_blocks": (c_int, []),
+    "npcd_grad_stats": (c_int, [_P, c_int64, _P, _P, _P]),
+    "npcd_scaler_finalize": (c_int, [_P, c_int, _P, c_int, c_int] + [c_float] * 5 + [c_int, _P]),
+    "npcd_adamw_ema_gated": (c_int, [_P] * 6 + [c_int, c_int64] + [c_float] * 5 + [c_double, c_int, _P, _P]),
     "npcd_wgrad_slices": (c_int, [c_int, c_int, c_int]),
     "npcd_wgrad": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "npcd_wgrad_group": (c_int, [c_int, POINTER(_P), POINTER(_P), POINTER(_P), POINTER(c_int), POINTER(c_int), c_int, c_int, _P]),

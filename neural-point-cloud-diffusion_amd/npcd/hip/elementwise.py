@@ -137,6 +137,50 @@ def adamw_ema(p, g, m, v, ema, shadow, lr, beta1, beta2, eps, weight_decay, step
                                   float(ema_decay if ema_decay is not None else 0.0), int(bool(zero_grad)), stream_ptr()), "npcd_adamw_ema")
 
 
+
+# ---- device-side loss scaling / clipping (include/npcd_hip.h, NpcdScalerCtl) ------------------------------------------------------
+# word indices of the 16-word control record (an int32 tensor; the float fields are read through .view(torch.float32))
+CTL_FOUND_INF, CTL_STEP, CTL_GROWTH_TRACKER, CTL_SKIPPED = 0, 1, 2, 3
+CTL_LOSS_SCALE, CTL_INV_SCALE, CTL_GRAD_NORM, CTL_CLIP_COEF, CTL_BC1, CTL_BC2_SQRT = 4, 5, 6, 7, 8, 9
+CTL_WORDS = 16
+
+
+def scaler_record(device, loss_scale=1.0, step=0):
+    """A fresh control record on `device`: the given scale and applied-step count, everything else zero."""
+    ctl = torch.zeros(CTL_WORDS, dtype=torch.int32, device=device)
+    ctl[CTL_STEP] = int(step)
+    ctl.view(_f32)[CTL_LOSS_SCALE] = float(loss_scale)
+    return ctl
+
+
+def grad_stats_work(device):
+    """Scratch of npcd_grad_stats: the per-workgroup partials."""
+    return torch.empty(2 * lib().npcd_grad_stats_blocks(), dtype=torch.float64, device=device)
+
+
+def grad_stats(g, out, work):
+    """out[0:2] (fp64) = [sum of squares of the finite elements, number of inf / nan elements] of the fp32 range g."""
+    require_gpu(g)
+    check(lib().npcd_grad_stats(ptr(g), g.numel(), ptr(work), ptr(out), stream_ptr()), "npcd_grad_stats")
+
+
+def scaler_finalize(stats, nslots, ctl, scaling, max_norm, beta1, beta2, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+    """Sum stats[0:nslots] (fp64 pairs) in slot order and update the control record (skip decision, unscaled norm, clip coefficient,
+    step count and bias corrections, next scale).  max_norm None: no clipping."""
+    check(lib().npcd_scaler_finalize(ptr(stats), int(nslots), ptr(ctl), int(bool(scaling)), int(max_norm is not None),
+                                     float(max_norm if max_norm is not None else 0.0), float(beta1), float(beta2), float(growth_factor),
+                                     float(backoff_factor), int(growth_interval), stream_ptr()), "npcd_scaler_finalize")
+
+
+def adamw_ema_gated(p, g, m, v, ema, shadow, lr, beta1, beta2, eps, weight_decay, ema_decay, ctl, zero_grad=True):
+    """adamw_ema on (g * inv_scale) * clip_coef with the record's bias corrections; a step the record marks as overflowed only moves
+    the EMA (and zeroes g when asked)."""
+    require_gpu(p)
+    check(lib().npcd_adamw_ema_gated(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(shadow), dtype_code(shadow) if shadow is not None else 0,
+                                     p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                     float(ema_decay if ema_decay is not None else 0.0), int(bool(zero_grad)), ptr(ctl), stream_ptr()),
+          "npcd_adamw_ema_gated")
+
 def small_wgrad(dy, x):
     """dW [J, K] fp32 = dy^T @ x for bf16 dy [T, J <= 4], x [T, K] (K a power of two in 64..2048); None if the shape is not covered."""
     T, J = dy.shape

@@ -235,10 +235,15 @@ class DiffusionTrainer:
     def __init__(self, diffusion: nn.Module, lr: float = 7e-5, weight_decay: float = 0.01, ema_decay: Optional[float] = 0.9999,
                  dtype: Optional[torch.dtype] = torch.bfloat16, group=None, bucket_bytes: int = 64 << 20, max_grad_norm=None,
                  fused: bool = True, always_reduce: bool = False, shard_optimizer: Optional[bool] = None,
-                 comm_dtype: Optional[torch.dtype] = None):
-        """shard_optimizer (default: on whenever gradients are exchanged on the native path without clipping / loss scaling):
-        ZeRO-1 style -- reduce-scatter instead of all-reduce, each rank runs AdamW + EMA on 1/world of every bucket, the updated
-        parameters are all-gathered.  Same bytes on the wire as the all-reduce, optimizer pass divided by the number of ranks."""
+                 comm_dtype: Optional[torch.dtype] = None, device_scaler: bool = False):
+        """shard_optimizer (default: on whenever gradients are exchanged on the native path without clipping / loss scaling, or
+        with them under device_scaler): ZeRO-1 style -- reduce-scatter instead of all-reduce, each rank runs AdamW + EMA on 1/world
+        of every bucket, the updated parameters are all-gathered.  Same bytes on the wire as the all-reduce, optimizer pass divided
+        by the number of ranks.
+        device_scaler (or NPCD_DEVICE_SCALER=1): float16 loss scaling and gradient clipping without any host wait -- the overflow
+        check, the global gradient norm, the skip decision, the scale update and the AdamW step count live in a control record in
+        device memory that the optimizer kernel reads.  Native path only (ValueError otherwise)."""
+        self._ctl = None                   # device-side loss-scaler record (device_scaler); None: the host keeps the bookkeeping
         self.model = diffusion
         self.dtype = dtype
         # the training loop never looks at the pointwise losses: this package's DiffusionModel can skip materialising them
@@ -254,7 +259,7 @@ class DiffusionTrainer:
         self.ema_decay = ema_decay
         self.ema = self.flat.flat.clone() if ema_decay is not None else None
         self.max_grad_norm = max_grad_norm
-        self.iteration = 0                 # optimizer steps applied (AdamW bias correction)
+        self.iteration = 0                 # optimizer steps applied (AdamW bias correction; property, see below)
         self.finished_iterations = 0       # loop iterations, including those a float16 overflow skipped (diffusion_training.py:190)
         # float16 autocast (the reference's default --dtype, train_diffusion.py:78) trains with dynamic loss scaling
         # (torch.cuda.amp.GradScaler defaults, diffusion_training.py:62,156,169-170): scale 2^16, halved when a gradient
@@ -263,6 +268,10 @@ class DiffusionTrainer:
         self._clean_steps = 0
         self.skipped_steps = 0
         self.native = self.flat.flat.is_cuda and fused
+        if not device_scaler:
+            device_scaler = os.environ.get("NPCD_DEVICE_SCALER", "") not in ("", "0")
+        if device_scaler and not self.native:
+            raise ValueError("device_scaler needs the native HIP path (a GPU model and fused=True)")
         if self.native:
             # HIP path: one fused AdamW+EMA kernel over the flat buffers, a bf16 shadow of the parameters for
             # the GEMMs and the explicit backbone forward/backward (npcd.models.diffusion.fused)
@@ -295,8 +304,19 @@ class DiffusionTrainer:
                     ranges.append((off, end - off))
             self._accum_ranges = ranges
             want = shard_optimizer if shard_optimizer is not None else not os.environ.get("NPCD_NO_SHARD_OPTIMIZER")
-            if want and self.reducer.active and max_grad_norm is None and self.loss_scale is None:
+            if want and self.reducer.active and (device_scaler or (max_grad_norm is None and self.loss_scale is None)):
                 self.reducer.enable_sharding()
+            if device_scaler:
+                # one fp64 [sum of squares, non-finite count] slot per bucket (or one for the whole buffer), the scratch of each
+                # slot's statistics, and the control record; the backward multiplies the loss by the record's scale (a device scalar)
+                nslots = max(1, len(self.reducer.buckets))
+                dev = self.flat.flat.device
+                self._scaling = self._loss_scale is not None
+                self._stats = torch.zeros((nslots, 2), dtype=torch.float64, device=dev)
+                self._stats_work = torch.stack([ew.grad_stats_work(dev) for _ in range(nslots)])
+                self._ctl = ew.scaler_record(dev, self._loss_scale if self._scaling else 1.0, self._iteration)
+                self._ctl_f = self._ctl.view(torch.float32)
+                self._scale_dev = self._ctl_f[ew.CTL_LOSS_SCALE]
             # Sharded optimizer: the updated parameters come back with one all-gather per bucket.  Those gathers are NOT awaited
             # at the end of the step: a bucket is awaited (and its bf16 shadow refreshed) right before the next forward first
             # reads a parameter of it -- the fused backbone asks block by block -- so that the 1.24 GB of parameter traffic runs
@@ -344,6 +364,56 @@ class DiffusionTrainer:
     def __reduce__(self):
         return (_none, ())
 
+    # ---- scaler bookkeeping: host attributes, or (device_scaler) fields of the device-side control record ------------------
+    @property
+    def iteration(self) -> int:
+        """Optimizer steps applied (AdamW bias correction; a float16 overflow does not count).  With device_scaler the count lives
+        in device memory: reading it waits for the GPU to finish the work queued so far."""
+        return self._iteration if self._ctl is None else int(self._ctl[self._ew.CTL_STEP])
+
+    @iteration.setter
+    def iteration(self, value):
+        if self._ctl is None:
+            self._iteration = value
+        else:
+            self._ctl[self._ew.CTL_STEP] = int(value)
+
+    @property
+    def loss_scale(self) -> Optional[float]:
+        """Scale of the next backward (float16 training; None without loss scaling).  With device_scaler it lives in device memory:
+        reading it waits for the GPU to finish the work queued so far."""
+        if self._ctl is None:
+            return self._loss_scale
+        return float(self._ctl_f[self._ew.CTL_LOSS_SCALE]) if self._scaling else None
+
+    @loss_scale.setter
+    def loss_scale(self, value):
+        if self._ctl is None:
+            self._loss_scale = value
+        elif not self._scaling:
+            if value is not None:
+                raise ValueError("this trainer does not scale its loss (dtype is not float16)")
+        else:
+            self._ctl_f[self._ew.CTL_LOSS_SCALE] = float(value)
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps a float16 overflow skipped.  With device_scaler it lives in device memory: reading it waits for the GPU."""
+        return self._skipped_steps if self._ctl is None else int(self._ctl[self._ew.CTL_SKIPPED])
+
+    @skipped_steps.setter
+    def skipped_steps(self, value):
+        if self._ctl is None:
+            self._skipped_steps = value
+        else:
+            self._ctl[self._ew.CTL_SKIPPED] = int(value)
+
+    @property
+    def last_grad_norm(self) -> Optional[float]:
+        """device_scaler: global L2 norm of the last step's UNSCALED gradient (before clipping; inf when it overflowed).  Reading it
+        waits for the GPU.  None without device_scaler."""
+        return None if self._ctl is None else float(self._ctl_f[self._ew.CTL_GRAD_NORM])
+
     def comm_stats(self):
         """Communication bookkeeping of the LAST step of this rank (bench.py --full puts it into the line for n_gpus > 1, DESIGN.md
         section 6): bytes handed to the gradient collectives, bytes of the parameter all-gather, number of collectives, and how many
@@ -359,7 +429,8 @@ class DiffusionTrainer:
                 "parameter_all_gather_send_bytes": int(gather),
                 "collectives_per_step": len(getattr(red, "launched", [])) * (2 if shard else 1),
                 "gradient_collectives_pending_when_backward_ended": int(getattr(red, "pending_at_finish", 0)),
-                "lazy_parameter_gather": bool(shard and getattr(self, "lazy_gather", False))}
+                "lazy_parameter_gather": bool(shard and getattr(self, "lazy_gather", False)),
+                "device_scaler": self._ctl is not None}
 
     def close(self):
         """Detach this trainer from the model: complete pending parameter gathers, remove its forward / state_dict hooks and the
@@ -420,20 +491,26 @@ class DiffusionTrainer:
             self.wait_params(off, off + n)
 
     def step(self, coords, feats, t=None, coords_noise=None, feats_noise=None):
-        if not self.native or self.iteration == 0:
+        if not self.native or (self.finished_iterations == 0 if self._ctl is not None else self.iteration == 0):
             self.flat.zero_grad()                 # afterwards the fused optimizer kernel leaves the gradients zeroed
         self.reducer.start_step()
         self.finished_iterations += 1
         dev_type = "cuda" if coords.is_cuda else "cpu"
         with torch.autocast(dev_type, dtype=self.dtype, enabled=self.dtype is not None):
             loss, sub, _ = self.model.compute_loss(coords, feats, t=t, coords_noise=coords_noise, feats_noise=feats_noise, **self._loss_kwargs)
-        (loss if self.loss_scale is None else loss * self.loss_scale).backward()
+        if self._ctl is not None:
+            (loss * self._scale_dev if self._scaling else loss).backward()
+        else:
+            (loss if self.loss_scale is None else loss * self.loss_scale).backward()
         self.apply_gradients()
         return loss.detach(), sub
 
     def apply_gradients(self):
         """Second half of an iteration: finish the gradient exchange, then AdamW + EMA on what the flat gradient buffer holds
         (diffusion_training.py:169-174).  step() calls this after backward."""
+        if self._ctl is not None:
+            self._apply_device_scaled()
+            return
         self.iteration += 1
         if self.native and self.reducer.shard:
             if self.reducer.finish(self._adamw_shard):
@@ -510,9 +587,60 @@ class DiffusionTrainer:
         ema = None if self.ema is None else self.ema[a:b]
         self._ew.adamw_ema(self.flat.flat[a:b], g, self.exp_avg[a:b], self.exp_avg_sq[a:b], ema, self.shadow[a:b], self.lr, self.betas[0],
                            self.betas[1], self.eps, self.weight_decay, self.iteration, self.ema_decay, zero_grad=False)
+        self._start_param_gather(s0, e0, a, b)
+
+    def _start_param_gather(self, s0, e0, a, b):
         mine = self.flat.flat[a:b].clone()            # out-of-place gather: the output range contains the input range
-        h = dist.all_gather_into_tensor(self.flat.flat[s0:e0], mine, group=red.group, async_op=True)
+        h = dist.all_gather_into_tensor(self.flat.flat[s0:e0], mine, group=self.reducer.group, async_op=True)
         self._pending[self._bucket_of[(s0, e0)]] = (h, mine, s0, e0)
+
+    # ---- device-side loss scaling / clipping (device_scaler) ---------------------------------------------------------------
+    def _apply_device_scaled(self):
+        """apply_gradients() without host waits: statistics of every gradient range into its slot (as its collective lands), one
+        finalize of the control record (skip decision, unscaled norm, clip coefficient, step count, next scale), then the gated
+        AdamW + EMA.  Sharded: the slots are all-reduced (one collective of a few hundred bytes) and the shard updates start after
+        the LAST reduce-scatter -- the skip decision and the norm are global -- each followed by its lazy parameter all-gather."""
+        red, ew = self.reducer, self._ew
+        if red.shard:
+            red.finish(self._stats_shard)
+            dist.all_reduce(self._stats, op=dist.ReduceOp.SUM, group=red.group)
+            ew.scaler_finalize(self._stats, len(red.buckets), self._ctl, self._scaling, self.max_grad_norm, *self.betas)
+            for b in red.launched:
+                self._adamw_shard_gated(*red.buckets[b])
+            self._finish_shards()
+            return
+        if red.finish(self._stats_range):
+            nslots = len(red.buckets)
+        else:
+            ew.grad_stats(self.flat.grad, self._stats[0], self._stats_work[0])
+            nslots = 1
+        ew.scaler_finalize(self._stats, nslots, self._ctl, self._scaling, self.max_grad_norm, *self.betas)
+        self._shadow_written()
+        ew.adamw_ema_gated(self.flat.flat, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.ema, self.shadow, self.lr, self.betas[0],
+                           self.betas[1], self.eps, self.weight_decay, self.ema_decay, self._ctl, zero_grad=False)
+        self._zero_accumulating()
+
+    def _stats_range(self, s0, e0):
+        """all-reduced bucket [s0, e0) (identical on every rank): its statistics into its slot"""
+        b = self._bucket_of[(s0, e0)]
+        self._ew.grad_stats(self.flat.grad[s0:e0], self._stats[b], self._stats_work[b])
+
+    def _stats_shard(self, s0, e0):
+        """reduce-scattered bucket [s0, e0): the statistics of this rank's shard into the bucket's slot"""
+        red = self.reducer
+        b = self._bucket_of[(s0, e0)]
+        self._ew.grad_stats(red.gshard[s0 // red.world:e0 // red.world], self._stats[b], self._stats_work[b])
+
+    def _adamw_shard_gated(self, s0, e0):
+        red = self.reducer
+        self.wait_params(s0, e0)
+        a, b = red.shard_range(s0, e0)
+        self._shadow_written()
+        ema = None if self.ema is None else self.ema[a:b]
+        self._ew.adamw_ema_gated(self.flat.flat[a:b], red.gshard[s0 // red.world:e0 // red.world], self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                                 ema, self.shadow[a:b], self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay,
+                                 self._ctl, zero_grad=False)
+        self._start_param_gather(s0, e0, a, b)
 
     def _finish_shards(self):
         if not self.lazy_gather:
