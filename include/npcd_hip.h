@@ -591,6 +591,35 @@ int npcd_split3_bf16(const float* x, const float* bias, void* out, int64_t rows,
 int npcd_add_ln_split3_bf16(const float* x, const float* o, const float* bias, const float* gamma, const float* beta, float* xnew,
                             void* out, int64_t rows, int W, float eps, void* stream);
 
+/* ---- fp32-class TRAINING of the denoiser's residual blocks (DiffusionTrainer(dtype="fp32_class")): every forward, data-gradient and
+ * weight-gradient product of a block as bf16 GEMMs over the three cross products hi*hi + lo*hi + hi*lo of split operands, fp32
+ * accumulation; LayerNorm, GELU, attention and every column sum in fp32.  All sums in a fixed order, no atomics.
+ * npcd_add_ln_split3_stats_bf16: npcd_add_ln_split3_bf16 that also writes the row statistics mean / rstd [rows] fp32 (the LayerNorm
+ *   backward reads them).
+ * npcd_split_weights_bf16: up to NPCD_SPLIT_WEIGHTS_MAX fp32 weights W [N, K] (the four Linear layers of a block) in one launch, each
+ *   to both split layouts: fwd [N, 3 K] = [Wh | Wh | Wl] (the forward product's operand) and dgrad [3 N, K] = [Wh ; Wh ; Wl] (the data
+ *   gradient's: [dyh | dyl | dyh] [3 N, K] = dyh Wh + dyl Wh + dyh Wl).  K % 8 == 0, 16-byte aligned pointers.
+ * npcd_ln_bwd_split3_bf16: the LayerNorm backward of npcd_ln_bwd_dt with an fp32 dy and, in place of the 16-bit dxb, the split
+ *   dx3 [T, 3 W] = [hi | lo | hi] of dx (may be NULL); dx and the column partials are computed exactly as there.
+ * npcd_split3_colsum_bf16: v = a [T, N] fp32, or with gelu != 0 v = a * gelu_erf'(h + bias) (the GELU backward: a = dg, h = the c_fc
+ *   output without its bias) -> out [T, 3 N] = [hi | lo | hi] of v, part [npcd_colsum_blocks(T)][N] fp32 column partials of v, finished
+ *   by npcd_colsum_finalize.  N % 8 == 0, 16-byte aligned pointers. */
+#define NPCD_SPLIT_WEIGHTS_MAX 8
+typedef struct NpcdSplitWeight {
+    const float* w; /* [N, K] fp32 */
+    void* fwd;      /* [N, 3 K] bf16 */
+    void* dgrad;    /* [3 N, K] bf16 */
+    int N, K;
+} NpcdSplitWeight;
+int npcd_add_ln_split3_stats_bf16(const float* x, const float* o, const float* bias, const float* gamma, const float* beta, float* xnew,
+                                  void* out, float* mean, float* rstd, int64_t rows, int W, float eps, void* stream);
+int npcd_split_weights_bf16(const NpcdSplitWeight* desc, int count, void* stream);
+int npcd_ln_bwd_split3_bf16(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                            const float* dres, float* dx, void* dx3, float* part_gamma, float* part_beta, float* part_col, int T, int W,
+                            void* stream);
+int npcd_split3_colsum_bf16(const float* a, const float* h, const float* bias, void* out, float* part, int T, int N, int gelu,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,13 +149,15 @@ static inline int ln_rows_per_wave(int T) {
     return 16;
 }
 
-template <class E, int NCH>
-__global__ __launch_bounds__(256, 2) void ln_bwd_kernel(const E* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
+// D: the type of dy (E, or fp32 in the fp32-class runs); SPLIT: dxb is the bf16 [T, 3 W] = [hi | lo | hi] of dx (npcd_ln_bwd_split3_bf16)
+// instead of the 16-bit copy -- dx itself and the column partials are the same operations either way
+template <class E, int NCH, class D = E, bool SPLIT = false>
+__global__ __launch_bounds__(256, 2) void ln_bwd_kernel(const D* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                      const float* __restrict__ dres, float* __restrict__ dx, E* __restrict__ dxb,
                                                      float* __restrict__ part_gamma, float* __restrict__ part_beta,
                                                      float* __restrict__ part_col, int T, int W, int rows_per_wave) {
-    using e4 = typename V<E>::x4;
+    using e4 = typename V<D>::x4;
     extern __shared__ __attribute__((aligned(16))) unsigned char dsmem[];
     float* red = reinterpret_cast<float*>(dsmem);  // [3][4 waves][W]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -216,7 +218,20 @@ __global__ __launch_bounds__(256, 2) void ln_bwd_kernel(const E* __restrict__ dy
                 f32x4 o = (gy[ch] - c1 - xh[ch] * c2) * rs;
                 if (dres) o += rA[ch];
                 *reinterpret_cast<f32x4*>(dx + base + c) = o;
-                if (dxb) *reinterpret_cast<e4*>(dxb + base + c) = from_f32<E>(o);
+                if (SPLIT && dxb) {
+                    bf16x4 hi, lo;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        hi[j] = (__bf16)o[j];
+                        lo[j] = (__bf16)(o[j] - (float)hi[j]);
+                    }
+                    __bf16* o3 = reinterpret_cast<__bf16*>(dxb) + 3 * base + c;
+                    *reinterpret_cast<bf16x4*>(o3) = hi;
+                    *reinterpret_cast<bf16x4*>(o3 + W) = lo;
+                    *reinterpret_cast<bf16x4*>(o3 + 2 * W) = hi;
+                } else if (dxb) {
+                    *reinterpret_cast<typename V<E>::x4*>(dxb + base + c) = from_f32<E>(o);
+                }
                 ac[ch] += o;
             }
         }
@@ -775,6 +790,29 @@ extern "C" int npcd_ln_bwd_dt(const void* dy, const float* x, const float* mean,
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
+extern "C" int npcd_ln_bwd_split3_bf16(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                       const float* dres, float* dx, void* dx3, float* part_gamma, float* part_beta, float* part_col, int T,
+                                       int W, void* stream) {
+    if (!dy || !x || !mean || !rstd || !gamma || !dx || T <= 0 || W <= 0) return NPCD_ERR_ARG;
+    if (W % 4 != 0 || W > 256 * kMaxChunks) return NPCD_ERR_UNSUPPORTED;
+    if (!al16(dy) || !al16(x) || !al16(gamma) || !al16(dx) || (dres && !al16(dres)) || (dx3 && !al16(dx3))) return NPCD_ERR_ARG;
+    const int nblk = npcd_ln_bwd_blocks(T);
+    const size_t lds = (size_t)3 * 4 * W * sizeof(float);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    static DynLds lds_attr;
+    NPCD_HIP_CHECK(lds_attr.ensure(reinterpret_cast<const void*>(ln_bwd_kernel<__bf16, 8, float, true>), 3 * 4 * 2048 * 4));
+#define NPCD_LAUNCH_LN_BWD3(NCH)                                                                                                        \
+    hipLaunchKernelGGL((ln_bwd_kernel<__bf16, NCH, float, true>), dim3(nblk), dim3(256), lds, st, dy, x, mean, rstd, gamma, dres, dx, \
+                       static_cast<__bf16*>(dx3), part_gamma, part_beta, part_col, T, W, ln_rows_per_wave(T))
+    if (W <= 256) NPCD_LAUNCH_LN_BWD3(1);
+    else if (W <= 512) NPCD_LAUNCH_LN_BWD3(2);
+    else if (W <= 1024) NPCD_LAUNCH_LN_BWD3(4);
+    else NPCD_LAUNCH_LN_BWD3(8);
+#undef NPCD_LAUNCH_LN_BWD3
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
+}
+
 extern "C" int npcd_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* dres,
                            float* dx, void* dxb, float* part_gamma, float* part_beta, float* part_col, int T, int W, void* stream) {
     return npcd_ln_bwd_dt(dy, x, mean, rstd, gamma, dres, dx, dxb, part_gamma, part_beta, part_col, T, W, NPCD_BF16, stream);

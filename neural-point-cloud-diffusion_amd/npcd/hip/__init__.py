@@ -123,6 +123,10 @@ SIGNATURES = {
     "npcd_eps_mse_bwd": (c_int, [_P, _P, c_int, c_int64, _P, _P, _P]),
     "npcd_split3_bf16": (c_int, [_P, _P, _P, c_int64, c_int, c_int, _P]),
     "npcd_add_ln_split3_bf16": (c_int, [_P] * 7 + [c_int64, c_int, c_float, _P]),
+    "npcd_add_ln_split3_stats_bf16": (c_int, [_P] * 9 + [c_int64, c_int, c_float, _P]),
+    "npcd_split_weights_bf16": (c_int, [_P, c_int, _P]),
+    "npcd_ln_bwd_split3_bf16": (c_int, [_P] * 11 + [c_int, c_int, _P]),
+    "npcd_split3_colsum_bf16": (c_int, [_P] * 5 + [c_int, c_int, c_int, _P]),
     "npcd_pair_mlp_wpack_bytes": (c_int64, [c_int, c_int]),
     "npcd_pair_mlp_pack": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, _P, _P]),
     "npcd_pair_mlp_fwd": (c_int, [_P, c_int, c_int] + [_P] * 5 + [c_int64, c_int, c_int64] + [_P] * 4 + [_P]),

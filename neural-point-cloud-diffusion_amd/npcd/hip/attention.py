@@ -124,6 +124,17 @@ def _f32_layout_ok(q, k, v):
             and q.data_ptr() % 16 == 0 and k.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0)
 
 
+def _bwd_f32(q, k, v, out, dout, lse, dq, dk, dv, scale):
+    """The fp32 attention backward (attn_bwd_f32_dq_kernel / attn_bwd_f32_dkdv_kernel) into given gradient views: dq / dk / dv share one
+    stride set (the q / k / v slices of one packed [B, n, H, 3 d] buffer in the fp32-class fused node), dout has out's strides."""
+    B, n, H, d = q.shape
+    assert q.stride() == k.stride() == v.stride() and dq.stride() == dk.stride() == dv.stride() and dout.stride() == out.stride()
+    delta = torch.empty(lib().npcd_attn_bwd_workspace_floats(B, n, H), dtype=torch.float32, device=q.device)
+    check(lib().npcd_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(dq), ptr(dk), ptr(dv), ptr(delta),
+                              B, n, H, d, q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2),
+                              dq.stride(0), dq.stride(1), dq.stride(2), scale, dtype_code(q), stream_ptr()), "npcd_attn_bwd(f32)")
+
+
 class _AttnF32(torch.autograd.Function):
     """fp32 attention with gradients (`--dtype float32` training, where the reference runs its einsum path in fp32,
     transformer.py:76-83).  Forward: the exact-fp32 HIP kernel (+ the log-sum-exp of every row); backward: the two fp32
@@ -148,11 +159,7 @@ class _AttnF32(torch.autograd.Function):
         B, n, H, d = q.shape
         gout = gout.contiguous()
         dq, dk, dv = (torch.empty((B, n, H, d), dtype=torch.float32, device=q.device) for _ in range(3))
-        delta = torch.empty(B * H * n, dtype=torch.float32, device=q.device)
-        check(lib().npcd_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(gout), ptr(lse), ptr(dq), ptr(dk), ptr(dv), ptr(delta),
-                                  B, n, H, d, q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2),
-                                  dq.stride(0), dq.stride(1), dq.stride(2), ctx.scale, dtype_code(q), stream_ptr()),
-              "npcd_attn_bwd(f32)")
+        _bwd_f32(q, k, v, out, gout, lse, dq, dk, dv, ctx.scale)
         return dq, dk, dv, None
 
 

@@ -279,6 +279,81 @@ def add_ln_split3(x, gamma, beta, o=None, bias=None, eps=1e-5):
     return (x if xnew is None else xnew), out
 
 
+# ---- fp32-class training of the residual blocks (csrc/split.hip, npcd_ln_bwd_split3_bf16 in csrc/elementwise.hip) ------------------------
+class SplitWeight(ctypes.Structure):
+    """NpcdSplitWeight (include/npcd_hip.h)."""
+    _fields_ = [("w", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgrad", ctypes.c_void_p), ("N", ctypes.c_int), ("K", ctypes.c_int)]
+
+
+def split_weights(ws):
+    """fp32 weights [N, K] (<= 8, contiguous) -> [(fwd [N, 3 K], dgrad [3 N, K]), ...] bf16, fwd = [Wh | Wh | Wl] and dgrad = [Wh ; Wh ; Wl]
+    (W = Wh + Wl), in ONE launch."""
+    require_gpu(*ws)
+    if not all(w.is_contiguous() and w.dtype == _f32 for w in ws):
+        raise RuntimeError("split_weights takes contiguous fp32 weights (the views of a trainer's flat parameter buffer)")
+    out = []
+    arr = (SplitWeight * len(ws))()
+    for a, w in zip(arr, ws):
+        N, K = w.shape
+        f, d = arena.empty((N, 3 * K), _bf16, w.device), arena.empty((3 * N, K), _bf16, w.device)
+        a.w, a.fwd, a.dgrad, a.N, a.K = w.data_ptr(), f.data_ptr(), d.data_ptr(), N, K
+        out.append((f, d))
+    check(lib().npcd_split_weights_bf16(ctypes.cast(arr, ctypes.c_void_p), len(ws), stream_ptr()), "npcd_split_weights_bf16")
+    return out
+
+
+def add_ln_split3_stats(x, gamma, beta, o=None, bias=None, eps=1e-5):
+    """add_ln_split3 that also returns the row statistics: (xnew or x, [T, 3 W] split of the LayerNorm output, mean [T], rstd [T])."""
+    require_gpu(x)
+    T, W = x.shape
+    if W % 256 or W // 256 not in (1, 2, 3, 4, 8, 16):
+        raise RuntimeError(f"npcd_add_ln_split3_stats_bf16 takes widths 256, 512, 768, 1024, 2048 and 4096 (got {W})")
+    x = x.contiguous()
+    out = arena.empty((T, 3 * W), _bf16, x.device)
+    mean, rstd = arena.empty(T, _f32, x.device), arena.empty(T, _f32, x.device)
+    xnew = None
+    if o is not None:
+        o, bias = o.contiguous(), bias.to(_f32).contiguous()
+        xnew = arena.empty_like(x)
+    check(lib().npcd_add_ln_split3_stats_bf16(ptr(x), ptr(o), ptr(bias), ptr(gamma.contiguous()), ptr(beta.contiguous()), ptr(xnew), ptr(out),
+                                              ptr(mean), ptr(rstd), T, W, float(eps), stream_ptr()), "npcd_add_ln_split3_stats_bf16")
+    return (x if xnew is None else xnew), out, mean, rstd
+
+
+def ln_bwd_split3(dy, x, mean, rstd, gamma, dres, dgamma_out, dbeta_out, dcol_out=None, want_split=True, batch=None):
+    """ln_bwd for an fp32 dy: dx (fp32) and, when asked, its split [T, 3 W] bf16 [hi | lo | hi] (the operand of the next data-gradient
+    product) -- (dx, dx3 or None).  The column sums as in ln_bwd."""
+    T, W = x.shape
+    dev = x.device
+    L = lib()
+    nblk = L.npcd_ln_bwd_blocks(T)
+    dx = arena.empty((T, W), _f32, dev)
+    dx3 = arena.empty((T, 3 * W), _bf16, dev) if want_split else None
+    parts = arena.empty((3, nblk + L.npcd_colsum_scratch_rows(), W), _f32, dev)
+    check(L.npcd_ln_bwd_split3_bf16(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx), ptr(dx3), ptr(parts[0]), ptr(parts[1]),
+                                    ptr(parts[2]) if dcol_out is not None else ptr(None), T, W, stream_ptr()), "npcd_ln_bwd_split3_bf16")
+    _finish(batch, parts[0], nblk, W, dgamma_out)
+    _finish(batch, parts[1], nblk, W, dbeta_out)
+    if dcol_out is not None:
+        _finish(batch, parts[2], nblk, W, dcol_out)
+    return dx, dx3
+
+
+def split3_colsum(a, colsum_out, h=None, bias=None, batch=None):
+    """v = a [T, N] fp32, or (h given: the GELU backward) v = a * gelu_erf'(h + bias)  ->  [T, 3 N] bf16 [hi | lo | hi] of v; colsum_out [N]
+    (fp32) = the column sum of v (a bias gradient) -- immediately, or at batch.flush()."""
+    require_gpu(a)
+    T, N = a.shape
+    L = lib()
+    nblk = L.npcd_colsum_blocks(T)
+    out = arena.empty((T, 3 * N), _bf16, a.device)
+    part = arena.empty((nblk + L.npcd_colsum_scratch_rows(), N), _f32, a.device)
+    b = None if bias is None else bias.to(_f32).contiguous()
+    check(L.npcd_split3_colsum_bf16(ptr(a), ptr(h), ptr(b), ptr(out), ptr(part), T, N, int(h is not None), stream_ptr()), "npcd_split3_colsum_bf16")
+    _finish(batch, part, nblk, N, colsum_out)
+    return out
+
+
 def ddpm_reverse_step(x_t, eps, noise, t, tables, clip=None, want_x0=False):
     """Fused reverse step of the sampler.  x_t / noise fp32 [B, ...], eps fp32 or bf16 (same shape), t int64 [B], tables = the five
     fp32 device tables (sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,

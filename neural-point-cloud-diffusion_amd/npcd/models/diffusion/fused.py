@@ -234,8 +234,10 @@ import contextlib
 _NULL = contextlib.nullcontext()
 
 
-class FusedBackboneEngine:
-    """Views into the flat fp32 parameter / gradient buffers and the bf16 shadow for every block."""
+class _BlockViews:
+    """What every fused backbone node of a trainer holds: per block the parameters, views of their fp32 masters and of their fp32
+    gradients in the trainer's flat buffers, the reducer, and the hooks of a trainer with lazily gathered parameters."""
+    fp32_class = False
 
     # the engine belongs to ONE trainer's flat buffers: a deep copy / pickle of the backbone carries None (the module path) instead
     def __deepcopy__(self, memo):
@@ -244,30 +246,45 @@ class FusedBackboneEngine:
     def __reduce__(self):
         return (_no_engine, ())
 
-    def __init__(self, backbone, flat, shadow, reducer=None):
+    def __init__(self, backbone, flat, reducer=None):
         self.heads = backbone.resblocks[0].attn.heads
         self.width = backbone.width
         self.reducer = reducer
-        offset = {id(p): off for p, off in zip(flat.params, flat.offsets)}
+        self._offset = {id(p): off for p, off in zip(flat.params, flat.offsets)}
         self.blocks = []
         for blk in backbone.resblocks:
             named = dict(blk.named_parameters())
             entry = {"params": [named[n] for n in _BLOCK_PARAMS]}
             for n in _BLOCK_PARAMS:
                 p = named[n]
-                off = offset[id(p)]
+                off = self._offset[id(p)]
                 key = n.replace(".", "_")
                 entry[key] = p.data                                              # fp32 master (LN affine is used in fp32)
-                entry[key + "_16"] = shadow[off:off + p.numel()].view_as(p)     # bf16 shadow (GEMM operands)
                 entry[key + "_g"] = flat.grad[off:off + p.numel()].view_as(p)   # fp32 gradient
             self.blocks.append(entry)
+        self.block_ranges, self.wait_range = None, None      # set by a trainer with lazily gathered parameters (engine.py)
+
+    def shadow_written(self):
+        pass
+
+
+class FusedBackboneEngine(_BlockViews):
+    """The 16-bit node (bf16, or f16 with loss scaling): the block views plus views of the 16-bit shadow of the flat parameters."""
+
+    def __init__(self, backbone, flat, shadow, reducer=None):
+        super().__init__(backbone, flat, reducer)
+        for blk, entry in zip(backbone.resblocks, self.blocks):
+            named = dict(blk.named_parameters())
+            for n in _BLOCK_PARAMS:
+                p = named[n]
+                off = self._offset[id(p)]
+                entry[n.replace(".", "_") + "_16"] = shadow[off:off + p.numel()].view_as(p)     # bf16 shadow (GEMM operands)
 
         # The GEMMs read the bf16 SHADOW, which only the optimizer kernel (and load_trainer_state) refresh.  Any other in-place
         # write to a parameter -- model.load_state_dict, copying EMA weights in to sample from them -- bumps the parameter's
         # version counter (the optimizer kernel writes through raw pointers and does not): the stamp below notices that and the
         # shadow is re-cast from the fp32 masters before the next forward instead of silently running stale Linear weights
         # beside fresh LayerNorm ones.
-        self.block_ranges, self.wait_range = None, None      # set by a trainer with lazily gathered parameters (engine.py)
         self._flat, self._shadow = flat, shadow
         self.dtype = shadow.dtype                            # the run's 16-bit activation type: bf16, or f16 (with loss scaling)
         self._stamped = [p for e in self.blocks for p in e["params"]]
@@ -584,4 +601,180 @@ class _BackboneFn(torch.autograd.Function):
             if side:
                 _wgrad_join(dx.device)
                 ready(eng.blocks[0])
+        return dx.view(B, n, W), None
+
+
+# ---- fp32-class training: DiffusionTrainer(dtype="fp32_class") ---------------------------------------------------------------------------
+# The reference's --dtype float32 (train_diffusion.py:78) on the bf16 matrix rate: every product of a block -- forward, data gradient and
+# weight gradient -- is ONE bf16 GEMM (or, for a weight gradient, three) over the three cross products hi*hi + lo*hi + hi*lo of split
+# operands (x = hi + lo, bf16 halves) with fp32 accumulation; the residual stream, LayerNorm, attention (the exact-fp32 kernels), GELU
+# (exact erf) and every bias / LayerNorm-affine column sum in fp32.  The split weights are built from the fp32 masters inside the forward,
+# block by block, right behind the wait for that block's parameters: nothing is cached between steps, so a lazily gathered parameter,
+# load_state_dict or an EMA copy-in can never leave a stale operand behind.
+SPLIT_WIDTHS = (256, 512, 768, 1024, 2048)          # add_ln_split3 (W / 256 in 1, 2, 3, 4, 8, 16) and the LayerNorm backward (W <= 2048)
+_X2_LINEARS = ("attn_c_qkv", "attn_c_proj", "mlp_c_fc", "mlp_c_proj")
+
+
+def x2_supported(width, heads):
+    """None, or why DiffusionTrainer(dtype="fp32_class") cannot train a backbone of this width / head count."""
+    if heads <= 0 or width % heads or width // heads != 64:
+        return (f"head dim {width // heads if heads > 0 and width % heads == 0 else width / max(heads, 1)}: the fp32 attention backward "
+                f"is built for head dim 64 only")
+    if width not in SPLIT_WIDTHS:
+        return f"width {width}: the split-operand kernels take widths {', '.join(map(str, SPLIT_WIDTHS))}"
+    return None
+
+
+def _mm_x2(a3, w3):
+    """[T, 3 K] bf16 x [3 K, N] bf16 (a transposed forward layout or a data-gradient layout) -> [T, N] fp32."""
+    return torch.mm(a3, w3, out_dtype=_f32)
+
+
+def _wgrad_x2(dy3, x3, out):
+    """out [N, K] fp32 = dy^T x from the split operands dy3 [T, 3 N] = [dyh | dyl | dyh], x3 [T, 3 K] = [xh | xl | xh]: the three cross
+    products as library GEMMs on strided views -- (dyh, xl) and (dyl, xh) as one batched call (slice strides N and K), (dyh, xh) as one
+    more -- into fp32 slabs, added in a fixed order."""
+    T, N = dy3.shape[0], out.shape[0]
+    K = out.shape[1]
+    d, x = dy3.view(T, 3, N), x3.view(T, 3, K)
+    part = harena.empty((3, N, K), _f32, out.device)
+    torch.bmm(d[:, 0:2].permute(1, 2, 0), x[:, 1:3].permute(1, 0, 2), out_dtype=_f32, out=part[0:2])
+    torch.mm(d[:, 0].t(), x[:, 0], out_dtype=_f32, out=part[2])
+    torch.sum(part, dim=0, out=out)
+
+
+# The form of the weight gradients (A/B switch, NPCD_X2_WGRAD): "library" = _wgrad_x2 above; "own" = the own kernels of csrc/gemm.hip on
+# the operands stacked along the token dimension -- dy [dyh ; dyl ; dyh] and x [xl ; xh ; xh], [3 T, N] / [3 T, K], one reduction over
+# 3 T rows (the four products of a block in one npcd_wgrad_group launch up to _WGRAD_GROUP_MAX_T rows, else npcd_wgrad per product).
+_X2_WGRAD = os.environ.get("NPCD_X2_WGRAD", "library")
+if _X2_WGRAD not in ("library", "own"):
+    raise ValueError(f"NPCD_X2_WGRAD={_X2_WGRAD!r}: expected library or own")
+
+
+def _stack_x2(a3, lo_first):
+    """[T, 3 N] = [hi | lo | hi] -> [3 T, N] bf16 stacked along the tokens: [hi ; lo ; hi], or (lo_first) [lo ; hi ; hi]."""
+    T, N = a3.shape[0], a3.shape[1] // 3
+    v = a3.view(T, 3, N)
+    out = harena.empty((3, T, N), _bf16, a3.device)
+    if lo_first:
+        out[0].copy_(v[:, 1])
+        out[1:].copy_(v[:, 0::2].transpose(0, 1))
+    else:
+        out.copy_(v.transpose(0, 1))
+    return out.view(3 * T, N)
+
+
+def _wgrad_own(pending):
+    """The queued weight gradients of a block, (dy3, x3, out) each, on the own kernels (see _X2_WGRAD)."""
+    triples = [(_stack_x2(dy3, False), _stack_x2(x3, True), out) for dy3, x3, out in pending]
+    pending.clear()
+    if triples[0][0].shape[0] <= _WGRAD_GROUP_MAX_T:
+        ok = ew.wgrad_group(triples)
+    else:
+        ok = all(ew.wgrad(dy, x, out) for dy, x, out in triples)
+    if not ok:
+        raise RuntimeError("fp32-class weight gradients: the own kernels do not take these shapes (NPCD_X2_WGRAD=library does)")
+
+
+class FusedBackboneEngineX2(_BlockViews):
+    """The fused backbone node in the fp32 class: the block views only -- no 16-bit shadow (the split weights are derived from the fp32
+    masters in every forward), no step arena.  transformer.py routes on `fp32_class`: grad enabled, autocast off."""
+    fp32_class = True
+
+    def __init__(self, backbone, flat, reducer=None):
+        why = x2_supported(backbone.width, backbone.resblocks[0].attn.heads)
+        if why is not None:
+            raise ValueError(f"fp32_class training: {why}")
+        super().__init__(backbone, flat, reducer)
+
+    def __call__(self, x):
+        return _BackboneX2Fn.apply(x, self)
+
+
+class _BackboneX2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, eng):
+        B, n, W = x.shape
+        T, H = B * n, eng.heads
+        d = W // H
+        scale = 1.0 / math.sqrt(d)
+        saved = []
+        with torch.autocast("cuda", enabled=False):
+            xs = x.reshape(T, W).contiguous().float()
+            o, ob = None, None               # the previous block's mlp.c_proj output and bias: added by the next LayerNorm kernel
+            for bi, e in enumerate(eng.blocks):
+                if eng.wait_range is not None:
+                    eng.wait_range(*eng.block_ranges[bi])        # this block's parameters (gathered lazily by the sharded optimizer)
+                split = dict(zip(_X2_LINEARS, ew.split_weights([e[k + "_weight"] for k in _X2_LINEARS])))
+                x_cur, y1, mean1, rstd1 = ew.add_ln_split3_stats(xs, e["ln_1_weight"], e["ln_1_bias"], o, ob)
+                qkv = _mm_x2(y1, split["attn_c_qkv"][0].t()).add_(e["attn_c_qkv_bias"])
+                q4 = qkv.view(B, n, H, 3 * d)
+                a, lse = hattn._fwd_f32(q4[..., :d], q4[..., d:2 * d], q4[..., 2 * d:], scale, want_lse=True)
+                a = a.view(T, W)
+                o = _mm_x2(ew.split3(a), split["attn_c_proj"][0].t())
+                x2, y2, mean2, rstd2 = ew.add_ln_split3_stats(x_cur, e["ln_2_weight"], e["ln_2_bias"], o, e["attn_c_proj_bias"])
+                h = _mm_x2(y2, split["mlp_c_fc"][0].t())                  # without its bias: the split kernels add it
+                o, ob = _mm_x2(ew.split3(h, bias=e["mlp_c_fc_bias"], gelu=True), split["mlp_c_proj"][0].t()), e["mlp_c_proj_bias"]
+                # (the split GELU output is rebuilt from h in the backward; only the data-gradient layouts of the weights are kept)
+                saved.append((x_cur, mean1, rstd1, y1, qkv, a, lse, x2, mean2, rstd2, y2, h, {k: v[1] for k, v in split.items()}))
+                del split
+                xs = x2
+            out = xs + o + ob
+        ctx.eng, ctx.saved, ctx.dims, ctx.scale = eng, saved, (B, n, W, H, d), scale
+        return out.view(B, n, W)
+
+    @staticmethod
+    def backward(ctx, dout):
+        if any(s is None for s in ctx.saved):
+            raise RuntimeError("the fused backbone engine does not support retain_graph / double backward: run a new forward "
+                               "for every backward")
+        eng, (B, n, W, H, d), scale = ctx.eng, ctx.dims, ctx.scale
+        T = B * n
+        with torch.autocast("cuda", enabled=False):
+            dx = dout.reshape(T, W).contiguous().float()
+            eng.blocks[-1]["mlp_c_proj_bias_g"].copy_(dx.sum(dim=0))
+            dx3 = ew.split3(dx)
+            reducing = eng.reducer is not None and eng.reducer.active
+            for bi in range(len(eng.blocks) - 1, -1, -1):
+                e = eng.blocks[bi]
+                x_cur, mean1, rstd1, y1, qkv, a, lse, x2, mean2, rstd2, y2, h, wd = ctx.saved[bi]
+                ctx.saved[bi] = None
+                sums = ew.ColsumBatch()            # this block's 8 bias / LN-affine column sums: one finalize
+                pending = []
+                wg = (lambda *t: pending.append(t)) if _X2_WGRAD == "own" else _wgrad_x2
+                # ---- MLP branch: x3 = x2 + c_proj(gelu(c_fc(ln_2(x2)))) ------------------------------
+                dg = _mm_x2(dx3, wd["mlp_c_proj"])
+                wg(dx3, ew.split3(h, bias=e["mlp_c_fc_bias"], gelu=True), e["mlp_c_proj_weight_g"])
+                dh3 = ew.split3_colsum(dg, e["mlp_c_fc_bias_g"], h=h, bias=e["mlp_c_fc_bias"], batch=sums)
+                del dg, h
+                dy2 = _mm_x2(dh3, wd["mlp_c_fc"])
+                wg(dh3, y2, e["mlp_c_fc_weight_g"])
+                del dh3, y2
+                dx2, dx2_3 = ew.ln_bwd_split3(dy2, x2, mean2, rstd2, e["ln_2_weight"], dx, e["ln_2_weight_g"], e["ln_2_bias_g"],
+                                              e["attn_c_proj_bias_g"], batch=sums)
+                del dy2, x2, dx, dx3
+                # ---- attention branch: x2 = x + c_proj(attn(c_qkv(ln_1(x)))) ---------------------------
+                da = _mm_x2(dx2_3, wd["attn_c_proj"])
+                wg(dx2_3, ew.split3(a), e["attn_c_proj_weight_g"])
+                del dx2_3
+                dqkv = torch.empty_like(qkv)
+                q4, g4, a4 = qkv.view(B, n, H, 3 * d), dqkv.view(B, n, H, 3 * d), a.view(B, n, H, d)
+                hattn._bwd_f32(q4[..., :d], q4[..., d:2 * d], q4[..., 2 * d:], a4, da.view(B, n, H, d), lse,
+                               g4[..., :d], g4[..., d:2 * d], g4[..., 2 * d:], scale)
+                del da, a, qkv, lse
+                dqkv3 = ew.split3_colsum(dqkv, e["attn_c_qkv_bias_g"], batch=sums)
+                del dqkv
+                dy1 = _mm_x2(dqkv3, wd["attn_c_qkv"])
+                wg(dqkv3, y1, e["attn_c_qkv_weight_g"])
+                del dqkv3, y1
+                prev_bias_g = eng.blocks[bi - 1]["mlp_c_proj_bias_g"] if bi > 0 else None
+                dx, dx3 = ew.ln_bwd_split3(dy1, x_cur, mean1, rstd1, e["ln_1_weight"], dx2, e["ln_1_weight_g"], e["ln_1_bias_g"],
+                                           prev_bias_g, want_split=bi > 0, batch=sums)
+                del dy1, dx2
+                if pending:
+                    _wgrad_own(pending)
+                sums.flush()
+                if reducing:
+                    for p in e["params"]:          # this block's gradients are final (mlp.c_proj.bias: by the block above / the tail)
+                        eng.reducer.mark_ready(p)
         return dx.view(B, n, W), None

@@ -107,6 +107,14 @@ class Transformer(nn.Module):
 
     def forward(self, x):
         eng = self.fused_engine
+        if eng is not None and eng.fp32_class:
+            if x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled() and not torch.is_autocast_enabled():
+                return eng(x)           # training in the fp32 class (DiffusionTrainer(dtype="fp32_class"): fused.FusedBackboneEngineX2)
+            # every other forward (sampling / evaluation in any precision) runs as for a model without a trainer -- the fp32-class node
+            # keeps no 16-bit shadow -- once the trainer's pending parameter gathers are complete
+            if eng.wait_range is not None:
+                eng.wait_range()
+            eng = None
         if x.is_cuda and x.dtype == torch.float32 and torch.is_autocast_enabled():
             act = torch.get_autocast_dtype("cuda")
             if torch.is_grad_enabled():

@@ -50,6 +50,23 @@ class _ParamWaitHook:
         return (_ParamWaitHook, (None, self.kind))
 
 
+def _check_fp32_class(diffusion, fused):
+    """ValueError unless DiffusionTrainer(dtype="fp32_class") can train `diffusion` on its fused fp32-class node."""
+    denoiser = getattr(diffusion, "denoiser", None)
+    params = [p for p in diffusion.parameters() if p.requires_grad]
+    if not fused:
+        raise ValueError('dtype="fp32_class" trains on the fused HIP node: it needs fused=True')
+    if denoiser is None or not hasattr(denoiser, "backbone"):
+        raise ValueError('dtype="fp32_class" needs a DiffusionModel with a transformer denoiser')
+    from ..models.diffusion.fused import x2_supported
+    bb = denoiser.backbone
+    why = x2_supported(bb.width, bb.resblocks[0].attn.heads)
+    if why is not None:
+        raise ValueError(f'dtype="fp32_class": {why}')
+    if not params or not params[0].is_cuda:
+        raise ValueError('dtype="fp32_class" trains on the fused HIP node: move the model to the GPU first (got a CPU model)')
+
+
 class FlatBuffers:
     """Re-home the trainable parameters of `module` into one flat buffer (+ flat grads)."""
     ALIGN = 256
@@ -240,10 +257,19 @@ class DiffusionTrainer:
         with them under device_scaler): ZeRO-1 style -- reduce-scatter instead of all-reduce, each rank runs AdamW + EMA on 1/world
         of every bucket, the updated parameters are all-gathered.  Same bytes on the wire as the all-reduce, optimizer pass divided
         by the number of ranks.
+        dtype: torch.bfloat16 / torch.float16 (autocast; float16 with loss scaling), None (fp32, the module path), or "fp32_class": no
+        autocast, the glue around the backbone in fp32 torch, the residual blocks on the fused node in the fp32 class (every product of a
+        block as bf16 GEMMs over the three cross products of split operands, fp32 accumulation: npcd.models.diffusion.fused,
+        FusedBackboneEngineX2).  Needs a GPU model, fused=True, head dim 64 and a width in fused.SPLIT_WIDTHS (ValueError otherwise).
         device_scaler (or NPCD_DEVICE_SCALER=1): float16 loss scaling and gradient clipping without any host wait -- the overflow
         check, the global gradient norm, the skip decision, the scale update and the AdamW step count live in a control record in
         device memory that the optimizer kernel reads.  Native path only (ValueError otherwise)."""
         self._ctl = None                   # device-side loss-scaler record (device_scaler); None: the host keeps the bookkeeping
+        self.fp32_class = isinstance(dtype, str) and dtype == "fp32_class"
+        if isinstance(dtype, str) and not self.fp32_class:
+            raise ValueError(f"dtype={dtype!r}: expected torch.bfloat16, torch.float16, None or \"fp32_class\"")
+        if self.fp32_class:
+            _check_fp32_class(diffusion, fused)
         self.model = diffusion
         self.dtype = dtype
         # the training loop never looks at the pointwise losses: this package's DiffusionModel can skip materialising them
@@ -282,12 +308,18 @@ class DiffusionTrainer:
             self.exp_avg_sq = torch.zeros_like(self.flat.flat)
             # the 16-bit shadow the GEMMs read is kept in the run's autocast type: bf16, or f16 (the reference's default --dtype,
             # train_diffusion.py:78 -- trained with the loss scaling below); any other dtype trains through the module path
+            # (fp32_class: no shadow -- its node splits the fp32 masters itself in every forward -- and the optimizer writes none)
             half = dtype if dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
-            self.shadow = torch.empty(self.flat.numel, dtype=half, device=self.flat.flat.device)
-            ew.cast_f32_bf16(self.flat.flat, self.shadow)
+            self.shadow = None if self.fp32_class else torch.empty(self.flat.numel, dtype=half, device=self.flat.flat.device)
+            if self.shadow is not None:
+                ew.cast_f32_bf16(self.flat.flat, self.shadow)
             denoiser = getattr(diffusion, "denoiser", None)
             fused_ids = set()
-            if (denoiser is not None and dtype in (torch.bfloat16, torch.float16)
+            if self.fp32_class:
+                from ..models.diffusion.fused import FusedBackboneEngineX2
+                denoiser.backbone.fused_engine = FusedBackboneEngineX2(denoiser.backbone, self.flat, self.reducer)
+                fused_ids = {id(p) for e in denoiser.backbone.fused_engine.blocks for p in e["params"]}
+            elif (denoiser is not None and dtype in (torch.bfloat16, torch.float16)
                     and denoiser.backbone.width // denoiser.backbone.resblocks[0].attn.heads == 64):
                 denoiser.backbone.fused_engine = FusedBackboneEngine(denoiser.backbone, self.flat, self.shadow, self.reducer)
                 fused_ids = {id(p) for e in denoiser.backbone.fused_engine.blocks for p in e["params"]}
@@ -472,8 +504,9 @@ class DiffusionTrainer:
         for b in [b for b, (_, _, s0, e0) in pend.items() if s0 < hi and e0 > lo]:
             h, _, s0, e0 = pend.pop(b)
             h.wait()
-            self._ew.cast_f32_bf16(self.flat.flat[s0:e0], self.shadow[s0:e0])
-            self._shadow_written()
+            if self.shadow is not None:
+                self._ew.cast_f32_bf16(self.flat.flat[s0:e0], self.shadow[s0:e0])
+                self._shadow_written()
 
     def _await_params_for_forward(self, module, args):
         """forward-pre-hook of the denoiser.  The fused training forward asks for its blocks one by one (so that the gathers of
@@ -482,8 +515,13 @@ class DiffusionTrainer:
         f16, sampling) gets everything."""
         if not getattr(self, "_pending", None):
             return
-        fused_training = (self._fused_engine is not None and torch.is_grad_enabled() and torch.is_autocast_enabled()
-                          and torch.get_autocast_dtype("cuda") == self._fused_engine.dtype and args and args[0].is_cuda)
+        eng = self._fused_engine
+        if eng is not None and getattr(eng, "fp32_class", False):
+            # the fp32-class node: entered with grad enabled and autocast off (transformer.py)
+            fused_training = torch.is_grad_enabled() and not torch.is_autocast_enabled() and bool(args) and args[0].is_cuda
+        else:
+            fused_training = (eng is not None and torch.is_grad_enabled() and torch.is_autocast_enabled()
+                              and torch.get_autocast_dtype("cuda") == eng.dtype and args and args[0].is_cuda)
         if not fused_training:
             self.wait_params()
             return
@@ -496,7 +534,8 @@ class DiffusionTrainer:
         self.reducer.start_step()
         self.finished_iterations += 1
         dev_type = "cuda" if coords.is_cuda else "cpu"
-        with torch.autocast(dev_type, dtype=self.dtype, enabled=self.dtype is not None):
+        amp = None if self.fp32_class else self.dtype          # fp32_class: no autocast (the glue runs in fp32)
+        with torch.autocast(dev_type, dtype=amp, enabled=amp is not None):
             loss, sub, _ = self.model.compute_loss(coords, feats, t=t, coords_noise=coords_noise, feats_noise=feats_noise, **self._loss_kwargs)
         if self._ctl is not None:
             (loss * self._scale_dev if self._scaling else loss).backward()
@@ -558,6 +597,9 @@ class DiffusionTrainer:
             self._clean_steps = 0
         return True
 
+    def _shadow_range(self, s0, e0):
+        return None if self.shadow is None else self.shadow[s0:e0]
+
     def _shadow_written(self):
         eng = getattr(self, "_fused_engine", None)
         if eng is not None:
@@ -567,7 +609,7 @@ class DiffusionTrainer:
         self._shadow_written()
         ema = None if self.ema is None else self.ema[s0:e0]
         self._ew.adamw_ema(self.flat.flat[s0:e0], self.flat.grad[s0:e0], self.exp_avg[s0:e0], self.exp_avg_sq[s0:e0], ema,
-                           self.shadow[s0:e0], self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.iteration,
+                           self._shadow_range(s0, e0), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.iteration,
                            self.ema_decay, zero_grad=zero_grad)
 
     def _zero_accumulating(self):
@@ -585,7 +627,7 @@ class DiffusionTrainer:
         g = red.gshard[s0 // red.world:e0 // red.world]
         self._shadow_written()
         ema = None if self.ema is None else self.ema[a:b]
-        self._ew.adamw_ema(self.flat.flat[a:b], g, self.exp_avg[a:b], self.exp_avg_sq[a:b], ema, self.shadow[a:b], self.lr, self.betas[0],
+        self._ew.adamw_ema(self.flat.flat[a:b], g, self.exp_avg[a:b], self.exp_avg_sq[a:b], ema, self._shadow_range(a, b), self.lr, self.betas[0],
                            self.betas[1], self.eps, self.weight_decay, self.iteration, self.ema_decay, zero_grad=False)
         self._start_param_gather(s0, e0, a, b)
 
@@ -638,7 +680,7 @@ class DiffusionTrainer:
         self._shadow_written()
         ema = None if self.ema is None else self.ema[a:b]
         self._ew.adamw_ema_gated(self.flat.flat[a:b], red.gshard[s0 // red.world:e0 // red.world], self.exp_avg[a:b], self.exp_avg_sq[a:b],
-                                 ema, self.shadow[a:b], self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay,
+                                 ema, self._shadow_range(a, b), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay,
                                  self._ctl, zero_grad=False)
         self._start_param_gather(s0, e0, a, b)
 
