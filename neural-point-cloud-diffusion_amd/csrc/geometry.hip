@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include <stdlib.h>
+#include <type_traits>
 
 #include "common.h"
 
@@ -34,7 +35,7 @@ __device__ __forceinline__ float fkey_inv(uint32_t k) {
 
 // One camera ray and its limits against the cube [-box, box]^3: E = world2cam [4 x 4], K = intrinsics [3 x 3], `ray` = row-major pixel
 // number.  tmin = -1, tmax = -2 for a ray that misses.  Shared by ray_gen_kernel and the fused query of a render
-// (grid_query_wave_kernel with QueryArgs::extr): the same operations in the same order, i.e. the same bits.
+// (grid_query_wave_kernel<true, true>, which takes the cameras in a RenderRays): the same operations in the same order, i.e. the same bits.
 __device__ __forceinline__ void gen_ray(const float* __restrict__ E, const float* __restrict__ K, int res, float box, int ray, float (&o)[3],
                                         float (&d)[3], float& tmin, float& tmax) {
     tmin = -1.f;
@@ -274,15 +275,19 @@ struct QueryArgs {
     float* sample_loc;
     int32_t* slot_sample;
     int32_t* nsel;
-    int rpw;                // rays per wave of grid_query_wave_kernel (0 / 1: one)
-    // fused ray generation (npcd_render_rays_query; round 6): when extr is set the kernel computes its ray from the camera of view
-    // r / (res res) of example b instead of reading rays_o / rays_d / t0 / t1, and lane 0 writes it to gen_* for the later stages
-    // (t0 = -1, t1 = -2 for a ray that misses the cube: the march substitutes the global end, see ray_march_wave_kernel)
+};
+
+// Fused ray generation (npcd_render_rays_query; round 6), the extra argument of grid_query_wave_kernel<true, true> alone: the kernel computes
+// its ray from the camera of view r / (res res) of example b instead of reading QueryArgs::rays_o .. t1, and lane 0 writes it to gen_* for the
+// later stages (t0 = -1, t1 = -2 for a ray that misses the cube: the march substitutes the global end, see ray_march_wave_kernel<true, true>)
+struct RenderRays {
     const float *extr, *intr;
-    int res, views;         // pixels per image edge, views per example (R = views * res * res)
+    int views, res;         // views per example, pixels per image edge (R = views * res * res)
     float box;
     float *gen_o, *gen_d, *gen_t0, *gen_t1;
+    uint32_t* lim_part;     // (host side: becomes CompactOut::lim_part)
 };
+struct Unused {};           // what a kernel form without the fused extras takes in their place
 
 // position of depth sample s of a ray: renderer.py:49-77 (eval) + volume_renderer.py:70
 __device__ __forceinline__ void sample_pos(const QueryArgs& a, int64_t ray, int s, const float o[3], const float d[3], float t0, float t1, float p[3]) {
@@ -454,55 +459,70 @@ struct CompactOut {
     uint32_t* lim_part;   // [2 * ceil(B R / 64)] or nullptr
 };
 
-template <bool COMPACT>
-__global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, CompactOut co, int blocks_per_example) {
+// The dynamic LDS of a grid_query_wave_kernel workgroup (four waves, one ray each), as byte offsets: the one description that the
+// kernel and both of its launches use.  [4][64] arrays are wave-private rows of 64 slots.  The cloud, pts [N], is at 0.
+struct QueryLds {
+    int N, nwords;
+    static constexpr size_t kSel = 4 * 64 * 4, kSelp = 4 * 64 * 16, kCpk = 4 * 64 * 8, kStageIdx = 4 * 64 * 8 * 4, kStagePos = 4 * 64 * 4 * 4;
+    constexpr size_t bitmap() const { return (size_t)N * 16; }                      // [nwords] occupancy of the coarse voxels
+    constexpr size_t sel() const { return bitmap() + (size_t)nwords * 4; }          // [4][64] ids of the selected samples
+    // [4][64] float4 position + packed cell (x | y << 10 | z << 20) of the selected samples: stage 2 used to recompute both, ~80 instructions
+    constexpr size_t selp() const { return (sel() + kSel + 15) / 16 * 16; }
+    constexpr size_t cpk() const { return selp() + kSelp; }                         // [4][64] a slot pair's in-radius candidates, packed
+    // [4][64][8] neighbour rows, [4][64][4] positions of a ray's slots until they are written out (COMPACT; unused but allocated otherwise)
+    constexpr size_t stage_idx() const { return cpk() + kCpk; }
+    constexpr size_t stage_pos() const { return stage_idx() + kStageIdx; }
+    constexpr size_t bytes() const { return sel() + kSel + 16 + kSelp + kCpk + kStageIdx + kStagePos; }      // (16: room for selp's alignment)
+    constexpr bool is_old_layout() const {      // the layout of rounds 3-6, as the kernel and each launch used to spell it
+        const size_t sel_end = (size_t)N * 16 + (size_t)nwords * 4 + 4 * 64 * 4;
+        return selp() == sel_end + ((16 - (sel_end & 15)) & 15) && bytes() == sel_end + 16 + 4 * 64 * 16 + 4 * 64 * 8 + 4 * 64 * 8 * 4 + 4 * 64 * 4 * 4;
+    }
+};
+static_assert(QueryLds{64, 1}.is_old_layout() && QueryLds{64, 1024}.is_old_layout() && QueryLds{512, 2}.is_old_layout() &&
+              QueryLds{512, 1027}.is_old_layout() && QueryLds{2048, 3}.is_old_layout() && QueryLds{2048, 4096}.is_old_layout());
+
+// COMPACT: the fused render's compact lists (CompactOut) instead of the dense [ray][slot] arrays of QueryArgs.
+// FUSED_RAYS: the rays come from the cameras in `rr` (RenderRays) and are written out; otherwise they are read from QueryArgs.
+template <bool COMPACT, bool FUSED_RAYS = false>
+__global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, CompactOut co, int blocks_per_example,
+                                                              std::conditional_t<FUSED_RAYS, RenderRays, Unused> rr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dsmem[];
-    float4* pts = reinterpret_cast<float4*>(dsmem);
-    uint32_t* bitmap = reinterpret_cast<uint32_t*>(pts + a.N);
-    int* sel = reinterpret_cast<int*>(bitmap + a.nwords);          // [4][64]
-    // [4][64] position + packed cell (x | y << 10 | z << 20) of every selected sample, written by pass A: pass B used to
-    // recompute both per sample on all 64 lanes (two IEEE divisions per axis: ~80 of its ~300 instructions per trip)
-    float4* selp = reinterpret_cast<float4*>(reinterpret_cast<unsigned char*>(sel + 4 * 64) + ((16 - ((a.N * 16 + a.nwords * 4 + 4 * 64 * 4) & 15)) & 15));
-    unsigned long long* cpk = reinterpret_cast<unsigned long long*>(selp + 4 * 64);   // [4][64] a slot pair's in-radius candidates, packed
-    int* stage_idx = reinterpret_cast<int*>(cpk + 4 * 64);          // [4][64][8]   (COMPACT)
-    float* stage_pos = reinterpret_cast<float*>(stage_idx + 4 * 64 * 8);  // [4][64][4]
+    const QueryLds lds{a.N, a.nwords};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x / blocks_per_example;
-    const int rb = blockIdx.x % blocks_per_example;
+    const int b = blockIdx.x / blocks_per_example, rb = blockIdx.x % blocks_per_example;
+    float4* pts = reinterpret_cast<float4*>(dsmem);
+    uint32_t* bitmap = reinterpret_cast<uint32_t*>(dsmem + lds.bitmap());
+    int* mysel = reinterpret_cast<int*>(dsmem + lds.sel()) + wave * 64;                 // this wave's rows of the [4][64] arrays
+    float4* myselp = reinterpret_cast<float4*>(dsmem + lds.selp()) + wave * 64;
+    unsigned long long* mycpk = reinterpret_cast<unsigned long long*>(dsmem + lds.cpk()) + wave * 64;
     for (int j = tid; j < a.N; j += blockDim.x) {
         const float* P = a.points + ((int64_t)b * a.N + j) * 3;
         pts[j] = make_float4(P[0], P[1], P[2], __int_as_float(a.pcoord[(int64_t)b * a.N + j]));
     }
     for (int w = tid; w < a.nwords; w += blockDim.x) bitmap[w] = a.occ[(int64_t)b * a.nwords + w];
     __syncthreads();
-    // a.rpw rays per wave, one after the other (round 6 experiment, default 1: more than one measured slower, see the launch code).
-    // Every ray is computed by the same code on wave-private LDS: the lists are the same bits whatever rpw is.
-    const int rpw = a.rpw > 0 ? a.rpw : 1;
-    for (int rr = 0; rr < rpw; ++rr) {
-    const int r = (rb * rpw + rr) * 4 + wave;
-    if (r >= a.R) break;
+    // From here on every wave works on its own ray and its own rows of LDS, in three stages.
+    const int r = rb * 4 + wave;
+    if (r >= a.R) return;
     const int64_t ray = (int64_t)b * a.R + r;
     float o[3] = {0, 0, 0}, d[3] = {0, 0, 0}, t0 = 0, t1 = 0;
     bool ray_hits = true;
-    if (a.extr) {
+    if constexpr (FUSED_RAYS) {
         // the ray of pixel r % (res res) of view r / (res res) of this example, computed by every lane (wave-uniform values)
-        const int rv = a.res * a.res, view = b * a.views + r / rv;
-        gen_ray(a.extr + view * 16, a.intr + view * 9, a.res, a.box, r % rv, o, d, t0, t1);
+        const int rv = rr.res * rr.res, view = b * rr.views + r / rv;
+        gen_ray(rr.extr + view * 16, rr.intr + view * 9, rr.res, rr.box, r % rv, o, d, t0, t1);
         ray_hits = t1 > t0;           // a ray that misses the cube has no sample inside the grid's range (the launch checks box >= range)
         if (lane == 0) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { a.gen_o[ray * 3 + c] = o[c]; a.gen_d[ray * 3 + c] = d[c]; }
-            a.gen_t0[ray] = t0;
-            a.gen_t1[ray] = t1;
+            for (int c = 0; c < 3; ++c) { rr.gen_o[ray * 3 + c] = o[c]; rr.gen_d[ray * 3 + c] = d[c]; }
+            rr.gen_t0[ray] = t0; rr.gen_t1[ray] = t1;
         }
     } else if (!a.x) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { o[c] = a.rays_o[ray * 3 + c]; d[c] = a.rays_d[ray * 3 + c]; }
-        t0 = a.t0[ray];
-        t1 = a.t1[ray];
+        t0 = a.t0[ray]; t1 = a.t1[ray];
     }
-    int* mysel = sel + wave * 64;
-    float4* myselp = selp + wave * 64;
+    // ---- stage 1, select (pass A): the first M depth samples that lie in an occupied coarse voxel, 64 samples per trip ----------
     const bool unit_scale = (a.g.voxel_scale[0] | a.g.voxel_scale[1] | a.g.voxel_scale[2]) == 1;      // the scaled reading
     int nsel = 0;
     for (int s0 = 0; ray_hits && s0 < a.S && nsel < a.M; s0 += 64) {
@@ -531,7 +551,9 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
         }
         nsel = min(a.M, nsel + __popcll(m));
     }
-    // what pass A left for slot `slot`: position and cell (a selected sample is in range by construction)
+    // ---- stage 2, neighbours: the k nearest kept points of every selected slot (`process`: one slot per trip, any table or none;
+    // `process2`: two slots per trip on the table path) go to the slot's staging row (COMPACT) or straight to the dense arrays -----
+    // what stage 1 left for slot `slot`: position and cell (a selected sample is in range by construction)
     auto slot_geom = [&](int slot, float (&p)[3], FineCoord& fc) {
         const float4 g4 = myselp[slot];                 // same-wave LDS write -> read is ordered
         p[0] = g4.x; p[1] = g4.y; p[2] = g4.z;
@@ -541,11 +563,13 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
     };
     const int hx = (a.g.kernel_size[0] - 1) / 2, hy = (a.g.kernel_size[1] - 1) / 2, hz = (a.g.kernel_size[2] - 1) / 2;
     const int gbase = b * a.N;
-    int32_t* out_idx = COMPACT ? nullptr : a.sample_idx + ray * a.M * a.k;
-    float* out_loc = COMPACT ? nullptr : a.sample_loc + ray * a.M * 3;
+    // where slot j's neighbours (rows + j kk) and position (poss + j pk) go: the wave's staging rows (COMPACT) or the ray's dense rows
+    const int kk = COMPACT ? 8 : a.k, pk = COMPACT ? 4 : 3;
+    int* const rows = COMPACT ? reinterpret_cast<int*>(dsmem + lds.stage_idx()) + wave * 64 * 8 : a.sample_idx + ray * a.M * a.k;
+    float* const poss = COMPACT ? reinterpret_cast<float*>(dsmem + lds.stage_pos()) + wave * 64 * 4 : a.sample_loc + ray * a.M * 3;
     int32_t* out_ss = COMPACT ? nullptr : a.slot_sample + ray * a.M;
     unsigned long long valid_bits = 0ull;
-    auto process = [&](int slot, u32x2 raw_in) {
+    auto process = [&](int slot) {
         const int s = mysel[slot];                     // same-wave LDS write -> read is ordered
         float p[3];
         FineCoord fc;
@@ -573,7 +597,6 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
         if (a.table) {
             // lanes 0..26: one fine voxel of the 3^3 window each -> its <= 4 kept points
             const int ky = a.g.kernel_size[1], kz = a.g.kernel_size[2], nk = a.g.kernel_size[0] * ky * kz;
-            (void)raw_in;
             int cand_idx[4] = {-1, -1, -1, -1};
             if (lane < nk) {
                 const int vx = fc.c[0] + lane / (ky * kz) - hx, vy = fc.c[1] + (lane / kz) % ky - hy, vz = fc.c[2] + lane % kz - hz;
@@ -615,15 +638,10 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
         }
         const bool has = key_lo != 0xffffffffu;
         const int first = __builtin_amdgcn_readfirstlane(has ? 1 : 0);   // lane 0 = best entry
-        if (COMPACT) {
-            if (lane < 8) stage_idx[(wave * 64 + slot) * 8 + lane] = has ? gbase + (int)key_lo : -1;
-            if (lane < 3) stage_pos[(wave * 64 + slot) * 4 + lane] = lane == 0 ? p[0] : (lane == 1 ? p[1] : p[2]);
-            if (first) valid_bits |= (1ull << slot);
-        } else {
-            if (lane < a.k) out_idx[slot * a.k + lane] = has ? gbase + (int)key_lo : -1;
-            if (lane < 3) out_loc[slot * 3 + lane] = lane == 0 ? p[0] : (lane == 1 ? p[1] : p[2]);
-            if (lane == 0) out_ss[slot] = s;
-        }
+        if (lane < kk) rows[slot * kk + lane] = has ? gbase + (int)key_lo : -1;
+        if (lane < 3) poss[slot * pk + lane] = lane == 0 ? p[0] : (lane == 1 ? p[1] : p[2]);
+        if (COMPACT && first) valid_bits |= (1ull << slot);
+        if (!COMPACT && lane == 0) out_ss[slot] = s;
     };
     // Table path with a window of <= 32 voxels (the reference's 3^3): TWO slots per trip, one per 32-lane half.  Lanes 0..26 of
     // a half fetch its slot's window voxels, the sorted list of a half lives in its lanes 0..7, and one trip of the insertion
@@ -660,7 +678,6 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
         uint32_t d2b[4];
         unsigned long long cmask[4];
         int n0 = 0, n1 = 0;                                             // candidates of the lower / upper half
-        unsigned long long* mycpk = cpk + wave * 64;
         float4 cq[4];
 #pragma unroll
         for (int qi = 0; qi < 4; ++qi) cq[qi] = pts[max(cand_idx[qi], 0)];      // all four reads in flight (empty entries read point 0)
@@ -695,8 +712,7 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
                 b1 += __popc(c1);
             }
         }
-        if (nmax == 0) {
-            // nothing to rank
+        if (nmax == 0) {                                                // nothing to rank
         } else if (packed) {
             if (l32 < (h ? n1 : n0)) mine = mycpk[lane];                // same-wave LDS write -> read is ordered
             const unsigned long long* half = mycpk + h * 32;
@@ -731,47 +747,35 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
             }
         }
         const int nh = h ? n1 : n0;
-        if (COMPACT) {
-            if (nmax > 0) {          // (a slot without neighbours is never copied out of the staging rows: nothing to write)
-                int* row = stage_idx + (wave * 64 + slot) * 8;
-                if (live && l32 < 8 && l32 >= nh) row[l32] = -1;
-                if (packed) {
-                    if (mine != ~0ull && rank[0] < 8) row[rank[0]] = gbase + (int)(uint32_t)mine;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (key[q] != ~0ull && rank[q] < 8) row[rank[q]] = gbase + cand_idx[q];
-                }
-                if (live && l32 < 3) stage_pos[(wave * 64 + slot) * 4 + l32] = l32 == 0 ? p[0] : (l32 == 1 ? p[1] : p[2]);
-            }
-            if (n0 > 0) valid_bits |= (1ull << (2 * pair));
-            if (n1 > 0) valid_bits |= (1ull << (2 * pair + 1));          // a dead upper half has no candidates
-        } else {
-            if (live && l32 < a.k && l32 >= nh) out_idx[slot * a.k + l32] = -1;
+        if (!COMPACT || nmax > 0) {          // (COMPACT: a slot without neighbours is never copied out of the staging rows)
+            if (live && l32 < kk && l32 >= nh) rows[slot * kk + l32] = -1;
             if (packed) {
-                if (mine != ~0ull && rank[0] < a.k) out_idx[slot * a.k + rank[0]] = gbase + (int)(uint32_t)mine;
+                if (mine != ~0ull && rank[0] < kk) rows[slot * kk + rank[0]] = gbase + (int)(uint32_t)mine;
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    if (key[q] != ~0ull && rank[q] < a.k) out_idx[slot * a.k + rank[q]] = gbase + cand_idx[q];
+                    if (key[q] != ~0ull && rank[q] < kk) rows[slot * kk + rank[q]] = gbase + cand_idx[q];
             }
-            if (live && l32 < 3) out_loc[slot * 3 + l32] = l32 == 0 ? p[0] : (l32 == 1 ? p[1] : p[2]);
-            if (live && l32 == 0) out_ss[slot] = s;
+            if (live && l32 < 3) poss[slot * pk + l32] = l32 == 0 ? p[0] : (l32 == 1 ? p[1] : p[2]);
         }
+        if (COMPACT && n0 > 0) valid_bits |= (1ull << (2 * pair));
+        if (COMPACT && n1 > 0) valid_bits |= (1ull << (2 * pair + 1));          // a dead upper half has no candidates
+        if (!COMPACT && live && l32 == 0) out_ss[slot] = s;
     };
     if (a.table && a.g.kernel_size[0] * a.g.kernel_size[1] * a.g.kernel_size[2] <= 32) {
         for (int pair = 0; 2 * pair < nsel; ++pair) process2(pair);
     } else {
-        for (int slot = 0; slot < nsel; ++slot) process(slot, u32x2{0u, 0u});
+        for (int slot = 0; slot < nsel; ++slot) process(slot);
     }
+    // ---- stage 3, write out: the ray's rows that have a neighbour, in slot order -------------------------------------------------
     if (COMPACT && co.ray_cnt) {
         // ordered form: rows to this ray's staging area, count to ray_cnt; bases come from compact_ordered_kernel
         const int cnt = __popcll(valid_bits);
         if (lane < nsel && ((valid_bits >> lane) & 1ull)) {
             const int64_t row = ray * a.M + __popcll(valid_bits & ((1ull << lane) - 1ull));
-            for (int t = 0; t < a.k; ++t) co.st_nb[row * a.k + t] = stage_idx[(wave * 64 + lane) * 8 + t];
+            for (int t = 0; t < a.k; ++t) co.st_nb[row * a.k + t] = rows[lane * 8 + t];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) co.st_pts[row * 3 + c] = stage_pos[(wave * 64 + lane) * 4 + c];
+            for (int c = 0; c < 3; ++c) co.st_pts[row * 3 + c] = poss[lane * 4 + c];
         }
         if (lane == 0) {
             co.ray_cnt[ray] = cnt;
@@ -793,9 +797,9 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
             if (lane < nsel && ((valid_bits >> lane) & 1ull)) {
                 const int row = base + __popcll(valid_bits & ((1ull << lane) - 1ull));
                 if (row < co.capacity) {
-                    for (int t = 0; t < a.k; ++t) co.nb[(int64_t)row * a.k + t] = over ? -1 : stage_idx[(wave * 64 + lane) * 8 + t];
+                    for (int t = 0; t < a.k; ++t) co.nb[(int64_t)row * a.k + t] = over ? -1 : rows[lane * 8 + t];
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) co.pts[(int64_t)row * 3 + c] = stage_pos[(wave * 64 + lane) * 4 + c];
+                    for (int c = 0; c < 3; ++c) co.pts[(int64_t)row * 3 + c] = poss[lane * 4 + c];
                 }
             }
         }
@@ -806,13 +810,12 @@ __global__ __launch_bounds__(256) void grid_query_wave_kernel(QueryArgs a, Compa
         }
     } else {
         for (int slot = nsel + lane; slot < a.M; slot += 64) {
-            for (int t = 0; t < a.k; ++t) out_idx[slot * a.k + t] = -1;
-            out_loc[slot * 3 + 0] = 0.f; out_loc[slot * 3 + 1] = 0.f; out_loc[slot * 3 + 2] = 0.f;
+            for (int t = 0; t < a.k; ++t) rows[slot * a.k + t] = -1;
+            poss[slot * 3 + 0] = 0.f; poss[slot * 3 + 1] = 0.f; poss[slot * 3 + 2] = 0.f;
             out_ss[slot] = -1;
         }
         if (lane == 0) a.nsel[ray] = nsel;
     }
-    }   // rays of this wave
 }
 
 // Ordered compaction (second launch of npcd_grid_query_compact_ordered).  Workgroup j owns the 64 rays [64 j, 64 j + 64).  Its
@@ -1039,28 +1042,29 @@ __device__ __forceinline__ float wave_total(float x) {                  // sum o
 #define NPCD_MARCH_RAYS 1
 #endif
 constexpr int kMarchRays = NPCD_MARCH_RAYS;
-// the fused render's extras of the march (null / 0 otherwise): the start of every ray + the per-workgroup limit pairs of the compaction
-// kernel (a ray that misses the cube ends at the global end)
+// the fused render's extras of the march (ray_march_wave_kernel<true, true> alone): the start of every ray + the per-workgroup limit pairs
+// of the compaction kernel (a ray that misses the cube ends at the global end)
 struct MarchFused {
     const float* t0;
     const uint32_t* lim_part;
     int lim_n;
 };
-template <bool COMPACT>
+template <bool COMPACT, bool FUSED = false>
 __global__ __launch_bounds__(256) void ray_march_wave_kernel(const float* __restrict__ sigma, const float* __restrict__ rgb,
                                                              const uint8_t* __restrict__ slot_valid, const float* __restrict__ slot_loc,
                                                              const int32_t* __restrict__ point_base, const float* __restrict__ rays_o,
                                                              const float* __restrict__ rays_d, const float* __restrict__ t1, int Nr, int M,
                                                              int capacity, int white_back, float* __restrict__ mask, float* __restrict__ depth,
-                                                             float* __restrict__ channels, uint32_t* ws, MarchFused mf) {
+                                                             float* __restrict__ channels, uint32_t* ws,
+                                                             std::conditional_t<FUSED, MarchFused, Unused> mf) {
     __shared__ uint32_t wg_min[4], wg_max[4];
-    __shared__ uint32_t lim_hi[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool in = lane < M;
     // fused render: the global end of the rays that hit the cube, from the pairs compact_ordered_kernel left (a few hundred words)
     float global_end = 0.f;
     bool any_hit = false;
-    if (mf.lim_part) {
+    if constexpr (FUSED) {
+        __shared__ uint32_t lim_hi[4];
         uint32_t kmax = 0u;
         for (int i = threadIdx.x; i < mf.lim_n; i += 256) kmax = max(kmax, mf.lim_part[2 * i + 1]);
 #pragma unroll
@@ -1080,7 +1084,8 @@ __global__ __launch_bounds__(256) void ray_march_wave_kernel(const float* __rest
         const float o[3] = {rays_o[ray * 3], rays_o[ray * 3 + 1], rays_o[ray * 3 + 2]};
         const float d[3] = {rays_d[ray * 3], rays_d[ray * 3 + 1], rays_d[ray * 3 + 2]};
         float ray_end = t1[ray];
-        if (mf.lim_part && any_hit && !(ray_end > mf.t0[ray])) ray_end = global_end;      // a ray that misses the cube (renderer.py:40-43)
+        if constexpr (FUSED)
+            if (any_hit && !(ray_end > mf.t0[ray])) ray_end = global_end;      // a ray that misses the cube (renderer.py:40-43)
         unsigned long long bits;
         if (COMPACT) bits = reinterpret_cast<const unsigned long long*>(slot_valid)[ray];
         else bits = __ballot(in && slot_valid[(int64_t)ray * M + lane] != 0);
@@ -1134,10 +1139,6 @@ __global__ __launch_bounds__(256) void ray_march_wave_kernel(const float* __rest
         ws[2 + 2 * blockIdx.x] = min(min(wg_min[0], wg_min[1]), min(wg_min[2], wg_min[3]));
         ws[3 + 2 * blockIdx.x] = max(max(wg_max[0], wg_max[1]), max(wg_max[2], wg_max[3]));
     }
-    // (Round 6 tried the depth clamp HERE -- the last workgroup to finish, found through a ticket counter behind a device-scope fence,
-    //  combining the limits and clamping all depths -- to save depth_clamp_kernel's launch: a view went from 0.354 to 0.626 ms.  The march
-    //  is 4,096 workgroups of four rays; a device-scope release fence on gfx950 writes the XCD's L2 back, once per workgroup.  Removed:
-    //  docs/experiments.md R6.6.)
 }
 
 // Backward of the ray march w.r.t. the compact densities and colours (stage-1 training; slot positions, ray geometry and hence
@@ -1163,7 +1164,10 @@ __global__ __launch_bounds__(64) void ray_march_bwd_kernel(const float* __restri
     const uint8_t* sv = slot_valid + (int64_t)ray * M;
     const float* sl = slot_loc + (int64_t)ray * M * 3;
     const int cp0 = point_base[ray];
-    float dep[64], al[64], Tt[64];
+    // per-slot depth, alpha and transmittance of every ray of the workgroup: [slot][thread] columns in LDS (3 x 16 KB, conflict-free);
+    // as indexed thread-private arrays they lived in scratch memory
+    __shared__ float cols[3 * 64 * 64];
+    float* const dep = cols + threadIdx.x, * const al = dep + 64 * 64, * const Tt = al + 64 * 64;
     // pass 1: per-slot depths (renderer.py:96-110)
     float run_max = -INFINITY;
     for (int j = 0; j < M; ++j) {
@@ -1177,7 +1181,7 @@ __global__ __launch_bounds__(64) void ray_march_bwd_kernel(const float* __restri
             }
             run_max = fmaxf(run_max, acc / (float)cnt);
         }
-        dep[j] = (run_max == -INFINITY) ? ray_end : run_max;
+        dep[j * 64] = (run_max == -INFINITY) ? ray_end : run_max;
     }
     // pass 2: alpha, transmittance, the two sums of the forward
     float T = 1.f, total = 0.f, wd = 0.f;
@@ -1185,12 +1189,12 @@ __global__ __launch_bounds__(64) void ray_march_bwd_kernel(const float* __restri
     for (int j = 0; j < M; ++j) {
         const float sg = sv[j] ? sigma[cp] : 0.f;
         cp += sv[j] ? 1 : 0;
-        const float delta = j + 1 < M ? dep[j + 1] - dep[j] : 0.f;
+        const float delta = j + 1 < M ? dep[(j + 1) * 64] - dep[j * 64] : 0.f;
         const float alpha = 1.f - expf(-(sg * delta));
-        al[j] = alpha;
-        Tt[j] = T;
+        al[j * 64] = alpha;
+        Tt[j * 64] = T;
         total += alpha * T;
-        wd += alpha * T * dep[j];
+        wd += alpha * T * dep[j * 64];
         T *= (1.f - alpha + 1e-10f);
     }
     const float lo = fkey_inv(ws[0]), hi = fkey_inv(ws[1]);
@@ -1204,15 +1208,15 @@ __global__ __launch_bounds__(64) void ray_march_bwd_kernel(const float* __restri
     for (int j = M - 1; j >= 0; --j) {
         const bool valid = sv[j] != 0;
         cp -= valid ? 1 : 0;                                     // compact index of slot j
-        const float w = al[j] * Tt[j];
+        const float w = al[j * 64] * Tt[j * 64];
         float G = gm - gbg;
-        if (depth_live) G += gd * (dep[j] - draw);               // (not a multiplication by 0: draw is NaN on an empty ray)
+        if (depth_live) G += gd * (dep[j * 64] - draw);               // (not a multiplication by 0: draw is NaN on an empty ray)
         if (valid) {
             const float r_ = rgb[cp * 3], g_ = rgb[cp * 3 + 1], b_ = rgb[cp * 3 + 2];
             G += gc[0] * r_ + gc[1] * g_ + gc[2] * b_;
-            const float dalpha = G * Tt[j] - S / (1.f - al[j] + 1e-10f);
-            const float delta = j + 1 < M ? dep[j + 1] - dep[j] : 0.f;
-            dsigma[cp] = dalpha * delta * (1.f - al[j]);         // exp(-sigma delta) = 1 - alpha
+            const float dalpha = G * Tt[j * 64] - S / (1.f - al[j * 64] + 1e-10f);
+            const float delta = j + 1 < M ? dep[(j + 1) * 64] - dep[j * 64] : 0.f;
+            dsigma[cp] = dalpha * delta * (1.f - al[j * 64]);         // exp(-sigma delta) = 1 - alpha
             drgb[cp * 3 + 0] = gc[0] * w;
             drgb[cp * 3 + 1] = gc[1] * w;
             drgb[cp * 3 + 2] = gc[2] * w;
@@ -1402,11 +1406,10 @@ extern "C" int npcd_grid_query(const npcd_grid_params* g_in, const void* workspa
     static DynLds lds_attr;
     if (mode == 1 && lds > 65536) NPCD_HIP_CHECK(lds_attr.ensure(reinterpret_cast<const void*>(grid_query_kernel<false>), lds));
     if (mode == 0) {
-        // grid_query_wave_kernel: + the selected samples' geometry, the packed candidates and the per-ray staging rows
-        const size_t lds2 = lds + 16 + 4 * 64 * 16 + 4 * 64 * 8 + 4 * 64 * 8 * 4 + 4 * 64 * 4 * 4;
+        const size_t lds2 = QueryLds{N, a.nwords}.bytes();
         static DynLds lds2_attr;
         if (lds2 > 65536) NPCD_HIP_CHECK(lds2_attr.ensure(reinterpret_cast<const void*>(grid_query_wave_kernel<false>), lds2));
-        hipLaunchKernelGGL(grid_query_wave_kernel<false>, dim3(B * bpe), dim3(256), lds2, st, a, CompactOut{}, bpe);
+        hipLaunchKernelGGL(grid_query_wave_kernel<false>, dim3(B * bpe), dim3(256), lds2, st, a, CompactOut{}, bpe, Unused{});
     }
     else hipLaunchKernelGGL(grid_query_kernel<false>, dim3(B * bpe), dim3(256), lds, st, a, bpe);
     NPCD_HIP_CHECK(hipGetLastError());
@@ -1429,7 +1432,7 @@ extern "C" int npcd_ray_march(const float* sigma, const float* rgb, const uint8_
     if (M <= 64 && !getenv("NPCD_MARCH_PER_THREAD")) {        // (A/B switch: the thread-per-ray form)
         nparts = march_parts(Nr);
         hipLaunchKernelGGL(ray_march_wave_kernel<false>, dim3(nparts), dim3(256), 0, st, sigma, rgb, slot_valid, slot_loc, point_base, rays_o, rays_d,
-                           t1, Nr, M, 0, white_back, mask, depth, channels, ws, MarchFused{});
+                           t1, Nr, M, 0, white_back, mask, depth, channels, ws, Unused{});
     } else {
         hipLaunchKernelGGL(march_init_kernel, dim3(1), dim3(1), 0, st, ws);
         hipLaunchKernelGGL(ray_march_kernel<false>, dim3(grid), dim3(256), 0, st, sigma, rgb, slot_valid, slot_loc, point_base, rays_o, rays_d, t1,
@@ -1460,12 +1463,6 @@ extern "C" int npcd_ray_march_bwd(const float* sigma, const float* rgb, const ui
 // arrays.  counter [4]: counter[0] receives the number of compact points, counter[1] an overflow flag (capacity too small;
 // nothing is written for the overflowing rays), counter[2] and [3] are zeroed (ABI 8: [2] is the word the caller hands to the
 // shading kernels as their range-guard `status`, zeroed here so that it costs no launch of its own).  Rows of one ray are contiguous and in slot order.
-struct RenderRays {          // fused ray generation of npcd_render_rays_query
-    const float *extr, *intr;
-    int views, res;
-    float box;
-    uint32_t* lim_part;
-};
 static int grid_query_compact_launch(const npcd_grid_params* g_in, const void* workspace, const float* points, int B, int N, int R, int S,
                                      int M, int k, float r, const float* rays_o, const float* rays_d, const float* t0, const float* t1,
                                      int32_t* counter, int32_t capacity, int32_t* ray_base, int32_t* ray_nsel, uint64_t* ray_bits,
@@ -1494,33 +1491,31 @@ static int grid_query_compact_launch(const npcd_grid_params* g_in, const void* w
     CompactOut co{};
     co.counter = counter; co.capacity = capacity; co.ray_base = ray_base; co.ray_nsel = ray_nsel;
     co.ray_bits = reinterpret_cast<unsigned long long*>(ray_bits); co.nb = nb_idx; co.pts = pts;
-    if (rr) {       // the rays are OUTPUTS of the query kernel here
-        a.extr = rr->extr; a.intr = rr->intr; a.views = rr->views; a.res = rr->res; a.box = rr->box;
-        a.gen_o = const_cast<float*>(rays_o); a.gen_d = const_cast<float*>(rays_d);
-        a.gen_t0 = const_cast<float*>(t0); a.gen_t1 = const_cast<float*>(t1);
-        co.lim_t0 = t0; co.lim_t1 = t1; co.lim_part = rr->lim_part;
-    }
-    // rays per wave (NPCD_QUERY_RPW, an A/B switch; default 1).  Round 6 measured 2 / 4 / 8 rays per wave on the bench view: the kernel
-    // got SLOWER -- 63.4 -> 70.4 / 103.5 / 102.7 us at 128 depth samples, 40.7 -> 40.9 / 58.5 / 58.8 at 64: the rays of a view differ by
-    // an order of magnitude in cost, a wave that draws several long ones finishes last, and the 12 KB of staging per workgroup it saves
-    // were never the limit (docs/experiments.md R6.7).
-    static const int rpw_env = [] { const char* e = getenv("NPCD_QUERY_RPW"); return e ? atoi(e) : 0; }();
-    int rpw = rpw_env > 0 ? rpw_env : 1;
-    a.rpw = rpw;
-    const int bpe = (R + 4 * rpw - 1) / (4 * rpw);
-    const size_t lds = (size_t)N * 16 + (size_t)a.nwords * 4 + 4 * 64 * 4 + 16 + 4 * 64 * 16 + 4 * 64 * 8 + 4 * 64 * 8 * 4 + 4 * 64 * 4 * 4;
+    if (rr) { co.lim_t0 = t0; co.lim_t1 = t1; co.lim_part = rr->lim_part; }       // (the rays are OUTPUTS of the query kernel here)
+    // One wave per ray.  (Round 6 measured 2 / 4 / 8 rays per wave: slower at every setting, docs/experiments.md R6.7.)
+    const int bpe = (R + 3) / 4;
+    const size_t lds = QueryLds{N, a.nwords}.bytes();
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static DynLds lds_attr;
-    if (lds > 65536) NPCD_HIP_CHECK(lds_attr.ensure(reinterpret_cast<const void*>(grid_query_wave_kernel<true>), lds));
+    const int64_t nrays = (int64_t)B * R, nblk = (nrays + kOrdRays - 1) / kOrdRays;
     if (order_ws) {
         // staging: group sums, [B R] counts (each padded to 16 bytes), [B R][M][k] indices, [B R][M][3] positions
-        const int64_t nrays = (int64_t)B * R, nblk = (nrays + kOrdRays - 1) / kOrdRays;
         unsigned char* w = static_cast<unsigned char*>(order_ws);
         w += (nblk * 4 + 15) / 16 * 16;                 // (the group sums of rounds 1-3: unused, the layout of the workspace is unchanged)
         co.ray_cnt = reinterpret_cast<int32_t*>(w);
         co.st_nb = reinterpret_cast<int32_t*>(w + (nrays * 4 + 15) / 16 * 16);
         co.st_pts = reinterpret_cast<float*>(co.st_nb + nrays * M * k);
-        hipLaunchKernelGGL(grid_query_wave_kernel<true>, dim3(B * bpe), dim3(256), lds, st, a, co, bpe);
+    } else {
+        NPCD_HIP_CHECK(hipMemsetAsync(counter, 0, 4 * sizeof(int32_t), st));
+    }
+    static DynLds lds_attr, lds_attr_rays;              // (one per instantiation: the attribute belongs to the kernel)
+    if (rr) {
+        if (lds > 65536) NPCD_HIP_CHECK(lds_attr_rays.ensure(reinterpret_cast<const void*>(grid_query_wave_kernel<true, true>), lds));
+        hipLaunchKernelGGL((grid_query_wave_kernel<true, true>), dim3(B * bpe), dim3(256), lds, st, a, co, bpe, *rr);
+    } else {
+        if (lds > 65536) NPCD_HIP_CHECK(lds_attr.ensure(reinterpret_cast<const void*>(grid_query_wave_kernel<true>), lds));
+        hipLaunchKernelGGL(grid_query_wave_kernel<true>, dim3(B * bpe), dim3(256), lds, st, a, co, bpe, Unused{});
+    }
+    if (order_ws) {
         int32_t* blk_sum = nullptr;
         if (nrays > kOrdTwoLevel) {                     // (they fit into the former group-sum area: one word per 1,024 rays of nblk * 4 bytes)
             blk_sum = static_cast<int32_t*>(order_ws);
@@ -1528,9 +1523,6 @@ static int grid_query_compact_launch(const npcd_grid_params* g_in, const void* w
                                blk_sum, (int)nrays);
         }
         hipLaunchKernelGGL(compact_ordered_kernel, dim3((unsigned)nblk), dim3(256), 0, st, co, (int)nrays, M, k, blk_sum);
-    } else {
-        NPCD_HIP_CHECK(hipMemsetAsync(counter, 0, 4 * sizeof(int32_t), st));
-        hipLaunchKernelGGL(grid_query_wave_kernel<true>, dim3(B * bpe), dim3(256), lds, st, a, co, bpe);
     }
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
@@ -1560,7 +1552,7 @@ extern "C" int npcd_grid_query_compact_ordered(const npcd_grid_params* g_in, con
 // Ray march on the compact layout produced by npcd_grid_query_compact.
 static int ray_march_compact_launch(const float* sigma, const float* rgb, const uint64_t* ray_bits, const float* pts, const int32_t* ray_base,
                                     const float* rays_o, const float* rays_d, const float* t1, int Nr, int M, int capacity, int white_back,
-                                    float* mask, float* depth, float* channels, float* depth_ws, const MarchFused& mf, void* stream) {
+                                    float* mask, float* depth, float* channels, float* depth_ws, const MarchFused* mf, void* stream) {
     if (!sigma || !rgb || !ray_bits || !pts || !ray_base || !rays_o || !rays_d || !t1 || !mask || !depth || !channels || !depth_ws)
         return NPCD_ERR_ARG;
     if (Nr <= 0 || M <= 0 || M > 64 || capacity <= 0) return NPCD_ERR_ARG;
@@ -1569,11 +1561,16 @@ static int ray_march_compact_launch(const float* sigma, const float* rgb, const 
     const int grid = (Nr + 255) / 256;
     int nparts = 0;
     const bool per_thread = getenv("NPCD_MARCH_PER_THREAD") != nullptr;
-    if (per_thread && mf.lim_part) return NPCD_ERR_UNSUPPORTED;
+    if (per_thread && mf) return NPCD_ERR_UNSUPPORTED;
     if (!per_thread) {
         nparts = march_parts(Nr);
-        hipLaunchKernelGGL(ray_march_wave_kernel<true>, dim3(nparts), dim3(256), 0, st, sigma, rgb, reinterpret_cast<const uint8_t*>(ray_bits), pts,
-                           ray_base, rays_o, rays_d, t1, Nr, M, capacity, white_back, mask, depth, channels, ws, mf);
+        const uint8_t* bits = reinterpret_cast<const uint8_t*>(ray_bits);
+        if (mf)
+            hipLaunchKernelGGL((ray_march_wave_kernel<true, true>), dim3(nparts), dim3(256), 0, st, sigma, rgb, bits, pts, ray_base, rays_o, rays_d,
+                               t1, Nr, M, capacity, white_back, mask, depth, channels, ws, *mf);
+        else
+            hipLaunchKernelGGL(ray_march_wave_kernel<true>, dim3(nparts), dim3(256), 0, st, sigma, rgb, bits, pts, ray_base, rays_o, rays_d,
+                               t1, Nr, M, capacity, white_back, mask, depth, channels, ws, Unused{});
     } else {
         hipLaunchKernelGGL(march_init_kernel, dim3(1), dim3(1), 0, st, ws);
         hipLaunchKernelGGL(ray_march_kernel<true>, dim3(grid), dim3(256), 0, st, sigma, rgb, reinterpret_cast<const uint8_t*>(ray_bits), pts, ray_base,
@@ -1587,7 +1584,7 @@ extern "C" int npcd_ray_march_compact(const float* sigma, const float* rgb, cons
                                       const float* rays_o, const float* rays_d, const float* t1, int Nr, int M, int capacity, int white_back,
                                       float* mask, float* depth, float* channels, float* depth_ws, void* stream) {
     return ray_march_compact_launch(sigma, rgb, ray_bits, pts, ray_base, rays_o, rays_d, t1, Nr, M, capacity, white_back, mask, depth, channels,
-                                    depth_ws, MarchFused{}, stream);
+                                    depth_ws, nullptr, stream);
 }
 
 // ---- fused render (round 6, ABI 9): ray generation inside the neighbour query, the box-limit fix-up inside the march -- two launches
@@ -1610,7 +1607,7 @@ extern "C" int npcd_render_rays_query(const npcd_grid_params* g_in, const void* 
     if ((int64_t)views * res * res > (1 << 28)) return NPCD_ERR_UNSUPPORTED;
     for (int a = 0; a < 3; ++a)
         if (!(box >= g_in->range_max[a]) || !(-box <= g_in->range_min[a])) return NPCD_ERR_UNSUPPORTED;
-    RenderRays rr{extr, intr, views, res, box, lim_part};
+    RenderRays rr{extr, intr, views, res, box, rays_o, rays_d, t0, t1, lim_part};
     return grid_query_compact_launch(g_in, workspace, points, B, N, views * res * res, S, M, k, r, rays_o, rays_d, t0, t1, counter, capacity,
                                      ray_base, ray_nsel, ray_bits, nb_idx, pts, order_ws, stream, &rr);
 }
@@ -1621,5 +1618,5 @@ extern "C" int npcd_ray_march_compact_fused(const float* sigma, const float* rgb
     if (!t0 || !lim_part || lim_pairs <= 0) return NPCD_ERR_ARG;
     MarchFused mf{t0, lim_part, lim_pairs};
     return ray_march_compact_launch(sigma, rgb, ray_bits, pts, ray_base, rays_o, rays_d, t1, Nr, M, capacity, white_back, mask, depth, channels,
-                                    depth_ws, mf, stream);
+                                    depth_ws, &mf, stream);
 }

@@ -1,0 +1,90 @@
+"""Register and scratch budget of the kernels of csrc/geometry.hip, read from the compiler's own output (no GPU needed).
+
+Round 6 folded two opt-in experiments into grid_query_wave_kernel as run-time branches; its default form went from 46 to 100
+VGPRs (8 -> 4 waves per SIMD) and nobody saw it, because every A/B compared the switch on with the switch off on the same binary.
+This compiles the file to assembly with the flags of csrc/build.py and checks the kernel descriptors, so that it cannot recur
+silently."""
+import importlib.util
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import PKG
+
+CSRC = os.path.join(PKG, "csrc")
+
+
+def _build_py():
+    spec = importlib.util.spec_from_file_location("npcd_csrc_build", os.path.join(CSRC, "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    """{mangled kernel name: {"vgpr": .amdhsa_next_free_vgpr, "scratch": .amdhsa_private_segment_fixed_size, "lds": static bytes}}
+    of geometry.hip: one hipcc run for the module."""
+    build = _build_py()
+    if not os.path.exists(build.HIPCC):
+        pytest.skip(f"hipcc not found at {build.HIPCC}")
+    out = str(tmp_path_factory.mktemp("kernel_resources") / "geometry.s")
+    cmd = [build.HIPCC, *build.COMMON, *build.SOURCES["geometry.hip"], "-S", "--cuda-device-only",
+           os.path.join(CSRC, "geometry.hip"), "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, f"hipcc failed:\n{r.stderr}"
+    found = {}
+    name = None
+    keys = {"next_free_vgpr": "vgpr", "private_segment_fixed_size": "scratch", "group_segment_fixed_size": "lds"}
+    for line in open(out):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
+        if m:
+            name = m.group(1)
+            found[name] = {}
+            continue
+        m = re.match(r"\s*\.amdhsa_(next_free_vgpr|private_segment_fixed_size|group_segment_fixed_size)\s+(\d+)\s*$", line)
+        if m and name:
+            found[name][keys[m.group(1)]] = int(m.group(2))
+        if ".end_amdhsa_kernel" in line:
+            name = None
+    assert found, "no kernel descriptor parsed"
+    for k, v in found.items():
+        assert set(v) == set(keys.values()), (k, v)
+        print(f"{k}: {v}")
+    return found
+
+
+def _form(kernels, name, *flags):
+    """The one instantiation name<flags...> (Itanium mangling of bool template arguments: I Lb1E Lb0E ... E)."""
+    tag = f"{len(name)}{name}I" + "".join(f"Lb{int(f)}E" for f in flags) + "E"
+    hit = [v for k, v in kernels.items() if tag in k]
+    assert len(hit) == 1, f"{name}{flags}: {len(hit)} kernels match {tag} in {sorted(kernels)}"
+    return hit[0]
+
+
+def test_no_kernel_of_geometry_uses_scratch(kernels):
+    assert len(kernels) >= 17, sorted(kernels)
+    spilling = {k: v["scratch"] for k, v in kernels.items() if v["scratch"] != 0}
+    assert not spilling, spilling
+
+
+def test_default_query_forms_keep_eight_waves_per_simd(kernels):
+    """51 / 54 VGPRs is what the round-6 source gave with its two experiments compiled out; 56 is the next multiple of the
+    8-register allocation granule (a SIMD holds min(8, 512 / allocation) waves: anything up to 64 allows all 8)."""
+    for compact in (True, False):
+        k = _form(kernels, "grid_query_wave_kernel", compact, False)
+        assert k["vgpr"] <= 56, (compact, k)
+
+
+def test_default_march_forms_do_not_pay_for_the_fused_one(kernels):
+    """No more than with the run-time MarchFused argument of round 6 (55 compact, 49 dense)."""
+    assert _form(kernels, "ray_march_wave_kernel", True, False)["vgpr"] <= 55
+    assert _form(kernels, "ray_march_wave_kernel", False, False)["vgpr"] <= 49
+
+
+def test_fused_forms_exist(kernels):
+    """The opt-in forms are separate instantiations (scratch is checked above; their register counts are not a bar)."""
+    _form(kernels, "grid_query_wave_kernel", True, True)
+    _form(kernels, "ray_march_wave_kernel", True, True)
