@@ -466,6 +466,11 @@ int npcd_linear_dgelu_bwd(const void* dy, const void* wt, const void* h, void* d
 int npcd_linear128_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int dtype, void* stream);
 /* out [C, R] = in [R, C]^T for 16-bit elements (the transposed shadow of the Linear weights that the data gradients read) */
 int npcd_transpose_16(const void* in, void* out, int R, int C, void* stream);
+/* `count` (1..4) such transposes in ONE launch: out_g [C_g, R_g] = in_g [R_g, C_g]^T, 16-bit elements of any type (the four Linear
+ * weights of a residual block -> the transposed shadow that the data-gradient products read).  16 bytes per lane on loads and
+ * stores where a side's pointer and row pitch are 16-byte aligned, 2 bytes per lane on that side otherwise and at ragged edges:
+ * any R, C >= 1, pointers 2-byte aligned.  in / out / R / C: host arrays of `count` entries; in and out must not overlap. */
+int npcd_transpose16_group(int count, const void* const* in, void* const* out, const int* R, const int* C, void* stream);
 
 /* out[i] = part[0 * numel + i] + ... + part[(S - 1) * numel + i], fp32, added in slice order (S = 2, 4 or 8; numel % 4 == 0;
  * 16-byte aligned): the sum of the row-split weight-gradient partials of the fused backbone (replaces torch.sum(part, dim=0)

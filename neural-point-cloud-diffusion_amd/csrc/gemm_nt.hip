@@ -711,6 +711,71 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const E* __restrict__ 
         if (c0 + i < C && r0 + tx < R) out[(int64_t)(c0 + i) * R + r0 + tx] = tile[tx][i];
 }
 
+// Up to four 16-bit transposes [R, C] -> [C, R] in ONE launch (the transposed shadow of a residual block's four Linear weights, which
+// the data-gradient products read): a workgroup per 64 x 64 tile, 16 bytes per lane on the global loads AND the global stores.
+// The LDS image is the TRANSPOSED tile, element (c, r) at [c][r], 64 x 64 with no padding: a lane loads 8 columns of TWO rows, packs
+// the two rows' values of each column into a dword and stores 8 dwords; it then reads 16 bytes of one image row and stores them.
+// Padding cannot serve both sides -- the 16-byte reads need a row pitch that is a multiple of 4 dwords, and with any such pitch the
+// 8 lanes that hold the 8 column groups of one row pair store to the same bank -- so the 16-byte slots of an image row are XOR-ed
+// with the row's column group instead: the 32 lanes of a ds_write_b32 group then cover 32 banks, and the 16 lanes of a
+// ds_read_b128 group 64.  A side whose pointer or row pitch is not 16-byte aligned (a view at an odd element offset of the flat
+// shadow), and every tile at a ragged edge, moves 2 bytes per lane through the same image.
+constexpr int kTransposeGroupMax = 4;
+struct TransposeGroup {
+    const uint16_t* in[kTransposeGroupMax];
+    uint16_t* out[kTransposeGroupMax];
+    int R[kTransposeGroupMax], C[kTransposeGroupMax];
+    int first[kTransposeGroupMax + 1];      // first tile of matrix g in the launch's tile order
+    int count;
+};
+
+__device__ __forceinline__ int transpose_slot(int c, int r) { return c * 64 + ((((r >> 3) ^ (c >> 3)) & 7) << 3) + (r & 7); }
+
+__global__ __launch_bounds__(256) void transpose16_group_kernel(TransposeGroup gp) {
+    __shared__ __attribute__((aligned(16))) uint16_t tile[64 * 64];
+    const int w = blockIdx.x;
+    int g = 0;
+#pragma unroll
+    for (int i = 1; i < kTransposeGroupMax; ++i)
+        if (i < gp.count && w >= gp.first[i]) g = i;
+    const uint16_t* __restrict__ in = gp.in[g];
+    uint16_t* __restrict__ out = gp.out[g];
+    const int R = gp.R[g], C = gp.C[g];
+    const int tiles_c = (C + 63) >> 6, t = w - gp.first[g];
+    const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
+    const bool full = r0 + 64 <= R && c0 + 64 <= C;                                                   // (workgroup-uniform, like all below)
+    const bool wide_in = full && !(reinterpret_cast<uintptr_t>(in) & 15) && !(C & 7);
+    const bool wide_out = full && !(reinterpret_cast<uintptr_t>(out) & 15) && !(R & 7);
+    const int tid = threadIdx.x;
+    if (wide_in) {
+        const int cg = tid & 7, rp = tid >> 3;              // 8 lanes x 16 bytes = the 128 bytes of a tile row; rows 2 rp and 2 rp + 1
+        const uint16_t* src = in + (int64_t)(r0 + 2 * rp) * C + c0 + 8 * cg;
+        const u32x4 a = *reinterpret_cast<const u32x4*>(src), b = *reinterpret_cast<const u32x4*>(src + C);
+        uint32_t* image = reinterpret_cast<uint32_t*>(tile);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t lo = (j & 1) ? a[j >> 1] >> 16 : a[j >> 1] & 0xffffu;
+            const uint32_t hi = (j & 1) ? b[j >> 1] & 0xffff0000u : b[j >> 1] << 16;
+            image[transpose_slot(8 * cg + j, 2 * rp) >> 1] = lo | hi;
+        }
+    } else {
+        const int tx = tid & 63, ty = tid >> 6;
+        for (int i = ty; i < 64; i += 4)
+            if (r0 + i < R && c0 + tx < C) tile[transpose_slot(tx, i)] = in[(int64_t)(r0 + i) * C + c0 + tx];
+    }
+    __syncthreads();
+    if (wide_out) {
+        const int rg = tid & 7;
+#pragma unroll
+        for (int c = tid >> 3; c < 64; c += 32)
+            *reinterpret_cast<u32x4*>(out + (int64_t)(c0 + c) * R + r0 + 8 * rg) = *reinterpret_cast<const u32x4*>(tile + transpose_slot(c, 8 * rg));
+    } else {
+        const int tx = tid & 63, ty = tid >> 6;
+        for (int i = ty; i < 64; i += 4)
+            if (c0 + i < C && r0 + tx < R) out[(int64_t)(c0 + i) * R + r0 + tx] = tile[transpose_slot(i, tx)];
+    }
+}
+
 }  // namespace npcd
 
 using namespace npcd;
@@ -815,6 +880,24 @@ extern "C" int npcd_transpose_16(const void* in, void* out, int R, int C, void* 
     if (!in || !out || R <= 0 || C <= 0) return NPCD_ERR_ARG;
     hipLaunchKernelGGL(transpose16_kernel<uint16_t>, dim3((C + 63) / 64, (R + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t*>(in), static_cast<uint16_t*>(out), R, C);
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
+}
+extern "C" int npcd_transpose16_group(int count, const void* const* in, void* const* out, const int* R, const int* C, void* stream) {
+    if (count < 1 || count > kTransposeGroupMax || !in || !out || !R || !C) return NPCD_ERR_ARG;
+    TransposeGroup gp{};
+    gp.count = count;
+    int64_t tiles = 0;
+    for (int g = 0; g < count; ++g) {
+        if (!in[g] || !out[g] || R[g] <= 0 || C[g] <= 0) return NPCD_ERR_ARG;
+        if ((reinterpret_cast<uintptr_t>(in[g]) & 1) || (reinterpret_cast<uintptr_t>(out[g]) & 1)) return NPCD_ERR_ARG;
+        gp.in[g] = static_cast<const uint16_t*>(in[g]); gp.out[g] = static_cast<uint16_t*>(out[g]); gp.R[g] = R[g]; gp.C[g] = C[g];
+        gp.first[g] = (int)tiles;
+        tiles += (int64_t)((R[g] + 63) / 64) * ((C[g] + 63) / 64);
+        if (tiles >= (int64_t)1 << 31) return NPCD_ERR_UNSUPPORTED;
+    }
+    gp.first[count] = (int)tiles;
+    hipLaunchKernelGGL(transpose16_group_kernel, dim3((unsigned)tiles), dim3(256), 0, static_cast<hipStream_t>(stream), gp);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }

@@ -115,6 +115,7 @@ SIGNATURES = {
     "npcd_linear_dgelu_rows": (c_int, [c_int]),
     "npcd_linear_dgelu_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "npcd_transpose_16": (c_int, [_P, _P, c_int, c_int, _P]),
+    "npcd_transpose16_group": (c_int, [c_int, POINTER(_P), POINTER(_P), POINTER(c_int), POINTER(c_int), _P]),
     "npcd_small_wgrad_blocks": (c_int, [c_int]),
     "npcd_small_wgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "npcd_q_sample": (c_int, [_P] * 6 + [c_int, c_int64, _P]),

@@ -92,3 +92,21 @@ def transpose16(w, out=None):
     o = arena.empty((C, R), w.dtype, w.device) if out is None else out
     check(lib().npcd_transpose_16(ptr(w), ptr(o), R, C, stream_ptr()), "npcd_transpose_16")
     return o
+
+
+def transpose16_group(pairs):
+    """[(w [R_g, C_g], out [C_g, R_g]), ...] (<= 4, contiguous 16-bit tensors of one element size): out_g = w_g^T, all in ONE launch
+    (csrc/gemm_nt.hip, npcd_transpose16_group).  Views at any element offset of a larger buffer are taken."""
+    import ctypes
+    n = len(pairs)
+    for w, o in pairs:
+        require_gpu(w, o)
+        if (w.dim() != 2 or w.element_size() != 2 or o.dtype != w.dtype or tuple(o.shape) != (w.shape[1], w.shape[0])
+                or not w.is_contiguous() or not o.is_contiguous()):
+            raise RuntimeError("npcd transpose16_group: contiguous 16-bit w [R, C] and out [C, R] of one type expected, got "
+                               f"{tuple(w.shape)} {w.dtype} -> {tuple(o.shape)} {o.dtype}")
+    P = ctypes.c_void_p * n
+    I = ctypes.c_int * n
+    check(lib().npcd_transpose16_group(n, P(*[ptr(w) for w, _ in pairs]), P(*[ptr(o) for _, o in pairs]),
+                                       I(*[w.shape[0] for w, _ in pairs]), I(*[w.shape[1] for w, _ in pairs]), stream_ptr()),
+          "npcd_transpose16_group")

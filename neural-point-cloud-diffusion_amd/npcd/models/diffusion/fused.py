@@ -24,6 +24,7 @@ from ...hip import linear as hlin
 _bf16, _f32 = torch.bfloat16, torch.float32
 _BLOCK_PARAMS = ("ln_1.weight", "ln_1.bias", "attn.c_qkv.weight", "attn.c_qkv.bias", "attn.c_proj.weight", "attn.c_proj.bias",
                  "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")
+_LINEARS = ("attn_c_qkv", "attn_c_proj", "mlp_c_fc", "mlp_c_proj")          # the four Linear layers of a block, in parameter order
 
 
 # ---- token-dimension split of the forward / data-gradient GEMMs ---------------------------------------------------------------
@@ -55,8 +56,16 @@ _SUM_KERNEL = not os.environ.get("NPCD_NO_SUM_KERNEL")          # the weight-gra
 _OWN_WGRAD = _env_on("NPCD_OWN_WGRAD")
 # opt-in: the data gradient of mlp.c_proj as the own NT product with the GELU backward and the c_fc bias-gradient column sums in its
 # epilogue (csrc/gemm_nt.hip, docs/experiments.md R4.1) on the full 256-row tiles of the token range; the remainder rows keep the
-# library product + the separate kernel.  Reads a TRANSPOSED 16-bit copy of the weight, refreshed per backward.
+# library product + the separate kernel.  Reads the engine's transposed shadow of the weight (below).
 _OWN_DGELU = _env_on("NPCD_OWN_DGELU")
+# The data gradients dy @ W read a TRANSPOSED 16-bit shadow of the four Linear weights of every block (FusedBackboneEngine), i.e. they
+# are the forward's BLAS-TN form dy @ (W^T)^T instead of BLAS-NN against the weight as stored: the library's TN kernel is the faster
+# one at these shapes (docs/experiments.md R10.1).  The shadow is re-transposed per block in the forward, one launch per block, only
+# after the 16-bit shadow was written (once per optimizer step).  NPCD_DGRAD_NN=1: the product against the weight as stored, no
+# transposed shadow kept up to date (A/B).  NPCD_DGRAD_T_MIN_T: the token rows from which the transposed form is used -- the
+# saving grows with the token rows, the transposes (13 us per block) do not: at 4,104 rows the two cancel (13 us saved per block).
+_DGRAD_NN = _env_on("NPCD_DGRAD_NN")
+_DGRAD_T_MIN_T = int(os.environ.get("NPCD_DGRAD_T_MIN_T", "16000"))
 
 
 # Below _SPLIT_MIN only the products whose OUTPUT is at least this wide are split (round 5, R5.18): at T = 4,104 / 8,208 the left-over
@@ -104,11 +113,13 @@ def _linear(bias, x, w16):
     return out
 
 
-def _dgrad(dy, w16):
-    """dy [T, N] bf16, w16 [N, K] bf16 -> dy @ w16, [T, K] bf16."""
+def _dgrad(dy, w16, wT=None):
+    """dy [T, N] bf16, w16 [N, K] bf16 -> dy @ w16, [T, K] bf16.  wT [K, N]: w16 transposed (the engine's transposed shadow) -- the
+    product then runs as dy @ wT^T, the forward's form; the large rows and the left-over rows of the split read the same buffer."""
     T = dy.shape[0]
     out = harena.empty((T, w16.shape[1]), dy.dtype, dy.device)
-    _split_gemm(lambda r: torch.mm(dy[r], w16, out=out[r]), T, w16.shape[1])
+    b = w16 if wT is None else wT.t()
+    _split_gemm(lambda r: torch.mm(dy[r], b, out=out[r]), T, w16.shape[1])
     return out
 
 
@@ -289,15 +300,53 @@ class FusedBackboneEngine(_BlockViews):
         self.dtype = shadow.dtype                            # the run's 16-bit activation type: bf16, or f16 (with loss scaling)
         self._stamped = [p for e in self.blocks for p in e["params"]]
         self._stamp = self._versions()
-        # counts the writes to the 16-bit shadow (optimizer pass, parameter gather, re-cast): what a cached derivative of the shadow
-        # -- the transposed mlp.c_proj weights of the NPCD_OWN_DGELU launch -- is stamped with
+        # counts the writes to the 16-bit shadow (optimizer pass, parameter gather, re-cast): what a derivative of the shadow -- the
+        # transposed shadow below -- is stamped with
         self.shadow_epoch = 0
+        # The TRANSPOSED shadow: W^T of the four Linear weights of every block (12 W^2 16-bit elements per block), which the data
+        # gradients read (_dgrad) and the NPCD_OWN_DGELU launch.  One buffer, allocated by the first refresh (an engine that never
+        # reads it -- NPCD_DGRAD_NN, or only steps below _DGRAD_T_MIN_T rows -- never pays for it) and kept for the life of the
+        # engine -- never from the step arena: its pointers stay put.  A block's part is rewritten by refresh_transposed(), in the
+        # forward, when its stamp is not the shadow's epoch; its views appear in the block's entry (e["<name>_weight_16T"]) once
+        # they hold the weights.  (With lazily gathered parameters every gather of a forward moves the epoch, so the blocks ahead of
+        # the last gather are transposed once more by the NEXT forward although their weights did not change: correct, and one
+        # launch per block per forward at the most.)
+        self._shadowT, self._wT = None, None
+        self._wT_stamp = [None] * len(self.blocks)
+        self.transposed_refreshes = 0                        # launches of the grouped transpose, one per block and refresh
         # the buffers of a step, reused by the next one (npcd.hip.arena) -- for the token counts of a rank of the strong-scaling job,
         # where the host side of a step is as long as its GPU side; NPCD_STEP_ARENA=0 switches it off
         self.arena = harena.StepArena() if _STEP_ARENA else None
 
     def shadow_written(self):
         self.shadow_epoch += 1
+
+    def wants_transposed(self, T):
+        """Whether a step over T token rows reads the transposed shadow."""
+        return _OWN_DGELU or (not _DGRAD_NN and T >= _DGRAD_T_MIN_T)
+
+    def refresh_transposed(self, bi):
+        """Block bi's part of the transposed shadow from its 16-bit shadow (which must be complete: behind wait_range), unless it
+        already is that epoch's: one launch."""
+        if self._wT_stamp[bi] == self.shadow_epoch:
+            return
+        if self._shadowT is None:
+            sizes = [entry[k + "_weight_16"].numel() for entry in self.blocks for k in _LINEARS]
+            self._shadowT = torch.empty(sum(sizes), dtype=self._shadow.dtype, device=self._shadow.device)      # (not an arena request)
+            self._wT, off = [], 0
+            for entry in self.blocks:
+                views = []
+                for k in _LINEARS:
+                    N, K = entry[k + "_weight_16"].shape
+                    views.append(self._shadowT[off:off + N * K].view(K, N))
+                    off += N * K
+                self._wT.append(views)
+        e = self.blocks[bi]
+        hlin.transpose16_group([(e[k + "_weight_16"], v) for k, v in zip(_LINEARS, self._wT[bi])])
+        for k, v in zip(_LINEARS, self._wT[bi]):
+            e[k + "_weight_16T"] = v
+        self._wT_stamp[bi] = self.shadow_epoch
+        self.transposed_refreshes += 1
 
     def _versions(self):
         return [p._version for p in self._stamped]
@@ -463,9 +512,12 @@ class _BackboneFn(torch.autograd.Function):
         with torch.autocast("cuda", enabled=False):
             xs = x.reshape(T, W).contiguous()
             delta = None
+            ctx.transposed = transposed = x.is_cuda and eng.wants_transposed(T)
             for bi, e in enumerate(eng.blocks):
                 if eng.wait_range is not None:
                     eng.wait_range(*eng.block_ranges[bi])        # this block's parameters (gathered lazily by the sharded optimizer)
+                if transposed:
+                    eng.refresh_transposed(bi)                   # (behind the wait: a gathered block is transposed once it has arrived)
                 x1, y1, mean1, rstd1 = ew.add_ln_fwd(xs, delta, e["ln_1_weight"], e["ln_1_bias"], dtype=eng.dtype)
                 x_cur = xs if x1 is None else x1
                 qkv = _linear(e["attn_c_qkv_bias_16"], y1, e["attn_c_qkv_weight_16"])
@@ -508,6 +560,8 @@ class _BackboneFn(torch.autograd.Function):
             last = eng.blocks[-1]
             last["mlp_c_proj_bias_g"].copy_(dx.sum(dim=0))
             side, pending = _wgrad_side_ok(T), []
+            # (the forward of this step brought the transposed shadow up to date, or did not: decided there, once)
+            dgrad_t = ctx.transposed and not _DGRAD_NN and T >= _DGRAD_T_MIN_T
 
             reducing = eng.reducer is not None and eng.reducer.active
 
@@ -526,41 +580,33 @@ class _BackboneFn(torch.autograd.Function):
                 w2 = e["mlp_c_proj_weight_16"]
                 # (the own launch only for what npcd_linear_dgelu_bwd takes -- contiguous 16-bit operands of one type; anything else
                 # goes through the library product + gelu_bwd below instead of raising, like NPCD_ERR_UNSUPPORTED would, ADVICE r4.
-                # The transposed 16-bit copy of the weight is CACHED per block and stamped with the engine's shadow epoch: it is rebuilt
-                # (into the same 8-MB buffer) only after the shadow was written -- once per optimizer step in a plain loop, not at
-                # all between the backwards of a gradient-accumulation loop or of repeated evaluations of one model state.)
-                if (_OWN_DGELU and Tm > 0 and hlin.supported(Tm, 4 * W, W) and dxb.is_contiguous() and h.is_contiguous()
+                # The transposed weight is the engine's transposed shadow, brought up to date by this step's forward.)
+                if (_OWN_DGELU and ctx.transposed and Tm > 0 and hlin.supported(Tm, 4 * W, W) and dxb.is_contiguous() and h.is_contiguous()
                         and w2.is_contiguous() and dxb.dtype == w2.dtype == h.dtype and dxb.dtype in (torch.bfloat16, torch.float16)):
-                    wT = e.get("mlp_c_proj_weight_16T")
-                    if wT is None or e.get("mlp_c_proj_weight_16T_epoch") != eng.shadow_epoch or wT.dtype != w2.dtype:
-                        # (outlives the step: never an arena slot -- a slot would be handed out again by a later step, and the
-                        # rebuild with out=wT takes no slot, so every later request of that step would shift by one)
-                        with harena.paused():
-                            wT = e["mlp_c_proj_weight_16T"] = hlin.transpose16(w2, out=wT if wT is not None and wT.dtype == w2.dtype else None)
-                        e["mlp_c_proj_weight_16T_epoch"] = eng.shadow_epoch
+                    wT = e["mlp_c_proj_weight_16T"]
                     dh = harena.empty_like(h)
                     extra = ew.lib().npcd_colsum_blocks(T - Tm) if Tm < T else 0
                     _, part, rows = hlin.linear_dgelu_bwd(dxb[:Tm], wT, h[:Tm], out=dh[:Tm], extra_part_rows=extra)
                     if Tm < T:       # remainder rows: library product + the separate kernel, partial rows behind the own kernel's
-                        dg = torch.mm(dxb[Tm:], e["mlp_c_proj_weight_16"])
+                        dg = torch.mm(dxb[Tm:], wT.t() if dgrad_t else w2)
                         ew.gelu_bwd(dg, h[Tm:], None, out=dh[Tm:], part_rows=part[rows:])
                         del dg
                     sums.add(part, rows + extra, 4 * W, e["mlp_c_fc_bias_g"])
                     wg((dxb, g, e["mlp_c_proj_weight_g"]))
                     del g, h
                 else:
-                    dg = _dgrad(dxb, e["mlp_c_proj_weight_16"])
+                    dg = _dgrad(dxb, w2, e["mlp_c_proj_weight_16T"] if dgrad_t else None)
                     wg((dxb, g, e["mlp_c_proj_weight_g"]))
                     dh = ew.gelu_bwd(dg, h, e["mlp_c_fc_bias_g"], batch=sums)
                     del dg, g, h
-                dy2 = _dgrad(dh, e["mlp_c_fc_weight_16"])
+                dy2 = _dgrad(dh, e["mlp_c_fc_weight_16"], e["mlp_c_fc_weight_16T"] if dgrad_t else None)
                 wg((dh, y2, e["mlp_c_fc_weight_g"]))
                 del dh, y2
                 dx2, dx2b = ew.ln_bwd(dy2, x2, mean2, rstd2, e["ln_2_weight"], dx, e["ln_2_weight_g"], e["ln_2_bias_g"],
                                       e["attn_c_proj_bias_g"], batch=sums)
                 del dy2, x2, dx, dxb
                 # ---- attention branch: x2 = x + c_proj(attn(c_qkv(ln_1(x)))) ---------------------------
-                da = _dgrad(dx2b, e["attn_c_proj_weight_16"])
+                da = _dgrad(dx2b, e["attn_c_proj_weight_16"], e["attn_c_proj_weight_16T"] if dgrad_t else None)
                 wg((dx2b, a, e["attn_c_proj_weight_g"]))
                 dqkv = harena.empty_like(qkv)
                 q4, g4 = qkv.view(B, n, H, 3 * d), dqkv.view(B, n, H, 3 * d)
@@ -573,7 +619,7 @@ class _BackboneFn(torch.autograd.Function):
                     sums.add(cpart[0], cpart[1], 3 * W, e["attn_c_qkv_bias_g"])
                 else:
                     ew.colsum_bf16(dqkv, e["attn_c_qkv_bias_g"], batch=sums)
-                dy1 = _dgrad(dqkv, e["attn_c_qkv_weight_16"])
+                dy1 = _dgrad(dqkv, e["attn_c_qkv_weight_16"], e["attn_c_qkv_weight_16T"] if dgrad_t else None)
                 wg((dqkv, y1, e["attn_c_qkv_weight_g"]))
                 del dqkv, y1
                 prev_bias_g = eng.blocks[bi - 1]["mlp_c_proj_bias_g"] if bi > 0 else None
