@@ -66,9 +66,10 @@ int npcd_attn_fwd(const void* q, const void* k, const void* v, void* out, float*
                   float scale, int dtype, void* stream);
 
 /* The same with caller-provided scratch (uninitialised): npcd_attn_fwd_workspace_floats(B, n, H) floats, 0 when the shape needs none.
- * With it, a sequence of 256 j + 1 tokens (the denoiser's 512 points + timestep token) runs without a workgroup for its last query
- * row: the waves of each (batch, head) split that row's keys and a small second kernel merges their partial softmax states.
- * workspace == NULL is npcd_attn_fwd. */
+ * Non-zero exactly when the sequence has 256 j + 1 > 256 tokens AND the 64-rows-per-wave form of the forward takes it (n >= 1024, or
+ * NPCD_ATTN_FWD=64; the variable is read at every call, by the sizing function too).  With the scratch, that form runs without a
+ * workgroup for the last query row: the waves of each (batch, head) split that row's keys and a small second kernel merges their
+ * partial softmax states.  workspace == NULL is npcd_attn_fwd. */
 int64_t npcd_attn_fwd_workspace_floats(int B, int n, int H);
 int npcd_attn_fwd_ws(const void* q, const void* k, const void* v, void* out, float* lse, float* workspace,
                      int B, int n, int H, int d,

@@ -23,26 +23,13 @@
 // and the measurements.
 #include <math.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "attention_gen.h"
 #include "common.h"
 
 namespace npcd {
-
-#if defined(NPCD_TIMELINE64) && !defined(NPCD_TIMELINE)
-#define NPCD_TIMELINE NPCD_TIMELINE64      // (the stamps of the 64-row forward: same buffer, same read-back entry point)
-#endif
-#ifdef NPCD_TIMELINE
-// diagnostic build only: s_memtime stamps of one wave (block NPCD_TIMELINE, wave 0), read back with npcd_debug_read
-__device__ long long g_timeline[80];
-#define NPCD_TS(i)                                                                       \
-    do {                                                                                 \
-        if (tl_on) tl[(i)] = __builtin_amdgcn_s_memtime();                               \
-    } while (0)
-#else
-#define NPCD_TS(i) do { } while (0)
-#endif
 
 struct AttnParams {
     const void *q, *k, *v, *out, *dout;
@@ -307,9 +294,6 @@ constexpr float kDeferLog2 = 8.f;
 // Lane (r, hh) of a wave owns, of its row r, the head dimensions 16 s + 8 hh + j of the four MFMA k-steps (the operand
 // fragments qf / dof / kf ...), and of a transposed accumulator pair (o0, o1) the dimensions 8 g + 4 hh + j and 32 + 8 g + 4 hh + j
 // (store_rows_staged).
-#ifndef NPCD_SEED_TAIL
-#define NPCD_SEED_TAIL 1
-#endif
 // All three seeds run on the matrix pipe, which has room (the kernels are bound by vector-instruction issue):
 //   row_bcast_issue: the row as an MFMA operand in which EVERY row (column) of the 32-wide block is that row -- four 16-byte
 //               loads from one address per lane-half; mfma_dot(that, f) is then x . (row of each lane) in all 16 accumulators;
@@ -386,7 +370,7 @@ __device__ __forceinline__ void colsum_zero(float* seg, int lane) {      // a wa
 
 // ---- the edge token of a sequence of 128 j + 1 tokens in the BACKWARD ---------------------------------------------------------
 // With the last key / query seeded as above, the only work left for a fifth workgroup per (batch, head) would be ONE row: dQ of
-// the last query in the dQ pass, dK / dV of the last key in the dK/dV pass.  Those workgroups are not launched (NPCD_EDGE_TOKEN):
+// the last query in the dQ pass, dK / dV of the last key in the dK/dV pass.  Those workgroups are not launched:
 //   * every dQ-pass row already holds P and dS against the last key (the seed); the workgroup's 128 rows are summed into partial
 //     dV_E = sum_i P_i dO_i and dK_E = sum_i dS_i q_i,
 //   * every dK/dV-pass key already holds dS of the last query against it; the workgroup's 128 keys give partial dQ_E = sum_j dS_j k_j,
@@ -394,19 +378,9 @@ __device__ __forceinline__ void colsum_zero(float* seg, int lane) {      // a wa
 // operand rows (edge_reduce; no barrier), and attn_bwd_edge_kernel adds the partials of a (batch, head) in (workgroup, wave) order
 // and writes the three rows.  Scratch: kEdgeFloats floats per (batch, head, 32-row block) behind the row-constant planes of
 // `delta` (npcd_attn_bwd_workspace_floats).
-#ifndef NPCD_EDGE_TOKEN
-#define NPCD_EDGE_TOKEN 1
-#endif
-// DIAGNOSTIC builds only (wrong results, timing): what the seeds / the edge reductions cost
-#ifndef NPCD_DIAG_NO_SEED
-#define NPCD_DIAG_NO_SEED 0
-#endif
-#ifndef NPCD_DIAG_NO_EDGE_REDUCE
-#define NPCD_DIAG_NO_EDGE_REDUCE 0
-#endif
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int kEdgeFloats = 192;       // [dK_E | dV_E | dQ_E] x 64
-__host__ __device__ inline bool edge_mode(int n) { return NPCD_SEED_TAIL && NPCD_EDGE_TOKEN && (n & 127) == 1 && n > 128; }
+__host__ __device__ inline bool edge_mode(int n) { return (n & 127) == 1 && n > 128; }
 
 // this wave's 32 operand rows as a row-major 32 x 64 image at LDS byte offset img_off (wave-private: no barrier)
 template <class V8>
@@ -542,15 +516,12 @@ __device__ __forceinline__ void kv_idle_loop(unsigned char* smem, const E* kb, c
 }
 
 // online-softmax update of one 32-key half from its raw scores; returns the 16-bit P operands.
-// Round 6 (NPCD_FWD32_TRIGGER, default on): the form of the 64-row kernel's blk_softmax -- P = exp2(c S - m) and its lane sum FIRST, against
-// the stored maximum; only when a lane sum leaves (0, 128] (a score more than ~2^7 above the stored maximum, or the very first tile of
-// an unseeded row: exp2(+inf)) the exact row maximum is taken, O / l are rescaled and P is recomputed.  The steady-state stage loses the
-// eight v_max3, the half-wave exchange, the multiply and the compare-with-margin of the per-tile maximum: ~60 instead of ~72 vector
-// instructions per 32 x 32 score block (the kernel is bound by vector issue).  P <= 128 on the fast path; 16-bit relative
-// precision is scale-free.  NPCD_FWD32_TRIGGER=0 builds the round-1..5 form (maximum per tile, advanced when exceeded by 2^8).
-#ifndef NPCD_FWD32_TRIGGER
-#define NPCD_FWD32_TRIGGER 1
-#endif
+// The form of the 64-row kernel's blk_softmax: P = exp2(c S - m) and its lane sum FIRST, against the stored maximum; only when a lane
+// sum leaves (0, 128] (a score more than ~2^7 above the stored maximum, or the very first tile of an unseeded row: exp2(+inf)) the
+// exact row maximum is taken, O / l are rescaled and P is recomputed.  Against a maximum per tile (the form fwd_half keeps for the
+// ragged tail) the steady-state stage loses the eight v_max3, the half-wave exchange, the multiply and the compare-with-margin: ~60
+// instead of ~72 vector instructions per 32 x 32 score block (the kernel is bound by vector issue).  P <= 128 on the
+// fast path; 16-bit relative precision is scale-free.
 constexpr float kTrigger32 = 128.f;
 template <class TR>
 __device__ __forceinline__ float fwd_exp_block(const f32x16& s0, float m, float c, u32x4 (&pw)[2]) {
@@ -567,7 +538,6 @@ __device__ __forceinline__ float fwd_exp_block(const f32x16& s0, float m, float 
 }
 template <class TR>
 __device__ __forceinline__ void fwd_softmax(const f32x16& s0, f32x16& o0, f32x16& o1, float& m, float& l, float c, u32x4 (&pw)[2]) {
-#if NPCD_FWD32_TRIGGER
     float rs = fwd_exp_block<TR>(s0, m, c, pw);
     if (__any(!(rs <= kTrigger32))) {                 // wave-uniform; !(<=) also catches inf / nan
         float mx = fmaxf(s0[0], s0[1]);
@@ -585,31 +555,6 @@ __device__ __forceinline__ void fwd_softmax(const f32x16& s0, f32x16& o0, f32x16
         rs = fwd_exp_block<TR>(s0, m, c, pw);
     }
     l += rs;
-#else
-    float mx = fmaxf(s0[0], s0[1]);
-#pragma unroll
-    for (int i = 2; i < 16; i += 2) mx = fmaxf(fmaxf(mx, s0[i]), s0[i + 1]);
-    mx = half_max(mx) * c;   // c = scale * log2(e) > 0: m lives in the exp2 domain
-    if (__any(mx > m + kDeferLog2)) {
-        const float mn = (mx > m + kDeferLog2) ? mx : m;
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);
-        m = mn;
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            o0[i] *= alpha;
-            o1[i] *= alpha;
-        }
-    }
-    float rs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float a = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[2 * j], c, -m)), b2 = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[2 * j + 1], c, -m));
-        rs += a + b2;
-        pw[j >> 2][j & 3] = pack2<TR>(a, b2);
-    }
-    l += rs;
-#endif
 }
 
 // One pipelined stage of the forward over FULL key tiles: the score products of half (SLOT, KB), then -- behind them on
@@ -632,20 +577,6 @@ __device__ __forceinline__ void fwd_stage(const FragAddr& fa, const typename TR:
     }
     tr_wait();
     f32x16 s0 = {0};
-#ifdef NPCD_DIAG_HALF_MFMA
-    // DIAGNOSTIC BUILD ONLY (tools/probes/gpu_dev_fp8_bound.py): half of the matrix instructions of every stage are dropped (the
-    // operands they would have used are kept alive, all loads, all vector work and the whole control flow stay) -- wrong
-    // results, timing only: what a matrix pipe of TWICE the rate (block-scaled fp8, v_mfma_scale_f32_32x32x64_f8f6f4) could
-    // buy this kernel at best, before the cost of producing fp8 operands.
-#pragma unroll
-    for (int s = 0; s < 2; ++s) s0 = TR::mfma32(__builtin_bit_cast(V8, kr[s]), qf[s], s0);
-    asm volatile("" ::"v"(kr[2]), "v"(kr[3]));
-    if (ACC) {
-        o0 = TR::mfma32(tr_vec<TR>(vt[0][0]), __builtin_bit_cast(V8, pw[0]), o0);
-        o1 = TR::mfma32(tr_vec<TR>(vt[0][1]), __builtin_bit_cast(V8, pw[0]), o1);
-        asm volatile("" ::"v"(vt[1][0].lo), "v"(vt[1][0].hi), "v"(vt[1][1].lo), "v"(vt[1][1].hi), "v"(pw[1]));
-    }
-#else
 #pragma unroll
     for (int s = 0; s < 4; ++s) s0 = TR::mfma32(__builtin_bit_cast(V8, kr[s]), qf[s], s0);
     if (ACC) {
@@ -654,7 +585,6 @@ __device__ __forceinline__ void fwd_stage(const FragAddr& fa, const typename TR:
         o0 = TR::mfma32(tr_vec<TR>(vt[1][0]), __builtin_bit_cast(V8, pw[1]), o0);
         o1 = TR::mfma32(tr_vec<TR>(vt[1][1]), __builtin_bit_cast(V8, pw[1]), o1);
     }
-#endif
     u32x4 nw[2];
     fwd_softmax<TR>(s0, o0, o1, m, l, c, nw);
     pw[0] = nw[0];
@@ -673,19 +603,14 @@ __device__ __forceinline__ void fwd_flush(const FragAddr& fa, f32x16& o0, f32x16
     o0 = TR::mfma32(tr_vec<TR>(vt[1][0]), __builtin_bit_cast(V8, pw[1]), o0);
     o1 = TR::mfma32(tr_vec<TR>(vt[1][1]), __builtin_bit_cast(V8, pw[1]), o1);
 }
-constexpr int kRowxFloats = 68;        // O[64], m, l, pad (272 B: records stay 16-byte aligned)
-__host__ __device__ inline bool rowx_mode(int n) { return NPCD_SEED_TAIL && n > 256 && ((n - 1) & 255) == 0; }
-template <class TR, int SLOT, int RING, bool LEAN> __device__ __forceinline__ void rowx_tile(unsigned char* smem, float c, int lane_in, int wave, float* rec);
 template <class TR, int SLOT>
 __device__ __forceinline__ void fwd_step(unsigned char* smem, const FragAddr& fa, const DmaLane& dl, const typename TR::elem* kb,
                                          const typename TR::elem* vb, int64_t sn, int t, int nt, int n, int wave, int lane,
-                                         const typename TR::vec8 (&qf)[4], f32x16& o0, f32x16& o1, float& m, float& l, float c, u32x4 (&pw)[2],
-                                         int xt, float* xrec) {
+                                         const typename TR::vec8 (&qf)[4], f32x16& o0, f32x16& o1, float& m, float& l, float c, u32x4 (&pw)[2]) {
     constexpr int PREV = (SLOT + 2) % 3;
     fwd_stage<TR, SLOT, 0, PREV, 1, true>(fa, qf, o0, o1, m, l, c, pw);
     kv_mid<typename TR::elem, SLOT>(smem, kb, vb, sn, t, nt, n, wave, lane, dl);
     fwd_stage<TR, SLOT, 1, SLOT, 0, true>(fa, qf, o0, o1, m, l, c, pw);
-    if (xt >= 0 && t == xt) rowx_tile<TR, SLOT, 3, true>(smem, c, lane, wave, xrec);      // (wave-uniform) this wave's share of the last query row
 }
 // the ragged last key tile (fewer than 64 keys): simple, masked, not pipelined
 template <class TR, int SLOT>
@@ -698,28 +623,24 @@ __device__ __forceinline__ void fwd_tail(const FragAddr& fa, const typename TR::
 #ifndef NPCD_FWD_WAVES
 #define NPCD_FWD_WAVES 2
 #endif
-// ROWX (opt-in, NPCD_ATTN_ROWX32=1): see `rowx` below.  Measured at cfg-D: 142-145 us against 128-130 us without it (same process,
-// same box, event-bracketed) -- the fifth workgroup it removes is cheap (one active wave, no matrix work) while the row's
-// vector work lands on eight busy waves and the merge is one more launch; as a template parameter so that the default
-// instantiation keeps its 166 registers (three waves per SIMD: 128 against 148 us at two).
-template <class TR, bool ROWX>
+// LDS of both forwards: the three ring slots, then 1,280 bytes that only the 64-row form uses (rowx_tile)
+constexpr int kFwdRing = 3 * 16384, kFwdLds = kFwdRing + 1024 + 256;
+// A sequence of 128 j + 1 tokens keeps a workgroup for its single last query row here: splitting that row over the other waves (the
+// 64-row form's rowx_tile) measured slower in this kernel (docs/experiments.md R4.2, R11.1; docs/patches/r11_attn_fwd32_row_split.patch).
+template <class TR>
 __global__ __launch_bounds__(256, NPCD_FWD_WAVES) void attn_fwd_kernel(AttnParams p) {
     using E = typename TR::elem;
     using V8 = typename TR::vec8;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[3 * 16384 + 1024 + 256];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kFwdLds];
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // A sequence of 64 j + 1 tokens (the denoiser's: 512 points + the timestep token) would end in a key tile with ONE key.
     // That key never enters the ring: its score and its value row SEED the online softmax (m = s, l = 1, O = v) from a few
     // direct loads and six matrix instructions while the first tiles are still in flight (row_bcast / outer_seed), and the stream
     // below covers nk = n - 1 keys, all in full tiles.
-    const bool seeded = NPCD_SEED_TAIL && (p.n & 63) == 1 && p.n > 64;          // kernel-uniform
+    const bool seeded = (p.n & 63) == 1 && p.n > 64;          // kernel-uniform
     const int n = p.n, nk = seeded ? n - 1 : n, nt = (nk + 63) >> 6, nfull = nk >> 6;
-    // ROWX: 256 j + 1 tokens with scratch (round 4; the 64-row form had it): no FIFTH workgroup for the single last query row -- at
-    // n = 513 it holds a slot for a whole pass over K / V, 1,024 of the 5,120 workgroups of a launch -- the first nt waves of the
-    // (batch, head) split that row's keys instead (rowx_tile, one resident key tile each), attn_fwd_rowx_merge_kernel combines them
-    const bool rowx = ROWX && p.rowx != nullptr && rowx_mode(p.n);               // kernel-uniform
-    const int nqt = rowx ? nk >> 7 : (n + 127) >> 7;
+    const int nqt = (n + 127) >> 7;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int qt = bid % nqt, bh = bid / nqt, h = bh % p.H, b = bh / p.H;
     const E* qb = static_cast<const E*>(p.q) + b * p.sb + h * p.sh;
@@ -730,16 +651,13 @@ __global__ __launch_bounds__(256, NPCD_FWD_WAVES) void attn_fwd_kernel(AttnParam
     const int qrow = q0 + r;
     const float c = p.scale_log2;
     const DmaLane dl = dma_lane<E>(p.sn, lane);
-    const int xt = (ROWX && rowx && qt * 4 + wave < nt) ? qt * 4 + wave : -1;   // the key tile this wave takes for the last query row
-    float* xrec = (ROWX && xt >= 0) ? p.rowx + ((int64_t)bh * nt + xt) * kRowxFloats : nullptr;
 
     // Q fragments stay unscaled (scores are scaled in fp32 after the MFMA, identically in fwd and bwd, so
     // that P recomputed in the backward matches the forward's LSE even for very large logits)
     u32x4 qraw[4], keraw[4] = {};
     uint32_t vx0 = 0, vx1 = 0;
     row_bcast_issue(qb + (int64_t)min(qrow, n - 1) * p.sn, hh, qraw);            // (one row per lane here, not a broadcast)
-    const bool seed = seeded && !NPCD_DIAG_NO_SEED;
-    if (seed) {
+    if (seeded) {
         row_bcast_issue(kb + (int64_t)(n - 1) * p.sn, hh, keraw);
         vx0 = gload_u16(vb + (int64_t)(n - 1) * p.sn + r);
         vx1 = gload_u16(vb + (int64_t)(n - 1) * p.sn + 32 + r);
@@ -754,7 +672,7 @@ __global__ __launch_bounds__(256, NPCD_FWD_WAVES) void attn_fwd_kernel(AttnParam
     arrived4(qraw, qf);
     f32x16 o0 = {0}, o1 = {0};
     float m = -INFINITY, l = 0.f;
-    if (seed) {
+    if (seeded) {
         V8 ke[4];
         arrived4(keraw, ke);
         NPCD_ARRIVED(vx0);
@@ -763,8 +681,6 @@ __global__ __launch_bounds__(256, NPCD_FWD_WAVES) void attn_fwd_kernel(AttnParam
         l = 0.5f;                                     // P = 1; the two half-wave partial sums are added at the end
         outer_seed<TR>(vx0, vx1, 1.f, lane, o0, o1);
     }
-    if (rowx && wave == 0)       // the last query row -> LDS (128 B, lanes 32..63 repeat lanes 0..31): lands with the first tiles
-        dma4_issue(qb + (int64_t)(n - 1) * p.sn, (uint32_t)((lane & 31) * 4), __builtin_amdgcn_readfirstlane(lds_addr(smem) + 3 * 16384 + 1024));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -779,11 +695,10 @@ __global__ __launch_bounds__(256, NPCD_FWD_WAVES) void attn_fwd_kernel(AttnParam
         fwd_stage<TR, 0, 0, 2, 1, false>(fa, qf, o0, o1, m, l, c, pw);
         kv_mid<E, 0>(smem, kb, vb, p.sn, 0, nt, nk, wave, lane, dl);
         fwd_stage<TR, 0, 1, 0, 0, true>(fa, qf, o0, o1, m, l, c, pw);
-        if (ROWX && xt == 0) rowx_tile<TR, 0, 3, true>(smem, c, lane, wave, xrec);
         for (int t = 1; t < nfull; t += 3) {
-            fwd_step<TR, 1>(smem, fa, dl, kb, vb, p.sn, t, nt, nk, wave, lane, qf, o0, o1, m, l, c, pw, xt, xrec);
-            if (t + 1 < nfull) fwd_step<TR, 2>(smem, fa, dl, kb, vb, p.sn, t + 1, nt, nk, wave, lane, qf, o0, o1, m, l, c, pw, xt, xrec);
-            if (t + 2 < nfull) fwd_step<TR, 0>(smem, fa, dl, kb, vb, p.sn, t + 2, nt, nk, wave, lane, qf, o0, o1, m, l, c, pw, xt, xrec);
+            fwd_step<TR, 1>(smem, fa, dl, kb, vb, p.sn, t, nt, nk, wave, lane, qf, o0, o1, m, l, c, pw);
+            if (t + 1 < nfull) fwd_step<TR, 2>(smem, fa, dl, kb, vb, p.sn, t + 1, nt, nk, wave, lane, qf, o0, o1, m, l, c, pw);
+            if (t + 2 < nfull) fwd_step<TR, 0>(smem, fa, dl, kb, vb, p.sn, t + 2, nt, nk, wave, lane, qf, o0, o1, m, l, c, pw);
         }
         const int last = (nfull - 1) % 3;
         if (last == 0) fwd_flush<TR, 0, 1>(fa, o0, o1, pw);
@@ -846,16 +761,8 @@ __device__ __forceinline__ void blk_advance_max(const f32x16& s, QBlk& b, float 
 }
 
 // scores (exp2 domain) -> exp2(s - m) as packed 16-bit P operands + this lane's partial row sum; no state is touched
-#ifndef NPCD_DIAG_F64
-#define NPCD_DIAG_F64 0      // DIAGNOSTIC builds (wrong results, timing only): 1 no softmax arithmetic, 2 no matrix instructions in the
-#endif                       // stages, 3 no LDS fragment reads in the stages, 4 no ring refill / barrier per tile
 template <class TR>
 __device__ __forceinline__ float blk_exp(const f32x16& s, float m, float c, u32x4 (&pw)[2]) {
-#if NPCD_DIAG_F64 == 1
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pw[j >> 2][j & 3] = pack2<TR>(s[2 * j], s[2 * j + 1]);
-    return 1.f;
-#endif
     float pr[16];
     float rs = 0.f;
 #pragma unroll
@@ -890,11 +797,6 @@ __device__ __forceinline__ void fwd64_stage(const FragAddr& fa, const typename T
     constexpr int KT = SLOT * 16384 + KB * 4096, PV = PSLOT * 16384 + 8192;
     u32x4 kr[4];
     TrPair vt[2][2];
-#if NPCD_DIAG_F64 == 3
-    for (int s = 0; s < 4; ++s) kr[s] = __builtin_bit_cast(u32x4, qA[s]);
-    for (int g = 0; g < 2; ++g)
-        for (int h2 = 0; h2 < 2; ++h2) { vt[g][h2].lo = u32x2{pwA[0][0], pwA[0][1]}; vt[g][h2].hi = u32x2{pwB[0][0], pwB[0][1]}; }
-#else
     kr[0] = lds_b128_issue<KT>(fa.row[0]);
     kr[1] = lds_b128_issue<KT>(fa.row[1]);
     kr[2] = lds_b128_issue<KT>(fa.row[2]);
@@ -904,19 +806,12 @@ __device__ __forceinline__ void fwd64_stage(const FragAddr& fa, const typename T
         vt[1][0] = tr_issue_at<PV, PKB * 2 + 1>(fa, 0); vt[1][1] = tr_issue_at<PV, PKB * 2 + 1>(fa, 1);
     }
     tr_wait();
-#endif
     f32x16 sA = {0}, sB = {0};
-#if NPCD_DIAG_F64 == 2
-    for (int i = 0; i < 16; ++i) { sA[i] = __uint_as_float(kr[i & 3][i >> 2]) * 1e-30f; sB[i] = __uint_as_float(kr[(i + 1) & 3][i >> 2]) * 1e-30f; }
-    if (ACC) { asm volatile("" ::"v"(vt[0][0].lo), "v"(vt[0][1].lo), "v"(vt[1][0].lo), "v"(vt[1][1].lo), "v"(vt[0][0].hi), "v"(vt[0][1].hi), "v"(vt[1][0].hi), "v"(vt[1][1].hi)); }
-    if (false) {
-#else
 #pragma unroll
     for (int s = 0; s < 4; ++s) sA = TR::mfma32(__builtin_bit_cast(V8, kr[s]), qA[s], sA);
 #pragma unroll
     for (int s = 0; s < 4; ++s) sB = TR::mfma32(__builtin_bit_cast(V8, kr[s]), qB[s], sB);
     if (ACC) {
-#endif
         A.o0 = TR::mfma32(tr_vec<TR>(vt[0][0]), __builtin_bit_cast(V8, pwA[0]), A.o0);
         A.o1 = TR::mfma32(tr_vec<TR>(vt[0][1]), __builtin_bit_cast(V8, pwA[0]), A.o1);
         A.o0 = TR::mfma32(tr_vec<TR>(vt[1][0]), __builtin_bit_cast(V8, pwA[1]), A.o0);
@@ -982,11 +877,14 @@ __device__ __forceinline__ float wave_reduce64(float x, Op op) {
 }
 __device__ __forceinline__ float wave_max64(float x) { return wave_reduce64(x, [](float a, float b) { return fmaxf(a, b); }); }
 __device__ __forceinline__ float wave_sum64(float x) { return wave_reduce64(x, [](float a, float b) { return a + b; }); }
-// LEAN: half-size batches of LDS reads (the 32-row forward has ~70 registers free between two stages, the 64-row one ~100)
-// rowx_core: `base` + KT / VT = the LDS byte addresses of the K / V tile, `scr` = 256 bytes of wave-private scratch (the row's P),
-// `qxa` = the 128-byte copy of the last query row; rowx_tile = the ring form of it (ring slot SLOT, scratch behind the RING slots)
-template <class TR, int KT, int VT, bool LEAN>
-__device__ __forceinline__ void rowx_core(uint32_t base, uint32_t scr, uint32_t qxa, float c, int lane_in, float* rec) {
+// The key tile is the one in ring slot SLOT; behind the ring: 256 bytes of scratch per wave (the row's P), then the 128-byte copy of
+// the last query row (made by the prologue).
+constexpr int kRowxFloats = 68;        // O[64], m, l, pad (272 B: records stay 16-byte aligned)
+__host__ __device__ inline bool rowx_mode(int n) { return n > 256 && ((n - 1) & 255) == 0; }
+template <class TR, int SLOT>
+__device__ __forceinline__ void rowx_tile(unsigned char* smem, float c, int lane_in, int wave, float* rec) {
+    constexpr int KT = SLOT * 16384, VT = KT + 8192;
+    const uint32_t base = lds_addr(smem), scr = base + kFwdRing + wave * 256, qxa = base + kFwdRing + 1024;
     // Everything lane-dependent in here is derived from an OPAQUE copy of the lane number: otherwise the compiler hoists the ~100
     // loop-invariant LDS addresses of the three ring-slot instances out of the tile loop and spills them (82 spilled registers,
     // the whole kernel 20 % slower).  Ring slot and row numbers go into the instructions' immediate offsets.
@@ -996,24 +894,6 @@ __device__ __forceinline__ void rowx_core(uint32_t base, uint32_t scr, uint32_t 
     // every lane reads the same address), two 16-byte chunks at a time so that the main loop's state stays in registers
     const uint32_t krow = base + lane * 128, ksw = (uint32_t)tile_swz(lane) << 4;
     float s0 = 0.f, s1 = 0.f;
-    if constexpr (LEAN) {
-#pragma unroll
-        for (int c2 = 0; c2 < 8; c2 += 2) {
-            u32x4 kv[2], qv[2];
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch) kv[ch] = lds_b128_issue<KT>(krow + (((uint32_t)(c2 + ch) << 4) ^ ksw));
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(qv[0]) : "v"(qxa), "n"(c2 * 16) : "memory");
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(qv[1]) : "v"(qxa), "n"(c2 * 16 + 16) : "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kv[0]), "+v"(kv[1]), "+v"(qv[0]), "+v"(qv[1])::"memory");
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch) {
-                s0 = TR::dot2(kv[ch][0], qv[ch][0], s0);
-                s1 = TR::dot2(kv[ch][1], qv[ch][1], s1);
-                s0 = TR::dot2(kv[ch][2], qv[ch][2], s0);
-                s1 = TR::dot2(kv[ch][3], qv[ch][3], s1);
-            }
-        }
-    } else {
 #pragma unroll
     for (int c4 = 0; c4 < 8; c4 += 4) {                   // (between two stages ~100 registers are free: 32 of them here)
         u32x4 kv[4], qv[4];
@@ -1032,7 +912,6 @@ __device__ __forceinline__ void rowx_core(uint32_t base, uint32_t scr, uint32_t 
             s1 = TR::dot2(kv[ch][3], qv[ch][3], s1);
         }
     }
-    }
     const float sc = (s0 + s1) * c;                       // exp2 domain
     const float m = wave_max64(sc);
     const float pj = __builtin_amdgcn_exp2f(sc - m);
@@ -1040,11 +919,11 @@ __device__ __forceinline__ void rowx_core(uint32_t base, uint32_t scr, uint32_t 
     asm volatile("ds_write_b32 %0, %1" ::"v"(scr + lane * 4), "v"(pj) : "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     // O[d] = sum_j p_j v_j[d]: lane = (key parity, d-pair); V row j = 2 i + parity, elements 2 dp, 2 dp + 1.  tile_swz(j) only
-    // depends on i, so a read's address is one lane register XOR a constant + an immediate.  Eight keys per batch in flight.
+    // depends on i, so a read's address is one lane register XOR a constant + an immediate.  Sixteen keys per batch in flight.
     const int dp = lane & 31, par = lane >> 5;
     const uint32_t vrow = base + par * 128 + (dp & 3) * 4, vch = (uint32_t)(dp >> 2) << 4, prow = scr + par * 4;
     float o0 = 0.f, o1 = 0.f;
-    constexpr int VB = LEAN ? 4 : 16;
+    constexpr int VB = 16;
 #pragma unroll
     for (int i0 = 0; i0 < 32; i0 += VB) {
         uint32_t vv[16];
@@ -1064,15 +943,11 @@ __device__ __forceinline__ void rowx_core(uint32_t base, uint32_t scr, uint32_t 
 #undef NPCD_RX
             }
         }
-        if constexpr (LEAN)
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vv[0]), "+v"(vv[1]), "+v"(vv[2]), "+v"(vv[3]), "+v"(pp[0]), "+v"(pp[1]), "+v"(pp[2]), "+v"(pp[3])::"memory");
-        else
-            asm volatile("s_waitcnt lgkmcnt(0)"
+        asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(vv[0]), "+v"(vv[1]), "+v"(vv[2]), "+v"(vv[3]), "+v"(vv[4]), "+v"(vv[5]), "+v"(vv[6]), "+v"(vv[7]), "+v"(pp[0]), "+v"(pp[1]),
                        "+v"(pp[2]), "+v"(pp[3]), "+v"(pp[4]), "+v"(pp[5]), "+v"(pp[6]), "+v"(pp[7])::"memory");
-        if constexpr (!LEAN)
-            asm volatile("" : "+v"(vv[8]), "+v"(vv[9]), "+v"(vv[10]), "+v"(vv[11]), "+v"(vv[12]), "+v"(vv[13]), "+v"(vv[14]), "+v"(vv[15]), "+v"(pp[8]), "+v"(pp[9]),
-                           "+v"(pp[10]), "+v"(pp[11]), "+v"(pp[12]), "+v"(pp[13]), "+v"(pp[14]), "+v"(pp[15]));
+        asm volatile("" : "+v"(vv[8]), "+v"(vv[9]), "+v"(vv[10]), "+v"(vv[11]), "+v"(vv[12]), "+v"(vv[13]), "+v"(vv[14]), "+v"(vv[15]), "+v"(pp[8]), "+v"(pp[9]),
+                       "+v"(pp[10]), "+v"(pp[11]), "+v"(pp[12]), "+v"(pp[13]), "+v"(pp[14]), "+v"(pp[15]));
 #pragma unroll
         for (int i = 0; i < VB; ++i) {
             o0 = __builtin_fmaf(pp[i], TR::lo(vv[i]), o0);
@@ -1083,11 +958,6 @@ __device__ __forceinline__ void rowx_core(uint32_t base, uint32_t scr, uint32_t 
     o1 = half_sum(o1);
     if (lane < 32) *reinterpret_cast<float2*>(rec + 2 * dp) = make_float2(o0, o1);
     if (lane == 0) *reinterpret_cast<float2*>(rec + 64) = make_float2(m, l);
-}
-template <class TR, int SLOT, int RING, bool LEAN>
-__device__ __forceinline__ void rowx_tile(unsigned char* smem, float c, int lane_in, int wave, float* rec) {
-    const uint32_t base = lds_addr(smem);
-    rowx_core<TR, SLOT * 16384, SLOT * 16384 + 8192, LEAN>(base, base + RING * 16384 + wave * 256, base + RING * 16384 + 1024, c, lane_in, rec);
 }
 // one 64-thread block per (batch, head): combine the nw partial states, add the pair (x, x), write the row and its LSE
 template <class E>
@@ -1119,11 +989,9 @@ __device__ __forceinline__ void fwd64_step(unsigned char* smem, const FragAddr& 
                                            u32x4 (&pwA)[2], u32x4 (&pwB)[2], int xt, float c, float* xrec) {
     constexpr int PREV = (SLOT + 2) % 3;
     fwd64_stage<TR, SLOT, 0, PREV, 1, true>(fa, qA, qB, A, B, pwA, pwB, c);
-#if NPCD_DIAG_F64 != 4
     kv_mid<typename TR::elem, SLOT>(smem, kb, vb, sn, t, nt, n, wave, lane, dl);
-#endif
     fwd64_stage<TR, SLOT, 1, SLOT, 0, true>(fa, qA, qB, A, B, pwA, pwB, c);
-    if (t == xt) rowx_tile<TR, SLOT, 3, false>(smem, c, lane, wave, xrec);      // (wave-uniform) this wave's share of the last query row
+    if (t == xt) rowx_tile<TR, SLOT>(smem, c, lane, wave, xrec);      // (wave-uniform) this wave's share of the last query row
 }
 // one 32-key half of the ragged last key tile for one block: masked, exact maximum, not pipelined
 template <class TR, int SLOT, int KB>
@@ -1167,10 +1035,10 @@ template <class TR>
 __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(AttnParams p) {
     using E = typename TR::elem;
     using V8 = typename TR::vec8;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[3 * 16384 + 1024 + 256];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kFwdLds];
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool seeded = NPCD_SEED_TAIL && (p.n & 63) == 1 && p.n > 64;          // kernel-uniform (see attn_fwd_kernel)
+    const bool seeded = (p.n & 63) == 1 && p.n > 64;          // kernel-uniform (see attn_fwd_kernel)
     const int n = p.n, nk = seeded ? n - 1 : n, nt = (nk + 63) >> 6, nfull = nk >> 6;
     // 256 j + 1 tokens with scratch: no workgroup for the last query row, the waves of the (batch, head) split its keys (rowx_tile)
     const bool rowx = p.rowx != nullptr && rowx_mode(p.n);                       // kernel-uniform
@@ -1196,26 +1064,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(AttnParams p) {
         vx0 = gload_u16(vb + (int64_t)(n - 1) * p.sn + r);
         vx1 = gload_u16(vb + (int64_t)(n - 1) * p.sn + 32 + r);
     }
-#ifdef NPCD_TIMELINE64
-    const bool tl_on = (blockIdx.x == NPCD_TIMELINE64) && wave == 0;
-    long long tl[40];
-    for (int i = 0; i < 40; ++i) tl[i] = 0;
-    NPCD_TS(0);
-#endif
     if (nt > 0) dma_tile_pair(smem, kb, p.sn, vb, p.sn, 0, nk, wave, lane);
     if (nt > 1) dma_tile_pair(smem + 16384, kb, p.sn, vb, p.sn, 64, nk, wave, lane);
-#ifdef NPCD_TIMELINE64
-    NPCD_TS(1);
-#endif
     if (nt > 1) vm_wait<8>();
     else if (nt > 0) vm_wait<4>();
     else vm_wait<0>();
     V8 qA[4], qB[4];
     arrived4(qrawA, qA);
     arrived4(qrawB, qB);
-#ifdef NPCD_TIMELINE64
-    NPCD_TS(2);
-#endif
     QBlk A, B;
     A.o0 = A.o1 = B.o0 = B.o1 = f32x16{0};
     A.m = B.m = -INFINITY;
@@ -1232,7 +1088,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(AttnParams p) {
         outer_seed<TR>(vx0, vx1, 1.f, lane, B.o0, B.o1);
     }
     if (rowx && wave == 0)       // the last query row -> LDS (128 B, lanes 32..63 repeat lanes 0..31): lands with the first tiles
-        dma4_issue(qb + (int64_t)(n - 1) * p.sn, (uint32_t)((lane & 31) * 4), __builtin_amdgcn_readfirstlane(lds_addr(smem) + 3 * 16384 + 1024));
+        dma4_issue(qb + (int64_t)(n - 1) * p.sn, (uint32_t)((lane & 31) * 4), __builtin_amdgcn_readfirstlane(lds_addr(smem) + kFwdRing + 1024));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1242,25 +1098,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(AttnParams p) {
     }
     const FragAddr fa = frag_addr(smem, lane);
     u32x4 pwA[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}}, pwB[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
-#ifdef NPCD_TIMELINE64
-    NPCD_TS(3);
-#define NPCD_TS_TILE(t) do { if (tl_on && (t) < 14) { __builtin_amdgcn_sched_barrier(0); tl[4 + (t)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define NPCD_TS_TILE(t) do { } while (0)
-#endif
     if (nfull > 0) {
         fwd64_stage<TR, 0, 0, 2, 1, false>(fa, qA, qB, A, B, pwA, pwB, c);
         kv_mid<E, 0>(smem, kb, vb, p.sn, 0, nt, nk, wave, lane, dl);
         fwd64_stage<TR, 0, 1, 0, 0, true>(fa, qA, qB, A, B, pwA, pwB, c);
-        if (xt == 0) rowx_tile<TR, 0, 3, false>(smem, c, lane, wave, xrec);
-        NPCD_TS_TILE(0);
+        if (xt == 0) rowx_tile<TR, 0>(smem, c, lane, wave, xrec);
         for (int t = 1; t < nfull; t += 3) {
             fwd64_step<TR, 1>(smem, fa, dl, kb, vb, p.sn, t, nt, nk, wave, lane, qA, qB, A, B, pwA, pwB, xt, c, xrec);
-            NPCD_TS_TILE(t);
             if (t + 1 < nfull) fwd64_step<TR, 2>(smem, fa, dl, kb, vb, p.sn, t + 1, nt, nk, wave, lane, qA, qB, A, B, pwA, pwB, xt, c, xrec);
-            NPCD_TS_TILE(t + 1);
             if (t + 2 < nfull) fwd64_step<TR, 0>(smem, fa, dl, kb, vb, p.sn, t + 2, nt, nk, wave, lane, qA, qB, A, B, pwA, pwB, xt, c, xrec);
-            NPCD_TS_TILE(t + 2);
         }
         const int last = (nfull - 1) % 3;
         if (last == 0) fwd64_flush<TR, 0, 1>(fa, A, B, pwA, pwB);
@@ -1275,15 +1121,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(AttnParams p) {
         else if (slot == 1) fwd64_tail<TR, 1>(fa, qA, qB, A, B, c, nfull * 64, nk, hh);
         else fwd64_tail<TR, 2>(fa, qA, qB, A, B, c, nfull * 64, nk, hh);
     }
-#ifdef NPCD_TIMELINE64
-    NPCD_TS(20);
-#endif
     A.l = half_sum(A.l);
     B.l = half_sum(B.l);
     __builtin_amdgcn_s_barrier();     // every wave has left the ring: 4 KiB of it per wave stage the output rows
-#ifdef NPCD_TIMELINE64
-    NPCD_TS(21);
-#endif
     E* orow0 = static_cast<E*>(p.o_w) + b * p.osb + (int64_t)q0 * p.osn + h * p.osh;
     store_rows_staged<TR>(smem + wave * 4096, orow0, p.osn, n - q0, A.o0, A.o1, 1.f / A.l, lane);
     if (q0 + 32 < n) store_rows_staged<TR>(smem + wave * 4096, orow0 + 32 * p.osn, p.osn, n - q0 - 32, B.o0, B.o1, 1.f / B.l, lane);
@@ -1292,154 +1132,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(AttnParams p) {
         if (q0 + r < n) lrow[q0 + r] = A.m * kLn2 + logf(A.l);
         if (q0 + 32 + r < n) lrow[q0 + 32 + r] = B.m * kLn2 + logf(B.l);
     }
-#ifdef NPCD_TIMELINE64
-    NPCD_TS(22);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    NPCD_TS(23);
-    if (tl_on && lane == 0)
-        for (int i = 0; i < 40; ++i) g_timeline[i] = tl[i];
-#endif
-}
-
-// ============================================================================================
-// forward, third form: K and V of a (batch, head) RESIDENT in LDS (sequences of 513 tokens: the denoiser's)
-// ============================================================================================
-// What the stage-loop probe says (tools/probes/attn_shape_probe.hip, round 5): the pipelined stage of the kernels above runs at
-// 408 cycles per 32 x 32 score block and SIMD with three waves per SIMD, 499 with two, 780 with one -- 1.0 / 0.88 / 0.70 PFLOP/s --
-// while the forward at n = 513 delivers 0.59-0.65: more than 40 % of its time is NOT the loop.  It is the shape of the launch:
-// five workgroups per (batch, head), each streaming all of K / V through a ring for 128 (or one!) query rows, a prologue and an
-// epilogue per eight tiles, a barrier + DMA wait per tile, 6.67 rounds of workgroups on the chip.
-// Here ONE workgroup of eight waves owns a whole (batch, head): its 512 keys x (K, V) = 128 KB are requested by LDS-DMA up front, tile
-// after tile, and stay; a wave owns 64 query rows (the two-block stage of the 64-row form: every fragment read feeds two matrix
-// instructions) and walks the eight tiles as they land -- one counted wait + barrier per tile, nothing to refill, no ring; the
-// 513th key seeds the softmax state as before; the 513th QUERY row is split over the eight waves (wave w takes the keys of tile w:
-// rowx_core) and merged by wave 0 through LDS -- no fifth workgroup, no scratch in HBM, no second launch.  K / V are read from HBM
-// exactly once per (batch, head); 1,024 workgroups = four rounds of one per CU (two waves per SIMD).
-// LDS: [0, 16 KB) the last query row, the eight partial records of its softmax, per-wave scratch; [16 KB + 16 KB t) tile t (K | V).
-// The fragment addresses point ONE TILE BELOW the current tile and are advanced by 16 KB per tile, so that every stage is the same
-// instantiation (ring slot 1, previous slot 0) and every offset fits the instructions' 16-bit immediate.
-constexpr int kResMisc = 16384, kResRecOff = 256, kResScrOff = 4096, kResTiles = 8;
-constexpr int kResLds = kResMisc + kResTiles * 16384;
-__host__ __device__ inline bool fwd_res_shape(int n) { return n == 64 * kResTiles + 1; }
-
-template <class E>
-__device__ __forceinline__ void rowx_merge_lds(const AttnParams& p, int b, int h, const float* rec, int nw, int d) {
-    const int x = p.n - 1;
-    const E* qx = static_cast<const E*>(p.q) + b * p.sb + (int64_t)x * p.sn + h * p.sh;
-    const E* kx = static_cast<const E*>(p.k) + b * p.sb + (int64_t)x * p.sn + h * p.sh;
-    const E* vx = static_cast<const E*>(p.v) + b * p.sb + (int64_t)x * p.sn + h * p.sh;
-    const float sxx = wave_sum64((float)qx[d] * (float)kx[d]) * p.scale_log2;
-    float M = sxx;
-    for (int w = 0; w < nw; ++w) M = fmaxf(M, rec[w * kRowxFloats + 64]);
-    const float pxx = __builtin_amdgcn_exp2f(sxx - M);
-    float L = pxx, O = pxx * (float)vx[d];
-    for (int w = 0; w < nw; ++w) {
-        const float a = __builtin_amdgcn_exp2f(rec[w * kRowxFloats + 64] - M);
-        L += a * rec[w * kRowxFloats + 65];
-        O += a * rec[w * kRowxFloats + d];
-    }
-    E* orow = static_cast<E*>(p.o_w) + b * p.osb + (int64_t)x * p.osn + h * p.osh;
-    orow[d] = (E)(O / L);
-    if (d == 0) p.lse[(int64_t)(b * p.H + h) * p.n + x] = M * kLn2 + logf(L);
-}
-
-template <int N> struct ResWait { static __device__ __forceinline__ void at(int t) { if (t == N) vm_wait<2 * (6 - N)>(); else ResWait<N + 1>::at(t); } };
-template <> struct ResWait<7> { static __device__ __forceinline__ void at(int) {} };
-
-template <class TR>
-__global__ __launch_bounds__(512, 2) void attn_fwd_res_kernel(AttnParams p) {
-    using E = typename TR::elem;
-    using V8 = typename TR::vec8;
-    extern __shared__ __attribute__((aligned(16))) unsigned char rsmem[];
-    unsigned char* tiles = rsmem + kResMisc;
-    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = p.n, nk = n - 1;
-    const int bh = xcd_remap(blockIdx.x, gridDim.x), h = bh % p.H, b = bh / p.H;
-    const E* qb = static_cast<const E*>(p.q) + b * p.sb + h * p.sh;
-    const E* kb = static_cast<const E*>(p.k) + b * p.sb + h * p.sh;
-    const E* vb = static_cast<const E*>(p.v) + b * p.sb + h * p.sh;
-    const int q0 = wave * 64;
-    const float c = p.scale_log2;
-    const DmaLane dl = dma_lane<E>(p.sn, lane);
-    // ---- prologue: the wave's query rows and the seed rows (oldest), the last query row -> LDS, then ALL tiles ------------------
-    u32x4 qrawA[4], qrawB[4], keraw[4];
-    row_bcast_issue(qb + (int64_t)(q0 + r) * p.sn, hh, qrawA);             // (one row per lane, not a broadcast)
-    row_bcast_issue(qb + (int64_t)(q0 + 32 + r) * p.sn, hh, qrawB);
-    row_bcast_issue(kb + (int64_t)nk * p.sn, hh, keraw);
-    uint32_t vx0 = gload_u16(vb + (int64_t)nk * p.sn + r), vx1 = gload_u16(vb + (int64_t)nk * p.sn + 32 + r);
-    // (every wave issues the 128-byte copy of the last query row -- same bytes, same place -- so that all waves count the same DMAs)
-    dma4_issue(qb + (int64_t)nk * p.sn, (uint32_t)((lane & 31) * 4), __builtin_amdgcn_readfirstlane(lds_addr(rsmem)));
-    {
-        // wave w: rows 16 (w & 3) .. + 15 of every K (w < 4) or V (w >= 4) tile = two 1-KiB pieces per tile
-        const bool second = wave >= 4;
-        const int w4 = wave & 3;
-        const char* sbase = reinterpret_cast<const char*>((second ? vb : kb) + (int64_t)(w4 * 16) * p.sn);
-        const uint32_t dst0 = lds_addr(tiles) + (second ? 8192 : 0) + w4 * 2048;
-#pragma unroll
-        for (int t = 0; t < kResTiles; ++t)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                dma16_issue(sbase + ((int64_t)t * 64 + i * 8) * p.sn * (int64_t)sizeof(E), dl.off[i & 1], __builtin_amdgcn_readfirstlane(dst0 + t * 16384 + i * 1024));
-    }
-    vm_wait<2 * kResTiles + 1>();                     // the register loads have landed; the DMAs may all still be in flight
-    V8 qA[4], qB[4], ke[4];
-    arrived4(qrawA, qA);
-    arrived4(qrawB, qB);
-    arrived4(keraw, ke);
-    NPCD_ARRIVED(vx0);
-    NPCD_ARRIVED(vx1);
-    QBlk A, B;
-    A.o0 = A.o1 = B.o0 = B.o1 = f32x16{0};
-    A.m = mfma_dot<TR>(ke, qA) * c;                   // the 513th key seeds the state (see attn_fwd_kernel): m = its score, l = 1, O = its value row
-    B.m = mfma_dot<TR>(ke, qB) * c;
-    A.l = B.l = 0.5f;                                 // (the two half-wave partial sums are added at the end)
-    outer_seed<TR>(vx0, vx1, 1.f, lane, A.o0, A.o1);
-    outer_seed<TR>(vx0, vx1, 1.f, lane, B.o0, B.o1);
-    vm_wait<2 * (kResTiles - 1)>();                   // this wave's pieces of tile 0 and the last query row
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    FragAddr fa = frag_addr(rsmem, lane);             // one tile below tile 0
-    u32x4 pwA[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}}, pwB[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
-    const uint32_t scr = lds_addr(rsmem) + kResScrOff + wave * 256, qxa = lds_addr(rsmem);
-    float* rec = reinterpret_cast<float*>(rsmem + kResRecOff) + wave * kRowxFloats;
-    // tile 0 (peeled: its first stage has no predecessor)
-    fwd64_stage<TR, 1, 0, 0, 1, false>(fa, qA, qB, A, B, pwA, pwB, c);
-    vm_wait<2 * (kResTiles - 2)>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    fwd64_stage<TR, 1, 1, 1, 0, true>(fa, qA, qB, A, B, pwA, pwB, c);
-    if (wave == 0) rowx_core<TR, 0, 8192, false>(lds_addr(tiles), scr, qxa, c, lane, rec);
-#pragma unroll 1
-    for (int t = 1; t < kResTiles; ++t) {
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) fa.row[s2] += 16384;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) { fa.tr[db][0] += 16384; fa.tr[db][1] += 16384; }
-        fwd64_stage<TR, 1, 0, 0, 1, true>(fa, qA, qB, A, B, pwA, pwB, c);
-        if (t + 1 < kResTiles) {                      // tile t + 1: this wave's pieces have landed -> barrier -> everybody's have
-            ResWait<1>::at(t);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-        fwd64_stage<TR, 1, 1, 1, 0, true>(fa, qA, qB, A, B, pwA, pwB, c);
-        if (t == wave) rowx_core<TR, 0, 8192, false>(lds_addr(tiles) + t * 16384, scr, qxa, c, lane, rec);      // (wave-uniform)
-    }
-    fwd64_flush<TR, 1, 1>(fa, A, B, pwA, pwB);
-    A.l = half_sum(A.l);
-    B.l = half_sum(B.l);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the partial record of the last query row is written
-    __builtin_amdgcn_s_barrier();     // every wave has left the tiles: 4 KiB of them per wave stage the output rows
-    asm volatile("" ::: "memory");
-    E* orow0 = static_cast<E*>(p.o_w) + b * p.osb + (int64_t)q0 * p.osn + h * p.osh;
-    store_rows_staged<TR>(tiles + wave * 4096, orow0, p.osn, 64, A.o0, A.o1, 1.f / A.l, lane);
-    store_rows_staged<TR>(tiles + wave * 4096, orow0 + 32 * p.osn, p.osn, 32, B.o0, B.o1, 1.f / B.l, lane);
-    float* lrow = p.lse + (int64_t)(b * p.H + h) * n;
-    if (hh == 0) {
-        lrow[q0 + r] = A.m * kLn2 + logf(A.l);
-        lrow[q0 + 32 + r] = B.m * kLn2 + logf(B.l);
-    }
-    if (wave == kResTiles - 1) rowx_merge_lds<E>(p, b, h, reinterpret_cast<const float*>(rsmem + kResRecOff), kResTiles, lane);
 }
 
 // ============================================================================================
@@ -1564,7 +1256,7 @@ __global__ __launch_bounds__(256, NPCD_DQ_WAVES) void attn_bwd_dq_kernel(AttnPar
     __shared__ __attribute__((aligned(16))) unsigned char smem[3 * 16384 + 512];       // ring + [dS_E | P_E] of the 128 rows (edge token), 16-bit
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool seeded = NPCD_SEED_TAIL && (p.n & 63) == 1 && p.n > 64;          // the single last key is folded into the initial dQ (see attn_fwd_kernel)
+    const bool seeded = (p.n & 63) == 1 && p.n > 64;          // the single last key is folded into the initial dQ (see attn_fwd_kernel)
     const int n = p.n, nk = seeded ? n - 1 : n, nt = (nk + 63) >> 6, nfull = nk >> 6;
     const bool edge = edge_mode(p.n);          // the last row has no workgroup of its own: its dQ comes from the dK/dV pass
     const int nqt = edge ? n >> 7 : (n + 127) >> 7;
@@ -1584,14 +1276,13 @@ __global__ __launch_bounds__(256, NPCD_DQ_WAVES) void attn_bwd_dq_kernel(AttnPar
 
     // the per-row operands (and the seed rows) first, then the K/V stream; delta and the seeds are computed under its flight
     const int qclamp = min(qrow, n - 1);
-    const bool seed = seeded && !NPCD_DIAG_NO_SEED;
     u32x4 qraw[4], doraw[4], oraw[4], keraw[4] = {}, veraw[4] = {};
     uint32_t kx0 = 0, kx1 = 0;
     row_bcast_issue(qb + (int64_t)qclamp * p.sn, hh, qraw);
     row_bcast_issue(dob + (int64_t)qclamp * p.osn, hh, doraw);
     row_bcast_issue(ob + (int64_t)qclamp * p.osn, hh, oraw);
     float lse_row = gload_f32(p.lse + (int64_t)(b * p.H + h) * n + qclamp);   // rows past the end duplicate the last row; never stored
-    if (seed) {
+    if (seeded) {
         row_bcast_issue(kb + (int64_t)(n - 1) * p.sn, hh, keraw);
         row_bcast_issue(vb + (int64_t)(n - 1) * p.sn, hh, veraw);
         kx0 = gload_u16(kb + (int64_t)(n - 1) * p.sn + r);
@@ -1625,7 +1316,7 @@ __global__ __launch_bounds__(256, NPCD_DQ_WAVES) void attn_bwd_dq_kernel(AttnPar
     }
     const float lse2 = lse_row * kLog2e;
     f32x16 dq0 = {0}, dq1 = {0};
-    if (seed) {       // dQ of the last key: dS = P (dP - delta), dQ = dS k
+    if (seeded) {       // dQ of the last key: dS = P (dP - delta), dQ = dS k
         V8 ke[4], ve[4];
         arrived4(keraw, ke);
         arrived4(veraw, ve);
@@ -1675,7 +1366,7 @@ __global__ __launch_bounds__(256, NPCD_DQ_WAVES) void attn_bwd_dq_kernel(AttnPar
     }
     __builtin_amdgcn_s_barrier();     // every wave has left the ring: 4 KiB of it per wave stage the gradient rows
     f32x16 k0 = {0}, k1 = {0}, v0 = {0}, v1 = {0};
-    if (edge && !NPCD_DIAG_NO_EDGE_REDUCE) {       // partial dK_E (Q rows weighted by dS_E) and dV_E (dO rows weighted by P_E) of this wave's 32 rows
+    if (edge) {       // partial dK_E (Q rows weighted by dS_E) and dV_E (dO rows weighted by P_E) of this wave's 32 rows
         const uint32_t img = 16384 + wave * 8192, wa = lds_addr(smem) + 3 * 16384 + wave * 128;
         edge_put_rows(fa, img, qf);
         edge_put_rows(fa, img + 4096, dof);
@@ -1685,7 +1376,7 @@ __global__ __launch_bounds__(256, NPCD_DQ_WAVES) void attn_bwd_dq_kernel(AttnPar
     }
     E* grow0 = static_cast<E*>(p.dq) + b * p.gsb + (int64_t)q0 * p.gsn + h * p.gsh;
     store_rows_staged<TR>(smem + wave * 4096, grow0, p.gsn, n - q0, dq0, dq1, p.scale, lane, colsum_seg(p, ((int64_t)b * nqt + qt) * 4 + wave, h, 0));
-    if (edge && !NPCD_DIAG_NO_EDGE_REDUCE) {
+    if (edge) {
         float* part = p.delta + 2 * (int64_t)p.B * p.H * (((n + 63) >> 6) << 6) + (((int64_t)bh * nqt + qt) * 4 + wave) * kEdgeFloats;
         unsigned char* scratch = smem + 16384 + wave * 8192;        // the wave's own image, read out by edge_reduce
         edge_stage(scratch, lane, k0, k1);
@@ -1736,22 +1427,7 @@ __device__ __forceinline__ void qdo_prefetch(unsigned char* slot, const QdoStrea
 
 struct DkdvState {
     f32x16 dk0, dk1, dv0, dv1;
-#ifdef NPCD_TIMELINE
-    long long* tl;
-    bool tl_on;
-#endif
 };
-#ifdef NPCD_TIMELINE
-#ifndef NPCD_TL_TILE
-#define NPCD_TL_TILE 3
-#endif
-#define NPCD_TS_STEP(i)                                                                        \
-    do {                                                                                       \
-        if (a.tl_on && t == NPCD_TL_TILE) { __builtin_amdgcn_sched_barrier(0); a.tl[(i)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } \
-    } while (0)
-#else
-#define NPCD_TS_STEP(i) do { } while (0)
-#endif
 
 // One stage of the dK/dV pass = one 32-row query sub-block (SLOT, SUB) of the ring, keys on the lanes:
 //   A  one batch of LDS reads: the sub-block's row constants and Q / dO row fragments, plus (ACC) the transposed
@@ -1875,16 +1551,11 @@ __device__ __forceinline__ bool dkdv_step(unsigned char* smem, const FragAddr& f
                                           const typename TR::vec8 (&vf)[4], float c, DkdvState& a, typename TR::vec8 (&pf)[2],
                                           typename TR::vec8 (&df)[2]) {
     constexpr int PREV = (SLOT + 2) % 3;
-    NPCD_TS_STEP(22);
     dkdv_stage<TR, SLOT, 0, PREV, 1, true>(fa, st_addr, kf, vf, c, a, pf, df);
-    NPCD_TS_STEP(25);
     NPCD_DKDV_MID();                                             // tile t+1 landed; every wave is done with tile t-1
-    NPCD_TS_STEP(26);
     if (t + 2 < nt) qdo_prefetch(smem + PREV * kDkdvSlot, qs, t + 2, n, wave, lane);
-    NPCD_TS_STEP(27);
     if (t * 64 + 32 >= n) return false;
     dkdv_stage<TR, SLOT, 1, SLOT, 0, true>(fa, st_addr, kf, vf, c, a, pf, df);
-    NPCD_TS_STEP(30);
     return true;
 }
 
@@ -1901,7 +1572,7 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
     // A sequence of 64 j + 1 tokens: the single last QUERY row never enters the ring, its dK / dV contributions are the
     // initial accumulators (from direct loads and a few matrix instructions while the first tiles are in flight; cf. attn_fwd_kernel),
     // and the stream below covers nq = n - 1 query rows in full tiles.
-    const bool seeded = NPCD_SEED_TAIL && (p.n & 63) == 1 && p.n > 64;          // kernel-uniform
+    const bool seeded = (p.n & 63) == 1 && p.n > 64;          // kernel-uniform
     const int n = p.n, nq = seeded ? n - 1 : n, nt = (nq + 63) >> 6;
     const bool edge = edge_mode(p.n);          // the last key has no workgroup of its own: its dK / dV come from the dQ pass
     const int nkt = edge ? n >> 7 : (n + 127) >> 7;
@@ -1916,12 +1587,6 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
     const int key = key0 + r;
     const bool key_ok = key < n;
 
-#ifdef NPCD_TIMELINE
-    const bool tl_on = (blockIdx.x == NPCD_TIMELINE) && wave == 0;
-    long long tl[40];
-    for (int i = 0; i < 40; ++i) tl[i] = 0;
-#endif
-    NPCD_TS(0);
     QdoStream<E> qs;
     {
         const bool second = wave >= 2;
@@ -1951,14 +1616,13 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
 
     // this lane's K / V row (and the seed rows) first, then the Q / dO stream (5 wave-instructions per tile and wave): the
     // seeds are computed under its flight (see gload16)
-    const bool seed = seeded && !NPCD_DIAG_NO_SEED;
     const int kclamp = min(key, n - 1);
     u32x4 kraw[4], vraw[4], qeraw[4] = {}, doeraw[4] = {}, oeraw[4] = {};
     uint32_t qx0 = 0, qx1 = 0, dx0 = 0, dx1 = 0;
     float lse_e = 0.f;
     row_bcast_issue(kb + (int64_t)kclamp * p.sn, hh, kraw);
     row_bcast_issue(vb + (int64_t)kclamp * p.sn, hh, vraw);
-    if (seed) {
+    if (seeded) {
         const E* qrow = qb + (int64_t)(n - 1) * p.sn;
         const E* dorow = dob + (int64_t)(n - 1) * p.osn;
         row_bcast_issue(qrow, hh, qeraw);
@@ -1986,7 +1650,7 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
     DkdvState a;
     a.dk0 = f32x16{0}; a.dk1 = f32x16{0}; a.dv0 = f32x16{0}; a.dv1 = f32x16{0};
     float ds_edge = 0.f;
-    if (seed) {       // the last query row against this lane's key: P = exp2(c (k.q - lse/scale)), dS = P (v.dO - delta)
+    if (seeded) {       // the last query row against this lane's key: P = exp2(c (k.q - lse/scale)), dS = P (v.dO - delta)
         V8 qe[4], doe[4], oe[4];
         arrived4(qeraw, qe);
         arrived4(doeraw, doe);
@@ -2010,12 +1674,9 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
     const float c = p.scale_log2;
     const FragAddr fa = frag_addr(dsmem, lane);
     const uint32_t st_addr = lds_addr(dsmem) + hh * 16;
-    NPCD_TS(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // tiles 0 / 1 have arrived
-    NPCD_TS(2);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    NPCD_TS(3);
     // tile 0 (slot 0) is peeled: its first stage has no predecessor to accumulate
     bool both = true;      // the last tile ended with its second sub-block
     {
@@ -2032,7 +1693,6 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
         if (t + 1 < nt) both = dkdv_step<TR, 2>(dsmem, fa, st_addr, qs, t + 1, nt, nq, wave, lane, kf, vf, c, a, pf, df);
         if (t + 2 < nt) both = dkdv_step<TR, 0>(dsmem, fa, st_addr, qs, t + 2, nt, nq, wave, lane, kf, vf, c, a, pf, df);
     }
-    NPCD_TS(20);
     {
         const int last = (nt - 1) % 3;
         if (both) {
@@ -2046,7 +1706,7 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
         }
     }
     f32x16 eq0 = {0}, eq1 = {0};
-    if (edge && !NPCD_DIAG_NO_EDGE_REDUCE) {   // partial dQ_E of this wave's 32 keys (K rows weighted by dS_E), in the slot before the last
+    if (edge) {   // partial dQ_E of this wave's 32 keys (K rows weighted by dS_E), in the slot before the last
         // tile's -- released, like the staging slot below, at the last mid-tile barrier
         const uint32_t img = ((nt + 1) % 3) * kDkdvSlot + wave * 4096, wa = lds_addr(dsmem) + ((nt + 1) % 3) * kDkdvSlot + 16384 + wave * 64;
         edge_put_rows(fa, img, kf);
@@ -2061,18 +1721,12 @@ __global__ __launch_bounds__(256, NPCD_DKDV_WAVES) void attn_bwd_dkdv_kernel(Att
         store_rows_staged<TR>(stage, gk, p.gsn, n - key0, a.dk0, a.dk1, p.scale, lane, colsum_seg(p, ((int64_t)b * nkt + kt) * 4 + wave, h, 1));
         store_rows_staged<TR>(stage, gv, p.gsn, n - key0, a.dv0, a.dv1, 1.f, lane, colsum_seg(p, ((int64_t)b * nkt + kt) * 4 + wave, h, 2));
     }
-    if (edge && !NPCD_DIAG_NO_EDGE_REDUCE) {
+    if (edge) {
         float* part = p.delta + 2 * (int64_t)p.B * p.H * (((n + 63) >> 6) << 6) + (((int64_t)bh * nkt + kt) * 4 + wave) * kEdgeFloats;
         unsigned char* scratch = dsmem + ((nt + 1) % 3) * kDkdvSlot + wave * 4096;      // the wave's own image, read out by edge_reduce
         edge_stage(scratch, lane, eq0, eq1);
         part[128 + lane] = reinterpret_cast<const float*>(scratch)[lane];
     }
-#ifdef NPCD_TIMELINE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    NPCD_TS(21);
-    if (tl_on && lane == 0)
-        for (int i = 0; i < 40; ++i) g_timeline[i] = tl[i];
-#endif
 }
 
 // ============================================================================================
@@ -2202,18 +1856,12 @@ __device__ __forceinline__ void fused_stage(const FragAddr& fa, uint32_t st_addr
     using V8 = typename TR::vec8;
     constexpr int QT = SLOT * kDkdvSlot + SUB * 4096, DT = QT + 8192, ST = SLOT * kDkdvSlot + 16384 + SUB * 128;
     constexpr int PQ = PSLOT * kDkdvSlot, PD = PQ + 8192;
-#if !defined(NPCD_FUSED_ABL) || NPCD_FUSED_ABL < 1
     if (ACC) fused_dq<TR, PAR ^ 1>(fc, prev_q0, slab_val, lane);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     // the Q / dO tile two ahead is requested only now: the running dQ sums above are ordinary loads, and an ordinary load's
     // wait (vmcnt(0), the compiler cannot count past hand-issued LDS-DMA) must not fall behind a freshly issued DMA
     prefetch();
-#if !defined(NPCD_FUSED_ABL) || NPCD_FUSED_ABL < 1
     if (!fc.first_pass) {                                        // this sub-block's running sum, consumed by the next stage
-#else
-    if (false) {
-#endif
         const float* sp = fused_slab_ptr(fc, cur_q0, lane);
         slab_val = sp ? *reinterpret_cast<const f32x4v*>(sp) : f32x4v{0.f, 0.f, 0.f, 0.f};
     }
@@ -2291,11 +1939,7 @@ __device__ __forceinline__ void fused_stage(const FragAddr& fa, uint32_t st_addr
     // publish dS^T of this sub-block: lane = key, registers 4g..4g+3 = four consecutive query rows 8g + 4hh .. -> 8 bytes at
     // [key][q = 8g + 4hh], 8-byte chunk index XOR (key & 7); keys past the end of the sequence publish zeros (their P is not
     // zero -- harmless for dK / dV, whose rows are never stored, but it would leak into every query's dQ)
-#if !defined(NPCD_FUSED_ABL) || NPCD_FUSED_ABL < 2
     {
-#else
-    if (false) {
-#endif
         const uint32_t base = fc.stg + PAR * kFStage + fc.wave * 2048 + fc.wr_off;
         const int key = lane & 31, hh = lane >> 5;
 #pragma unroll
@@ -2438,11 +2082,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnParams p, fl
         }
         auto step = [&](auto slot_c, int t) {
             constexpr int SLOT = decltype(slot_c)::value, PREV = (SLOT + 2) % 3;
-#if !defined(NPCD_FUSED_ABL) || NPCD_FUSED_ABL < 3
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                         // dS^T of the previous tile's second sub-block published
             asm volatile("" ::: "memory");
-#endif
             NPCD_F_STAGE(SLOT, 0, PREV, 1, true, 0, (t - 1) * 64 + 32, t * 64, nopf);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             NPCD_DMA_WAIT_BARRIER(0);                             // tile t+1 landed; every wave done with tile t-1; dS^T published
@@ -3048,27 +2690,56 @@ static int check_common(int B, int n, int H, int d, int dtype) {
     if (dtype != NPCD_BF16 && dtype != NPCD_F16) return NPCD_ERR_UNSUPPORTED;
     return NPCD_OK;
 }
-static bool strides_ok(int64_t sb, int64_t sn, int64_t sh) { return (sb % 8 == 0) && (sn % 8 == 0) && (sh % 8 == 0); }
+// The layout checks of the 16-bit entry points: every `required` pointer given, every `aligned` one on 16 bytes (an optional pointer
+// that is null passes), every stride a multiple of 8 elements (16-byte rows: LDS-DMA pieces and 16-byte loads).
+static int check_layout(std::initializer_list<const void*> required, std::initializer_list<const void*> aligned,
+                        std::initializer_list<int64_t> strides) {
+    for (const void* x : required)
+        if (!x) return NPCD_ERR_ARG;
+    for (const void* x : aligned)
+        if (!aligned16(x)) return NPCD_ERR_ARG;
+    for (int64_t x : strides)
+        if (x % 8 != 0) return NPCD_ERR_ARG;
+    return NPCD_OK;
+}
+// what the forward and the backward share; the forward adds o_w (and rowx), the backward attn_bwd_params
+static AttnParams attn_params(const void* q, const void* k, const void* v, const float* lse, int B, int n, int H, int64_t qkv_sb, int64_t qkv_sn,
+                              int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh, float scale) {
+    AttnParams p{};
+    p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse);
+    p.B = B; p.n = n; p.H = H;
+    p.sb = qkv_sb; p.sn = qkv_sn; p.sh = qkv_sh;
+    p.osb = out_sb; p.osn = out_sn; p.osh = out_sh;
+    p.scale = scale; p.scale_log2 = scale * kLog2e;
+    return p;
+}
+static void attn_bwd_params(AttnParams& p, const void* out, const void* dout, void* dq, void* dk, void* dv, float* delta, int64_t g_sb,
+                            int64_t g_sn, int64_t g_sh) {
+    p.out = out; p.dout = dout; p.delta = delta;
+    p.dq = dq; p.dk = dk; p.dv = dv;
+    p.gsb = g_sb; p.gsn = g_sn; p.gsh = g_sh;
+}
+// f(BF16{}) or f(F16{}): the element traits of `dtype` (check_common admits no other)
+template <class F>
+static void for_dtype(int dtype, F&& f) {
+    if (dtype == NPCD_BF16) f(BF16{});
+    else f(F16{});
+}
 
 }  // namespace npcd
 
 using namespace npcd;
 
-#ifdef NPCD_TIMELINE
-extern "C" int npcd_debug_read(long long* out, int count) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(npcd::g_timeline), sizeof(long long) * count);
-}
-#endif
-
-// which form of the forward a sequence length takes (NPCD_ATTN_FWD=32 / 64 forces one; see attn_fwd_launch)
+// which form of the forward a sequence length takes (NPCD_ATTN_FWD=32 / 64 forces one, read at every call; see attn_fwd_launch)
 static bool fwd_rows32(int n) {
     const char* form = getenv("NPCD_ATTN_FWD");
-    return (form && form[0] != 'r') ? form[0] == '3' : n < 1024;
+    if (form && (form[0] == '3' || form[0] == '6')) return form[0] == '3';
+    return n < 1024;
 }
+// scratch of the 64-row form's row split (rowx_tile): one record per (batch, head, 64-key tile)
 extern "C" int64_t npcd_attn_fwd_workspace_floats(int B, int n, int H) {
     if (B <= 0 || n <= 0 || H <= 0) return -1;
-    static const bool rowx32 = getenv("NPCD_ATTN_ROWX32") != nullptr;     // (opt-in: the 32-row form without its fifth workgroup; slower, see attn_fwd_kernel)
-    return (rowx_mode(n) && (rowx32 || !fwd_rows32(n))) ? (int64_t)B * H * ((n - 1) / 64) * kRowxFloats : 0;
+    return (rowx_mode(n) && !fwd_rows32(n)) ? (int64_t)B * H * ((n - 1) / 64) * kRowxFloats : 0;
 }
 
 static int attn_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, float* workspace, int B, int n, int H, int d,
@@ -3105,63 +2776,23 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* ou
     const bool gen = d != 64 || force_gen;
     int rc = check_common(B, n, H, gen && attn_gen_supported(d) ? 64 : d, dtype);
     if (rc != NPCD_OK) return rc;
-    if (!q || !k || !v || !out || !lse) return NPCD_ERR_ARG;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) return NPCD_ERR_ARG;
-    if (!strides_ok(qkv_sb, qkv_sn, qkv_sh) || !strides_ok(out_sb, out_sn, out_sh)) return NPCD_ERR_ARG;
+    rc = check_layout({q, k, v, out, lse}, {q, k, v, out}, {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh});
+    if (rc != NPCD_OK) return rc;
     if (gen) return attn_gen_fwd(q, k, v, out, lse, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale, dtype, stream);
-    AttnParams p{};
-    p.q = q; p.k = k; p.v = v; p.o_w = out; p.lse = lse;
-    p.B = B; p.n = n; p.H = H;
-    p.sb = qkv_sb; p.sn = qkv_sn; p.sh = qkv_sh;
-    p.osb = out_sb; p.osn = out_sn; p.osh = out_sh;
-    p.scale = scale; p.scale_log2 = scale * kLog2e;
+    AttnParams p = attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
+    p.o_w = out;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // Two forms of the forward (measured in one process, tools/probes/gpu_dev_fwd_ab.py): 64 query rows per wave wins
     // on long sequences (n = 2049: 597-614 against 640-653 us), 32 rows per wave on short ones, where a workgroup's start-up and
     // wind-down dominate and its finer grid fills the chip better (n = 513: 113 against 117 us).  NPCD_ATTN_FWD=32 / 64 forces one.
-    // n = 513 (the denoiser's sequence), OPT-IN NPCD_ATTN_FWD=res: K / V of a (batch, head) resident in LDS, one workgroup per
-    // (batch, head) -- attn_fwd_res_kernel.  Built in round 5 as the "different body" for this shape; parity green, and SLOWER in the
-    // step: 141 against 120 us (same box, alternating bench runs): with one workgroup per CU nothing computes while a workgroup's
-    // 200 KB arrive, the four rounds of workgroups load and compute in phase, and the eight waves of a workgroup run in lockstep
-    // behind the per-tile barrier (docs/experiments.md R5.2).
-    const char* fwd_form = getenv("NPCD_ATTN_FWD");
-    if (fwd_res_shape(n) && fwd_form && fwd_form[0] == 'r') {
-        static DynLds lds_bf, lds_f;
-        if (dtype == NPCD_BF16) {
-            NPCD_HIP_CHECK(lds_bf.ensure(reinterpret_cast<const void*>(attn_fwd_res_kernel<BF16>), kResLds));
-            hipLaunchKernelGGL(attn_fwd_res_kernel<BF16>, dim3(B * H), dim3(512), kResLds, st, p);
-        } else {
-            NPCD_HIP_CHECK(lds_f.ensure(reinterpret_cast<const void*>(attn_fwd_res_kernel<F16>), kResLds));
-            hipLaunchKernelGGL(attn_fwd_res_kernel<F16>, dim3(B * H), dim3(512), kResLds, st, p);
-        }
-        NPCD_HIP_CHECK(hipGetLastError());
-        return NPCD_OK;
-    }
-    if (fwd_rows32(n)) {
-        static const bool rowx32 = getenv("NPCD_ATTN_ROWX32") != nullptr;
-        p.rowx = (workspace && rowx32 && rowx_mode(n)) ? workspace : nullptr;
-        const int grid = B * H * (p.rowx ? (n - 1) / 128 : ceil_div(n, 128));
-        if (p.rowx) {
-            if (dtype == NPCD_BF16) hipLaunchKernelGGL((attn_fwd_kernel<BF16, true>), dim3(grid), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((attn_fwd_kernel<F16, true>), dim3(grid), dim3(256), 0, st, p);
-        } else {
-            if (dtype == NPCD_BF16) hipLaunchKernelGGL((attn_fwd_kernel<BF16, false>), dim3(grid), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((attn_fwd_kernel<F16, false>), dim3(grid), dim3(256), 0, st, p);
-        }
-        if (p.rowx) {
-            if (dtype == NPCD_BF16) hipLaunchKernelGGL(attn_fwd_rowx_merge_kernel<__bf16>, dim3(B * H), dim3(64), 0, st, p, (n - 1) / 64);
-            else hipLaunchKernelGGL(attn_fwd_rowx_merge_kernel<_Float16>, dim3(B * H), dim3(64), 0, st, p, (n - 1) / 64);
-        }
-    } else {
-        p.rowx = (workspace && rowx_mode(n)) ? workspace : nullptr;
-        const int grid = B * H * (p.rowx ? (n - 1) / 256 : ceil_div(n, 256));
-        if (dtype == NPCD_BF16) hipLaunchKernelGGL(attn_fwd64_kernel<BF16>, dim3(grid), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(attn_fwd64_kernel<F16>, dim3(grid), dim3(256), 0, st, p);
-        if (p.rowx) {
-            if (dtype == NPCD_BF16) hipLaunchKernelGGL(attn_fwd_rowx_merge_kernel<__bf16>, dim3(B * H), dim3(64), 0, st, p, (n - 1) / 64);
-            else hipLaunchKernelGGL(attn_fwd_rowx_merge_kernel<_Float16>, dim3(B * H), dim3(64), 0, st, p, (n - 1) / 64);
-        }
-    }
+    const bool rows32 = fwd_rows32(n);
+    p.rowx = (workspace && !rows32 && rowx_mode(n)) ? workspace : nullptr;
+    for_dtype(dtype, [&](auto tr) {
+        using TR = decltype(tr);
+        if (rows32) hipLaunchKernelGGL(attn_fwd_kernel<TR>, dim3(B * H * ceil_div(n, 128)), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(attn_fwd64_kernel<TR>, dim3(B * H * (p.rowx ? (n - 1) / 256 : ceil_div(n, 256))), dim3(256), 0, st, p);
+        if (p.rowx) hipLaunchKernelGGL(attn_fwd_rowx_merge_kernel<typename TR::elem>, dim3(B * H), dim3(64), 0, st, p, (n - 1) / 64);
+    });
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
@@ -3193,15 +2824,10 @@ extern "C" int npcd_attn_fwd_fp8(const void* q, const void* k, const void* v, vo
     if (dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
     const int nk = fp8_nk(n);
     if (nk % 64 != 0) return NPCD_ERR_UNSUPPORTED;
-    if (!q || !k || !v || !out || !lse || !workspace) return NPCD_ERR_ARG;
-    if (!npcd::aligned16(q) || !npcd::aligned16(k) || !npcd::aligned16(v) || !npcd::aligned16(out) || !npcd::aligned16(workspace)) return NPCD_ERR_ARG;
-    if (!npcd::strides_ok(qkv_sb, qkv_sn, qkv_sh) || !npcd::strides_ok(out_sb, out_sn, out_sh)) return NPCD_ERR_ARG;
-    npcd::AttnParams p{};
-    p.q = q; p.k = k; p.v = v; p.o_w = out; p.lse = lse;
-    p.B = B; p.n = n; p.H = H;
-    p.sb = qkv_sb; p.sn = qkv_sn; p.sh = qkv_sh;
-    p.osb = out_sb; p.osn = out_sn; p.osh = out_sh;
-    p.scale = scale; p.scale_log2 = scale * npcd::kLog2e;
+    rc = npcd::check_layout({q, k, v, out, lse, workspace}, {q, k, v, out, workspace}, {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh});
+    if (rc != NPCD_OK) return rc;
+    npcd::AttnParams p = npcd::attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
+    p.o_w = out;
     unsigned char* k8 = static_cast<unsigned char*>(workspace);
     unsigned char* v8t = k8 + (int64_t)B * H * nk * 64;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -3295,26 +2921,18 @@ static int attn_bwd_launch(int passes, const void* q, const void* k, const void*
     const bool gen = d != 64 || (force_gen && !colsum);
     int rc = check_common(B, n, H, gen && attn_gen_supported(d) ? 64 : d, dtype);
     if (rc != NPCD_OK) return rc;
-    if (!q || !k || !v || !out || !dout || !lse || !delta) return NPCD_ERR_ARG;
+    rc = check_layout({q, k, v, out, dout, lse, delta}, {q, k, v, out, dout, dq, dk, dv},
+                      {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, g_sb, g_sn, g_sh});
+    if (rc != NPCD_OK) return rc;
     if ((passes & 1) && !dq) return NPCD_ERR_ARG;
     if ((passes & 2) && (!dk || !dv)) return NPCD_ERR_ARG;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) ||
-        !aligned16(dk) || !aligned16(dv))
-        return NPCD_ERR_ARG;
-    if (!strides_ok(qkv_sb, qkv_sn, qkv_sh) || !strides_ok(out_sb, out_sn, out_sh) || !strides_ok(g_sb, g_sn, g_sh)) return NPCD_ERR_ARG;
     if (gen) {
         if (colsum) return NPCD_ERR_UNSUPPORTED;        // the column-sum by-product belongs to the d = 64 kernels (the fused backbone)
         return attn_gen_bwd(passes, q, k, v, out, dout, lse, dq, dk, dv, delta, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh,
                             g_sb, g_sn, g_sh, scale, dtype, stream);
     }
-    AttnParams p{};
-    p.q = q; p.k = k; p.v = v; p.out = out; p.dout = dout; p.lse = const_cast<float*>(lse); p.delta = delta;
-    p.dq = dq; p.dk = dk; p.dv = dv;
-    p.B = B; p.n = n; p.H = H;
-    p.sb = qkv_sb; p.sn = qkv_sn; p.sh = qkv_sh;
-    p.osb = out_sb; p.osn = out_sn; p.osh = out_sh;
-    p.gsb = g_sb; p.gsn = g_sn; p.gsh = g_sh;
-    p.scale = scale; p.scale_log2 = scale * kLog2e;
+    AttnParams p = attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
+    attn_bwd_params(p, out, dout, dq, dk, dv, delta, g_sb, g_sn, g_sh);
     if (colsum) {       // only for the packed c_qkv gradient: [.., H, (dq | dk | dv) x 64]
         const size_t es = 2;
         if (g_sh != 192 || (dk && reinterpret_cast<const char*>(dk) != reinterpret_cast<const char*>(dq) + 64 * es) ||
@@ -3329,15 +2947,12 @@ static int attn_bwd_launch(int passes, const void* q, const void* k, const void*
     static DynLds lds_bf16, lds_f16;
     NPCD_HIP_CHECK(lds_bf16.ensure(reinterpret_cast<const void*>(attn_bwd_dkdv_kernel<BF16>), dyn));
     NPCD_HIP_CHECK(lds_f16.ensure(reinterpret_cast<const void*>(attn_bwd_dkdv_kernel<F16>), dyn));
-    if (dtype == NPCD_BF16) {
-        if (passes & 1) hipLaunchKernelGGL(attn_bwd_dq_kernel<BF16>, dim3(grid), dim3(256), 0, st, p);
-        if (passes & 2) hipLaunchKernelGGL(attn_bwd_dkdv_kernel<BF16>, dim3(grid), dim3(256), dyn, st, p);
-        if ((passes & 2) && edge) hipLaunchKernelGGL(attn_bwd_edge_kernel<BF16::elem>, dim3(B * H), dim3(192), 0, st, p);
-    } else {
-        if (passes & 1) hipLaunchKernelGGL(attn_bwd_dq_kernel<F16>, dim3(grid), dim3(256), 0, st, p);
-        if (passes & 2) hipLaunchKernelGGL(attn_bwd_dkdv_kernel<F16>, dim3(grid), dim3(256), dyn, st, p);
-        if ((passes & 2) && edge) hipLaunchKernelGGL(attn_bwd_edge_kernel<F16::elem>, dim3(B * H), dim3(192), 0, st, p);
-    }
+    for_dtype(dtype, [&](auto tr) {
+        using TR = decltype(tr);
+        if (passes & 1) hipLaunchKernelGGL(attn_bwd_dq_kernel<TR>, dim3(grid), dim3(256), 0, st, p);
+        if (passes & 2) hipLaunchKernelGGL(attn_bwd_dkdv_kernel<TR>, dim3(grid), dim3(256), dyn, st, p);
+        if ((passes & 2) && edge) hipLaunchKernelGGL(attn_bwd_edge_kernel<typename TR::elem>, dim3(B * H), dim3(192), 0, st, p);
+    });
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
@@ -3355,26 +2970,17 @@ extern "C" int npcd_attn_bwd_fused(const void* q, const void* k, const void* v, 
                                    int64_t g_sb, int64_t g_sn, int64_t g_sh, float scale, int dtype, void* stream) {
     int rc = check_common(B, n, H, d, dtype);
     if (rc != NPCD_OK) return rc;
-    if (!q || !k || !v || !out || !dout || !lse || !delta || !dq || !dk || !dv) return NPCD_ERR_ARG;
+    rc = check_layout({q, k, v, out, dout, lse, delta, dq, dk, dv}, {q, k, v, out, dout, dq, dk, dv, dq_slab},
+                      {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, g_sb, g_sn, g_sh});
+    if (rc != NPCD_OK) return rc;
     if (n > 256 && !dq_slab) return NPCD_ERR_ARG;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) ||
-        !aligned16(dv) || (dq_slab && !aligned16(dq_slab)))
-        return NPCD_ERR_ARG;
-    if (!strides_ok(qkv_sb, qkv_sn, qkv_sh) || !strides_ok(out_sb, out_sn, out_sh) || !strides_ok(g_sb, g_sn, g_sh)) return NPCD_ERR_ARG;
-    AttnParams p{};
-    p.q = q; p.k = k; p.v = v; p.out = out; p.dout = dout; p.lse = const_cast<float*>(lse); p.delta = delta;
-    p.dq = dq; p.dk = dk; p.dv = dv;
-    p.B = B; p.n = n; p.H = H;
-    p.sb = qkv_sb; p.sn = qkv_sn; p.sh = qkv_sh;
-    p.osb = out_sb; p.osn = out_sn; p.osh = out_sh;
-    p.gsb = g_sb; p.gsn = g_sn; p.gsh = g_sh;
-    p.scale = scale; p.scale_log2 = scale * kLog2e;
+    AttnParams p = attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
+    attn_bwd_params(p, out, dout, dq, dk, dv, delta, g_sb, g_sn, g_sh);
     hipStream_t st = static_cast<hipStream_t>(stream);
     static DynLds lds_bf16, lds_f16;
     NPCD_HIP_CHECK(lds_bf16.ensure(reinterpret_cast<const void*>(attn_bwd_fused_kernel<BF16>), kFLds));
     NPCD_HIP_CHECK(lds_f16.ensure(reinterpret_cast<const void*>(attn_bwd_fused_kernel<F16>), kFLds));
-    if (dtype == NPCD_BF16) hipLaunchKernelGGL(attn_bwd_fused_kernel<BF16>, dim3(B * H), dim3(512), kFLds, st, p, dq_slab);
-    else hipLaunchKernelGGL(attn_bwd_fused_kernel<F16>, dim3(B * H), dim3(512), kFLds, st, p, dq_slab);
+    for_dtype(dtype, [&](auto tr) { hipLaunchKernelGGL(attn_bwd_fused_kernel<decltype(tr)>, dim3(B * H), dim3(512), kFLds, st, p, dq_slab); });
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }

@@ -552,19 +552,6 @@ def test_single_pass_backward_matches_oracle_and_two_pass(n, monkeypatch):
     check(qkv, H, gout, f"fused n={n}")
 
 
-def test_opt_in_forward_without_the_fifth_workgroup_still_matches():
-    """NPCD_ATTN_ROWX32=1 (round 4, opt-in because it measured slower): the 32-row forward of 256 j + 1-token sequences without a workgroup
-    for the single last query row -- eight waves of the (batch, head) split that row's keys, a merge kernel combines them.  The switch
-    is read once per process, so the golden + ragged-length tests run again in a child process with it set."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, NPCD_ATTN_ROWX32="1")
-    out = subprocess.run([sys.executable, "-m", "pytest", __file__, "-q", "-x", "-k", "golden or ragged"], capture_output=True, text=True,
-                         env=env, timeout=900)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-1000:]
-
-
 def test_fp32_class_sampler_forward_matches_the_fp32_path():
     """DiffusionModel.generate(dtype="fp32_class") (round 5): the reference samples in fp32 (diffusion_model.py:108-133); here the backbone's
     Linear layers run as ONE bf16 library GEMM each over the three cross products of split operands (csrc/split.hip + fused.backbone_forward_x2),
@@ -639,17 +626,3 @@ def test_fp32_class_sampler_forward_matches_the_fp32_path():
             assert float((torch.stack(a_c) - torch.stack(b_c)).abs().max()) < 1e-3 and float((torch.stack(a_f) - torch.stack(b_f)).abs().max()) < 1e-3
             with pytest.raises(ValueError):
                 model.generate(1, batch_size=1, progress=False, dtype="fp64")
-
-
-def test_opt_in_resident_forward_still_matches():
-    """NPCD_ATTN_FWD=res (round 5, opt-in because it measured slower: 141 against 120 us in the step): the forward of 513-token sequences
-    with K / V of a (batch, head) resident in LDS -- one workgroup of eight waves per (batch, head), the 513th query row split over the
-    waves and merged through LDS.  The golden, ragged-length (513 is among them), forced-rescale and reproducibility tests run again
-    in a child process with the switch set; other lengths fall through to the ring kernels."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, NPCD_ATTN_FWD="res")
-    out = subprocess.run([sys.executable, "-m", "pytest", __file__, "-q", "-x", "-k", "golden or ragged or rescale or reproduc or edge_token"],
-                         capture_output=True, text=True, env=env, timeout=900)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-1000:]

@@ -42,6 +42,24 @@ def test_attention_backward_workspace_size():
     assert g(2, 513, 3) == 2 * 3 * 64 * 2 * 512 and g(2, 512, 3) == 2 * 3 * 64 * 2 * 512 and g(2, 100, 3) == 0 and g(2, 1, 3) == 0
 
 
+def test_attention_forward_workspace_size(monkeypatch):
+    """Host-side sizing of the forward's scratch (include/npcd_hip.h): 68 floats per (batch, head, 64-key tile), non-zero exactly when
+    the sequence is 256 j + 1 > 256 tokens long AND the 64-row form takes it (n >= 1024, or NPCD_ATTN_FWD=64, read at every call)."""
+    from npcd import hip
+    f = hip.lib().npcd_attn_fwd_workspace_floats
+    B, H = 2, 3
+    monkeypatch.delenv("NPCD_ATTN_FWD", raising=False)
+    for n in (256, 257, 513, 769, 1024):
+        assert f(B, n, H) == 0, n
+    for n in (1025, 2049):
+        assert f(B, n, H) == B * H * ((n - 1) // 64) * 68, n
+    assert f(0, 1025, H) == -1
+    monkeypatch.setenv("NPCD_ATTN_FWD", "64")
+    assert f(B, 513, H) == B * H * 8 * 68
+    monkeypatch.setenv("NPCD_ATTN_FWD", "32")
+    assert f(B, 2049, H) == 0
+
+
 def test_no_cpu_fallback():
     from npcd.hip.attention import attention_qkvpacked, flash_attn_func
     with pytest.raises(RuntimeError, match="GPU"):

@@ -1,9 +1,11 @@
-"""Register and scratch budget of the kernels of csrc/geometry.hip, read from the compiler's own output (no GPU needed).
+"""Register and scratch budget of the kernels of csrc/geometry.hip and csrc/attention.hip, read from the compiler's own output (no GPU
+needed).
 
 Round 6 folded two opt-in experiments into grid_query_wave_kernel as run-time branches; its default form went from 46 to 100
 VGPRs (8 -> 4 waves per SIMD) and nobody saw it, because every A/B compared the switch on with the switch off on the same binary.
 This compiles the file to assembly with the flags of csrc/build.py and checks the kernel descriptors, so that it cannot recur
-silently."""
+silently.  The attention kernels sit close to occupancy boundaries of their own (168 registers: three waves per SIMD, 256: two);
+their budgets are those boundaries."""
 import importlib.util
 import os
 import re
@@ -23,16 +25,20 @@ def _build_py():
     return mod
 
 
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    """{mangled kernel name: {"vgpr": .amdhsa_next_free_vgpr, "scratch": .amdhsa_private_segment_fixed_size, "lds": static bytes}}
-    of geometry.hip: one hipcc run for the module."""
+def _kernels_of(source):
+    """Module-scoped fixture: {mangled kernel name: {"vgpr": .amdhsa_next_free_vgpr, "scratch": .amdhsa_private_segment_fixed_size,
+    "lds": static bytes}} of one source of csrc/ -- one hipcc run per source for the module."""
+    @pytest.fixture(scope="module")
+    def fixture(tmp_path_factory):
+        return _compile(source, str(tmp_path_factory.mktemp("kernel_resources") / source.replace(".hip", ".s")))
+    return fixture
+
+
+def _compile(source, out):
     build = _build_py()
     if not os.path.exists(build.HIPCC):
         pytest.skip(f"hipcc not found at {build.HIPCC}")
-    out = str(tmp_path_factory.mktemp("kernel_resources") / "geometry.s")
-    cmd = [build.HIPCC, *build.COMMON, *build.SOURCES["geometry.hip"], "-S", "--cuda-device-only",
-           os.path.join(CSRC, "geometry.hip"), "-o", out]
+    cmd = [build.HIPCC, *build.COMMON, *build.SOURCES[source], "-S", "--cuda-device-only", os.path.join(CSRC, source), "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, f"hipcc failed:\n{r.stderr}"
     found = {}
@@ -54,6 +60,10 @@ def kernels(tmp_path_factory):
         assert set(v) == set(keys.values()), (k, v)
         print(f"{k}: {v}")
     return found
+
+
+kernels = _kernels_of("geometry.hip")
+attention = _kernels_of("attention.hip")
 
 
 def _form(kernels, name, *flags):
@@ -88,3 +98,39 @@ def test_fused_forms_exist(kernels):
     """The opt-in forms are separate instantiations (scratch is checked above; their register counts are not a bar)."""
     _form(kernels, "grid_query_wave_kernel", True, True)
     _form(kernels, "ray_march_wave_kernel", True, True)
+
+
+def _instances(kernels, name):
+    """Every instantiation of the kernel template `name`."""
+    return {k: v for k, v in kernels.items() if f"{len(name)}{name}I" in k}
+
+
+@pytest.mark.parametrize("name,budget", [("attn_fwd_kernel", 168), ("attn_bwd_dq_kernel", 168), ("attn_fwd64_kernel", 256),
+                                         ("attn_bwd_dkdv_kernel", 256)])
+def test_attention_kernels_keep_their_waves_per_simd(attention, name, budget):
+    """A SIMD has 512 registers per lane, allocated in granules of 8: up to 168 allow three waves, up to 256 two.  The 32-row forward
+    and the dQ pass run at three (128 against 148 us at two for the forward), the 64-row forward and the dK/dV pass
+    are built for two."""
+    hit = _instances(attention, name)
+    assert len(hit) == 2, (name, sorted(hit))          # bf16 and f16
+    for k, v in hit.items():
+        assert v["vgpr"] <= budget, (k, v)
+
+
+def test_attention_scratch(attention):
+    """No kernel of the file spills -- except attn_bwd_fused_kernel, the OPT-IN single-pass backward (the training path runs the
+    two-pass kernels): it spills 140 bytes per lane and must not get worse."""
+    assert len(attention) >= 22, sorted(attention)
+    fused = _instances(attention, "attn_bwd_fused_kernel")
+    assert len(fused) == 2, sorted(fused)
+    for k, v in fused.items():
+        assert v["scratch"] <= 140, (k, v)
+    spilling = {k: v["scratch"] for k, v in attention.items() if v["scratch"] != 0 and k not in fused}
+    assert not spilling, spilling
+
+
+def test_attention_forward_has_no_shelved_forms(attention):
+    """The 32-row forward exists once per element type (no row-split instantiation beside it), and the forward with K / V resident
+    in LDS is gone (docs/experiments.md R11.1 has both as patches)."""
+    assert len(_instances(attention, "attn_fwd_kernel")) == 2, sorted(attention)
+    assert not [k for k in attention if "attn_fwd_res" in k], sorted(attention)

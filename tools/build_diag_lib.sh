@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev tool: build a DIAGNOSTIC variant of libnpcd_hip.so with extra -D flags into neural-point-cloud-diffusion_amd/lib/diag/libnpcd_hip_<tag>.so (git-ignored, travels with gpurun)
-# usage: tools/build_diag_lib.sh <tag> -DNPCD_DIAG_HALF_MFMA ...      (load it with NPCD_HIP_LIB=<path>)
+# usage: tools/build_diag_lib.sh <tag> -DNPCD_DIAG_NO_WLOAD ...      (load it with NPCD_HIP_LIB=<path>)
 set -e
 tag=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)
