@@ -626,6 +626,32 @@ int npcd_ln_bwd_split3_bf16(const float* dy, const float* x, const float* mean, 
 int npcd_split3_colsum_bf16(const float* a, const float* h, const float* bias, void* out, float* part, int T, int N, int gelu,
                             void* stream);
 
+/* ---- stage-1 regularisers (csrc/stage1_losses.hip): the TV loss over each point's neighbour list (neural_point_cloud_tv_loss.py:29-83)
+ * and the KL loss of the variational feature embedding (neural_point_cloud_kl_loss.py:29-44), one launch each way, no host wait.
+ *   tv_i = weight_tv * sum_{j in list(i)} (1 / (|p_j - p_i| + 1e-5)) * sum_f |feat_j - feat_i|
+ *   kl_i = weight_kl * (-0.5) * sum_f (1 + log_var - mean^2 - exp(log_var));     totals = means over B N
+ * coords [B, N, 3] contiguous.  nb: int32 GLOBAL indices b N + j, -1 padded, row (b N + i) at nb + (b N + i) * nb_ld, k entries -- slot 0
+ * of the dense query result [B, N, M, k] is read in place with nb_ld = M k.  LIST RULE: an entry is skipped when it is negative, when it
+ * is the point itself (the reference drops self beside another neighbour and a lost point keeps itself: a self pair adds exactly 0 to
+ * value and gradient), or when it lies outside [b N, (b + 1) N) (the query never returns one; a hand-made or stale list cannot read out
+ * of bounds).  feats / mean / log_var: rows of F floats at row strides feats_ld / kl_ld / kl_ld.  nb == NULL leaves the TV term out,
+ * mean == NULL the KL term (their outputs are then not touched); at least one is given.
+ * Forward: tv_pointwise / kl_pointwise [B, N], tv_total / kl_total one float each; workspace: npcd_stage1_reg_workspace_floats(B)
+ * floats, uninitialised (per-cloud partial sums; a one-wave second launch adds them in ascending cloud order).
+ * Backward: the upstream gradient of point (b, i) is g_*_total[0] / (B N) + g_*_pointwise[b N + i]; each of the four may be NULL (= 0).
+ * dfeats / dmean / dlog_var [B, N, F] contiguous, fully written.  The part of dfeats that comes from the lists naming a point is
+ * gathered through a reverse table in ascending owner index: no float atomics, the same bits from run to run.  Coordinates get no
+ * gradient (detached in the reference).
+ * Supported: dtype NPCD_F32, N <= 4096, k N <= 32768, F <= 128; anything else is NPCD_ERR_UNSUPPORTED before any launch. */
+int64_t npcd_stage1_reg_workspace_floats(int B);
+int npcd_stage1_reg_fwd(const float* coords, const int32_t* nb, int64_t nb_ld, const float* feats, int64_t feats_ld, const float* mean,
+                        const float* log_var, int64_t kl_ld, int B, int N, int k, int F, float weight_tv, float weight_kl, int dtype,
+                        float* tv_pointwise, float* tv_total, float* kl_pointwise, float* kl_total, float* workspace, void* stream);
+int npcd_stage1_reg_bwd(const float* coords, const int32_t* nb, int64_t nb_ld, const float* feats, int64_t feats_ld, const float* mean,
+                        const float* log_var, int64_t kl_ld, int B, int N, int k, int F, float weight_tv, float weight_kl, int dtype,
+                        const float* g_tv_total, const float* g_tv_pointwise, const float* g_kl_total, const float* g_kl_pointwise,
+                        float* dfeats, float* dmean, float* dlog_var, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,9 @@ SIGNATURES = {
     "npcd_pair_mlp_bwd_slabs": (c_int, [c_int64, c_int]),
     "npcd_pair_mlp_bwd_workspace_floats": (c_int64, [c_int, c_int64, c_int]),
     "npcd_pair_mlp_bwd": (c_int, [_P, c_int, c_int] + [_P] * 5 + [c_int64] + [_P] * 3 + [POINTER(_P), POINTER(_P), _P]),
+    "npcd_stage1_reg_workspace_floats": (c_int64, [c_int]),
+    "npcd_stage1_reg_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, c_int64] + [c_int] * 4 + [c_float, c_float, c_int] + [_P] * 5 + [_P]),
+    "npcd_stage1_reg_bwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, c_int64] + [c_int] * 4 + [c_float, c_float, c_int] + [_P] * 7 + [_P]),
 }
 
 _lib = None

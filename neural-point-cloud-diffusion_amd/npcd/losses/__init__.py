@@ -9,6 +9,10 @@
                               neighbours (neural_point_cloud_tv_loss.py:29-83); the neighbour lists come from the HIP
                               voxel-grid query through `model.pointnerf.field.aggregator.query_keypoints`
     PointNeRFLoss             their weighted sum (pointnerf_loss.py:10-52; train_pointnerf.py:56-59 uses 1 / 1e-7 / 3.5e-7)
+
+`fused=True` (KL, TV) / `fused_regularisers=True` (PointNeRFLoss) -- opt-in, not in the reference -- computes the two regularisers on
+csrc/stage1_losses.hip (npcd.hip.losses): one launch forward and one backward for both, no host wait, the same terms summed in another
+(fixed) order.  The default is the torch-operator path below, which the reference fixture pins bit by bit.
 """
 import torch
 import torch.nn as nn
@@ -40,17 +44,50 @@ class ImageReconstructionLoss(_Loss):
         return loss, {"pointnerf_reconstruction": loss}, {}
 
 
+def self_neighbour_lists(agg, coords: torch.Tensor) -> torch.Tensor:
+    """Each point's own neighbourhood for the fused TV loss: coords [B, N, 3] -> int32 [B, N, k] global indices padded with -1, the
+    strided view of slot 0 of the aggregator's dense query (one "ray" per point with a single sample: only slot 0 can be filled, so
+    M = 1 gives what query_keypoints reads at M = max_shading_pts).  Nothing is compacted: no host wait.  The branch is chosen like
+    Aggregator.query_keypoints does; requires a preceding voxel_grid.set_pointset on the grid branch."""
+    from ..hip import render as hr
+    B, N = coords.shape[:2]
+    x = coords.reshape(B, N, 1, 3)
+    if agg.voxel_grid is None:
+        grid = hr.HipVoxelGrid((0.04,) * 3, (2,) * 3, (3,) * 3, 4, 5000, (-1, -1, -1, 1, 1, 1))
+        idx = grid.query_dense(agg.k, agg.r, 1, x=x, mode=1, points=coords)[0]
+    else:
+        idx = agg.voxel_grid.query_dense(agg.k, agg.r, 1, x=x, mode=0)[0]
+    return idx[:, :, 0]
+
+
 class NeuralPointCloudKLLoss(_Loss):
+    def __init__(self, model=None, weight=1, verbose=False, fused=False):
+        super().__init__(model, weight, verbose)
+        self.fused = fused
+
     def forward(self, sample, pred, aux, iteration):
         mean, log_var = aux["feats_mean"], aux["feats_log_var"]
+        if self.fused:
+            from ..hip.losses import stage1_regularisers
+            _, _, total, kld = stage1_regularisers(feats_mean=mean, feats_log_var=log_var, weight_kl=self.weight)
+            return total, {"00_neural_point_cloud_kl": total}, {"00_neural_point_cloud_kl": kld}
         kld = -0.5 * torch.sum(1 + log_var - mean.pow(2) - log_var.exp(), dim=-1) * self.weight      # [B, N]
         total = kld.mean()
         return total, {"00_neural_point_cloud_kl": total}, {"00_neural_point_cloud_kl": kld}
 
 
 class NeuralPointCloudTVLoss(_Loss):
+    def __init__(self, model=None, weight=1, verbose=False, fused=False):
+        super().__init__(model, weight, verbose)
+        self.fused = fused
+
     def forward(self, sample, pred, aux, iteration):
         feats, coords = aux["feats"], aux["coords"].detach()
+        if self.fused:
+            from ..hip.losses import stage1_regularisers
+            nb = self_neighbour_lists(self.model[0].pointnerf.field.aggregator, coords)
+            total, tv, _, _ = stage1_regularisers(coords, nb, feats, weight_tv=self.weight)
+            return total, {"00_neural_point_cloud_tv": total}, {"00_neural_point_cloud_tv": tv}
         B, N = coords.shape[:2]
         dev = coords.device
         agg = self.model[0].pointnerf.field.aggregator
@@ -77,11 +114,11 @@ class NeuralPointCloudTVLoss(_Loss):
 
 class PointNeRFLoss(nn.Module):
     def __init__(self, model, image_reconstruction_loss_weight=1, neural_point_cloud_kl_loss_weight=1,
-                 neural_point_cloud_tv_loss_weight=1, verbose=False):
+                 neural_point_cloud_tv_loss_weight=1, verbose=False, fused_regularisers=False):
         super().__init__()
         self.image_reconstruction_loss = ImageReconstructionLoss(model, image_reconstruction_loss_weight, verbose)
-        self.neural_point_cloud_kl_loss = NeuralPointCloudKLLoss(model, neural_point_cloud_kl_loss_weight, verbose)
-        self.neural_point_cloud_tv_loss = NeuralPointCloudTVLoss(model, neural_point_cloud_tv_loss_weight, verbose)
+        self.neural_point_cloud_kl_loss = NeuralPointCloudKLLoss(model, neural_point_cloud_kl_loss_weight, verbose, fused=fused_regularisers)
+        self.neural_point_cloud_tv_loss = NeuralPointCloudTVLoss(model, neural_point_cloud_tv_loss_weight, verbose, fused=fused_regularisers)
 
     @property
     def name(self):
@@ -89,7 +126,16 @@ class PointNeRFLoss(nn.Module):
 
     def forward(self, sample, pred, aux, iteration):
         rec, _, _ = self.image_reconstruction_loss(sample, pred, aux, iteration)
-        kl, _, _ = self.neural_point_cloud_kl_loss(sample, pred, aux, iteration)
-        tv, _, _ = self.neural_point_cloud_tv_loss(sample, pred, aux, iteration)
+        kl_loss, tv_loss = self.neural_point_cloud_kl_loss, self.neural_point_cloud_tv_loss
+        if kl_loss.fused and tv_loss.fused:
+            # both regularisers in ONE forward launch (and one backward)
+            from ..hip.losses import stage1_regularisers
+            coords = aux["coords"].detach()
+            nb = self_neighbour_lists(tv_loss.model[0].pointnerf.field.aggregator, coords)
+            tv, _, kl, _ = stage1_regularisers(coords, nb, aux["feats"], aux["feats_mean"], aux["feats_log_var"], tv_loss.weight,
+                                               kl_loss.weight)
+        else:
+            kl, _, _ = kl_loss(sample, pred, aux, iteration)
+            tv, _, _ = tv_loss(sample, pred, aux, iteration)
         sub = {"00_image_reconstruction_loss": rec, "01_neural_point_cloud_kl": kl, "02_neural_point_cloud_tv": tv}
         return rec + kl + tv, sub, {}

@@ -5,23 +5,30 @@
 The forward renders a few hundred random rays per view (npcd.models.pointnerf.train_path): ray generation and the
 neighbour queries (rendering and the TV loss) are HIP kernels, the differentiable shading runs on torch operators.
 """
+import os
+
 import torch
 
 from ..losses import PointNeRFLoss
 
 
 class PointNeRFTrainer:
-    def __init__(self, model, loss=None, lr: float = 1e-3, mlp_dtype=None):
+    def __init__(self, model, loss=None, lr: float = 1e-3, mlp_dtype=None, fused_losses=None):
         """model: NPCD (uses model.pointnerf); loss: a PointNeRFLoss (default weights of train_pointnerf.py:56-59).
         mlp_dtype: None (or torch.float32, or "library") = the reference's numerics (train_pointnerf.py runs without autocast): TRUE
         fp32 operands and accumulation, every Linear layer on fp32 library GEMMs;
         "fp32_class" = explicit opt-in, faster: every operand as two bf16 halves on the matrix cores (~1e-5 relative per product
         where fp32 has ~6e-8: csrc/pairs_mlp.hip precision 1, csrc/points_x2.hip) -- the per-pair layers forward + backward and,
         from 4,096 shading points on, the point-level layers' forward;
-        torch.bfloat16 = bf16 operands throughout (opt-in, narrower still)."""
+        torch.bfloat16 = bf16 operands throughout (opt-in, narrower still).
+        fused_losses: True = the default loss computes its KL and TV regularisers on csrc/stage1_losses.hip (one launch forward, one
+        backward, no host wait; the same terms in another fixed summation order); False = the torch operators (the default); None
+        (argument not passed) reads NPCD_FUSED_STAGE1_LOSSES=1 from the environment.  A `loss` given by the caller is used as it is."""
         self.model = model
         model.pointnerf.field.train_mlp_dtype = mlp_dtype
-        self.loss = loss if loss is not None else PointNeRFLoss(model, 1, 1e-7, 3.5e-7)
+        if fused_losses is None:
+            fused_losses = os.environ.get("NPCD_FUSED_STAGE1_LOSSES", "0") == "1"
+        self.loss = loss if loss is not None else PointNeRFLoss(model, 1, 1e-7, 3.5e-7, fused_regularisers=bool(fused_losses))
         # every parameter is handed to Adam like the reference does (:102): frozen ones never get a gradient or a state, but
         # keep their index, so optimizer state dictionaries are interchangeable with the reference's
         self.optimizer = torch.optim.Adam(model.pointnerf.parameters(), lr=lr)
@@ -30,7 +37,16 @@ class PointNeRFTrainer:
 
     def describe(self) -> str:
         """What runs where in this trainer's step (bench.py prints it next to the timing).  Derived from the predicates the forward
-        itself uses (train_path.fused_pair_mlp_precision / point_layers_fused), so the text cannot drift from the code path."""
+        itself uses (train_path.fused_pair_mlp_precision / point_layers_fused) and from the loss modules' own `fused` switches, so the
+        text cannot drift from the code path."""
+        kl, tv = (getattr(self.loss, n, None) for n in ("neural_point_cloud_kl_loss", "neural_point_cloud_tv_loss"))
+        fused = [name for name, part in (("KL", kl), ("TV", tv)) if getattr(part, "fused", False)]
+        if not fused:
+            return self._describe_step()
+        return (self._describe_step() + "; regularisers (" + " + ".join(fused) + "): fused HIP kernel pair, one launch forward and one "
+                "backward, no host wait (csrc/stage1_losses.hip)")
+
+    def _describe_step(self) -> str:
         from ..hip import render as hr
         from ..models.pointnerf.train_path import fused_pair_mlp_precision, point_layers_fused
         field = self.model.pointnerf.field
