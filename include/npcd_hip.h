@@ -489,6 +489,36 @@ int npcd_ddpm_reverse_step(const float* x_t, const void* eps, int eps_dtype, con
                            const float* tab_coef1, const float* tab_coef2, const float* tab_logvar, float clip_lo, float clip_hi,
                            int has_clip, void* stream);
 
+/* One step of the SCHEDULED sampler (strided DDIM schedule with eta in [0, 1]; replacement conditioning), both tensors of the step
+ * (coords, feats) in ONE launch.  `table` is fp32 [T, 8] on the device, one 32-byte row per level, indexed by the timestep itself:
+ * (r, m, c1, c2, s, h1, h2, 0), built by GaussianDiffusion.sampling_schedule (rows of levels that are not on the schedule are NaN;
+ * a timestep outside [0, T) reads no row and gives NaN).  Per tensor, with its own per_sample (fp32 [B, per_sample] throughout):
+ *   mode NPCD_SAMPLER_REVERSE: x0 = r[t] x_t - m[t] eps (clamped to [clip_lo, clip_hi] if has_clip; the same bits as the x0 of
+ *        the reverse step above on the same r, m), out = (c1[t] x0 + c2[t] x_t) + s[t] noise.  eps is fp32 or bf16 (eps_dtype).
+ *        noise may be NULL only when `deterministic` is non-zero (the caller's statement that every s of the table is 0, eta = 0):
+ *        the term is then skipped and nothing is read.  x0_out receives x0 when not NULL.  known is ignored.
+ *   mode NPCD_SAMPLER_HOLD   : out = h1[t] known + h2[t] noise (the known tensor forward-noised to the level the step arrives at;
+ *        exactly known on the last step, h1 = 1 and h2 = 0).  known and noise must be given; x_t, eps, x0_out and the clip are ignored.
+ * t is int64 [B], shared by both tensors.  Pointers are 4-byte aligned (2 bytes for bf16 eps); a tensor whose per_sample is a
+ * multiple of 4 and whose pointers are 16-byte aligned (8 bytes for bf16 eps) moves 16 bytes per lane.  No atomics: the same bits
+ * on every run.  NPCD_ERR_ARG for a missing pointer (a NULL noise without `deterministic` included) or a bad mode, NPCD_ERR_UNSUPPORTED
+ * for another eps_dtype or B above 65535, before any launch. */
+#define NPCD_SAMPLER_REVERSE 0
+#define NPCD_SAMPLER_HOLD 1
+typedef struct NpcdSamplerTensor {
+    const float* x_t;
+    const void* eps;
+    const float* noise;
+    const float* known;
+    float* out;
+    float* x0_out;
+    int64_t per_sample;
+    float clip_lo, clip_hi;
+    int32_t has_clip, mode, eps_dtype, reserved;
+} NpcdSamplerTensor;
+int npcd_sampler_step(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const int64_t* t, const float* table, int T,
+                      int B, int deterministic, void* stream);
+
 /* Forward process and training loss of the DDPM, fused (reference gaussian_diffusion.py:68-76 q_sample, :199-230 p_losses):
  *   npcd_q_sample    : x_t = tab_sqrt_acp[t_b] * x_0 + tab_sqrt_1macp[t_b] * noise, fp32 [B, per_sample], t int64 [B]; the products
  *                      and the sum are rounded separately like the reference's eager ops (bit-identical to them)

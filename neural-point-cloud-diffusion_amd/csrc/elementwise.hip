@@ -10,6 +10,8 @@
 //   column sum of a bf16 matrix (bias gradient of c_qkv)          -> colsum
 //   AdamW + EMA + bf16 weight shadow + gradient zeroing           -> adamw_ema (1 pass over 310 M params)
 //   GradScaler + clip_grad_norm_ bookkeeping on the device        -> grad_stats, scaler_finalize, adamw_ema_gated
+// and of the sampler (gaussian_diffusion.py:100-146): the DDPM reverse step per tensor -> ddpm_reverse; a step of the scheduled sampler
+// (strided DDIM levels, eta, one tensor held), both tensors in one launch          -> sampler_step
 // All are pure streaming kernels: 16-byte accesses per lane, fp32 math, no LDS except the cross-wave
 // reduction of column partials.  Roofline: HBM.
 #include <math.h>
@@ -719,6 +721,111 @@ __global__ __launch_bounds__(256) void ddpm_reverse_kernel(const float* __restri
     }
 }
 
+// Scheduled sampler step (strided DDIM schedule with eta in [0, 1], and replacement conditioning): ONE launch advances both tensors of
+// a step, blockIdx.z = 0 coords, 1 feats, blockIdx.y = sample.  The seven coefficients of a sample are one 32-byte row of the
+// [T, 8] table, indexed by the timestep itself (GaussianDiffusion.sampling_schedule):
+//   reverse: x0 = clamp(r x - m eps) (the expression of ddpm_reverse_kernel: the same bits), out = (c1 x0 + c2 x) [+ s z]
+//   hold   : out = h1 known + h2 z       (the known tensor, forward-noised to the level the step arrives at)
+// `noise` of a reverse tensor may be null (eta = 0: every s is 0): the term is then skipped and nothing is read.  A timestep outside
+// [0, T) reads no table row and gives NaN outputs.  Tensors whose per_sample is a multiple of 4 and whose pointers are 16-byte
+// aligned (8 bytes for bf16 eps) move 16 bytes per lane; the others one element per lane, on the grid of ddpm_reverse_kernel.
+struct SamplerCoef {
+    float r, m, c1, c2, s, h1, h2;
+};
+struct SamplerArgs {
+    NpcdSamplerTensor tz[2];
+    int vec[2];
+};
+
+// The roundings are written out (fused multiply-adds), so that the 16-byte and the one-element path give the same bits and x0 is what
+// ddpm_reverse_kernel's `a * x - bb * eps` compiles to: fma(a, x, -(bb eps)).  x0: 2 roundings, out: 3 more, hold: 2.
+__device__ __forceinline__ float sampler_x0(const SamplerCoef& k, float x, float e, int has_clip, float lo, float hi) {
+    float x0 = __builtin_fmaf(k.r, x, -(k.m * e));
+    if (has_clip) x0 = fminf(fmaxf(x0, lo), hi);
+    return x0;
+}
+
+template <class EPS, bool VEC>
+__device__ __forceinline__ void sampler_reverse(const NpcdSamplerTensor& a, const SamplerCoef& k, int64_t base) {
+    const float* __restrict__ x_t = a.x_t + base;
+    const EPS* __restrict__ eps = static_cast<const EPS*>(a.eps) + base;
+    const float* __restrict__ noise = a.noise ? a.noise + base : nullptr;
+    float* __restrict__ out = a.out + base;
+    float* __restrict__ x0_out = a.x0_out ? a.x0_out + base : nullptr;
+    if constexpr (VEC) {
+        const int64_t n4 = a.per_sample / 4;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+            const f32x4 x = reinterpret_cast<const f32x4*>(x_t)[i];
+            const f32x4 e = to_f32(reinterpret_cast<const typename V<EPS>::x4*>(eps)[i]);
+            f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (noise) z = reinterpret_cast<const f32x4*>(noise)[i];
+            f32x4 x0, o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                x0[q] = sampler_x0(k, x[q], e[q], a.has_clip, a.clip_lo, a.clip_hi);
+                o[q] = __builtin_fmaf(k.c1, x0[q], k.c2 * x[q]);
+                if (noise) o[q] = __builtin_fmaf(k.s, z[q], o[q]);
+            }
+            if (x0_out) reinterpret_cast<f32x4*>(x0_out)[i] = x0;
+            reinterpret_cast<f32x4*>(out)[i] = o;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256) {
+            const float x = x_t[i];
+            const float x0 = sampler_x0(k, x, (float)eps[i], a.has_clip, a.clip_lo, a.clip_hi);
+            float o = __builtin_fmaf(k.c1, x0, k.c2 * x);
+            if (noise) o = __builtin_fmaf(k.s, noise[i], o);
+            if (x0_out) x0_out[i] = x0;
+            out[i] = o;
+        }
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void sampler_hold(const NpcdSamplerTensor& a, const SamplerCoef& k, int64_t base) {
+    const float* __restrict__ known = a.known + base;
+    const float* __restrict__ noise = a.noise + base;
+    float* __restrict__ out = a.out + base;
+    if constexpr (VEC) {
+        const int64_t n4 = a.per_sample / 4;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+            const f32x4 kn = reinterpret_cast<const f32x4*>(known)[i], z = reinterpret_cast<const f32x4*>(noise)[i];
+            f32x4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = __builtin_fmaf(k.h1, kn[q], k.h2 * z[q]);
+            reinterpret_cast<f32x4*>(out)[i] = o;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256)
+            out[i] = __builtin_fmaf(k.h1, known[i], k.h2 * noise[i]);
+    }
+}
+
+__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerArgs args, const int64_t* __restrict__ t, const float* __restrict__ table, int T) {
+    const int z = blockIdx.z, b = blockIdx.y;
+    const NpcdSamplerTensor& a = args.tz[z];
+    const int vec = args.vec[z];
+    // (blocks of the wider tensor's grid that lie past this tensor's range fall through their loop)
+    const int64_t ts = t[b];
+    const float nan = __builtin_nanf("");
+    SamplerCoef k{nan, nan, nan, nan, nan, nan, nan};
+    if (ts >= 0 && ts < T) {
+        const f32x4 lo = reinterpret_cast<const f32x4*>(table)[2 * ts], hi = reinterpret_cast<const f32x4*>(table)[2 * ts + 1];
+        k = SamplerCoef{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2]};
+    }
+    const int64_t base = (int64_t)b * a.per_sample;
+    if (a.mode == NPCD_SAMPLER_HOLD) {
+        if (vec) sampler_hold<true>(a, k, base);
+        else sampler_hold<false>(a, k, base);
+    } else if (a.eps_dtype == NPCD_F32) {
+        if (vec) sampler_reverse<float, true>(a, k, base);
+        else sampler_reverse<float, false>(a, k, base);
+    } else {
+        if (vec) sampler_reverse<__bf16, true>(a, k, base);
+        else sampler_reverse<__bf16, false>(a, k, base);
+    }
+}
+
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace npcd
@@ -1070,6 +1177,39 @@ extern "C" int npcd_ddpm_reverse_step(const float* x_t, const void* eps, int eps
     else
         hipLaunchKernelGGL(ddpm_reverse_kernel<__bf16>, dim3(gx, B), dim3(256), 0, st, x_t, static_cast<const __bf16*>(eps), noise, x_prev, x0_out, t,
                            per_sample, tab, clip_lo, clip_hi, has_clip);
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
+}
+
+extern "C" int npcd_sampler_step(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const int64_t* t, const float* table, int T,
+                                 int B, int deterministic, void* stream) {
+    if (!coords || !feats || !t || !table || T <= 0 || B <= 0) return NPCD_ERR_ARG;
+    if (B > 65535 || !al16(table)) return NPCD_ERR_UNSUPPORTED;
+    SamplerArgs args;
+    int gx = 1;
+    for (int z = 0; z < 2; ++z) {
+        const NpcdSamplerTensor& a = z ? *feats : *coords;
+        if (!a.out || a.per_sample <= 0) return NPCD_ERR_ARG;
+        bool vec = a.per_sample % 4 == 0 && al16(a.out);
+        if (a.mode == NPCD_SAMPLER_HOLD) {
+            if (!a.known || !a.noise) return NPCD_ERR_ARG;
+            vec = vec && al16(a.known) && al16(a.noise);
+        } else if (a.mode == NPCD_SAMPLER_REVERSE) {
+            if (!a.x_t || !a.eps || (!a.noise && !deterministic)) return NPCD_ERR_ARG;
+            if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
+            vec = vec && al16(a.x_t) && (!a.noise || al16(a.noise)) && (!a.x0_out || al16(a.x0_out)) &&
+                  (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
+        } else {
+            return NPCD_ERR_ARG;
+        }
+        args.tz[z] = a;
+        args.vec[z] = vec ? 1 : 0;
+        // the grid of ddpm_reverse_kernel: one sweep of 256 lanes per workgroup, at most 1024 workgroups per sample, the rest strided
+        const int64_t items = vec ? a.per_sample / 4 : a.per_sample;
+        const int g = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
+        gx = g > gx ? g : gx;
+    }
+    hipLaunchKernelGGL(sampler_step_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }

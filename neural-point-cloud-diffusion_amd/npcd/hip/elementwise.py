@@ -370,6 +370,71 @@ def ddpm_reverse_step(x_t, eps, noise, t, tables, clip=None, want_x0=False):
     return out, x0
 
 
+class SamplerTensor(ctypes.Structure):
+    """NpcdSamplerTensor (include/npcd_hip.h)."""
+    _fields_ = [("x_t", ctypes.c_void_p), ("eps", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("known", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("x0_out", ctypes.c_void_p), ("per_sample", ctypes.c_int64), ("clip_lo", ctypes.c_float),
+                ("clip_hi", ctypes.c_float), ("has_clip", ctypes.c_int32), ("mode", ctypes.c_int32), ("eps_dtype", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+SAMPLER_REVERSE, SAMPLER_HOLD = 0, 1
+
+
+def _sampler_tensor(spec, B):
+    """One tensor of sampler_step -> (the C record, out, x0 or None, the tensors the record points to)."""
+    hold = spec.get("mode", "reverse") == "hold"
+    if spec.get("mode", "reverse") not in ("reverse", "hold"):
+        raise ValueError("sampler_step: mode is 'reverse' or 'hold'")
+    keep = [None if spec.get(k) is None else spec[k].contiguous() for k in ("x_t", "eps", "noise", "known")]
+    x_t, eps, noise, known = keep
+    like = known if hold else x_t
+    if like is None:
+        like = next((v for v in keep if v is not None), None)
+    if like is None or like.shape[0] != B:
+        raise RuntimeError("sampler_step: every tensor is [B, ...] with the B of t")
+    for v in (x_t, noise, known):
+        if v is not None and (v.dtype != _f32 or v.shape != like.shape):
+            raise RuntimeError("sampler_step: x_t, noise and known are fp32 tensors of one shape")
+    if eps is not None and eps.shape != like.shape:
+        raise RuntimeError("sampler_step: eps has the shape of x_t")
+    require_gpu(*[v for v in keep if v is not None])
+    out = spec.get("out")
+    out = arena.empty(like.shape, _f32, like.device) if out is None else out
+    x0 = spec.get("x0_out")
+    if x0 is None and spec.get("want_x0") and not hold:
+        x0 = arena.empty(like.shape, _f32, like.device)
+    clip = None if hold else spec.get("clip")
+    rec = SamplerTensor()
+    rec.x_t, rec.eps, rec.noise, rec.known = (0 if v is None else v.data_ptr() for v in keep)
+    rec.out, rec.x0_out = out.data_ptr(), (0 if x0 is None else x0.data_ptr())
+    rec.per_sample = like.numel() // B
+    rec.clip_lo, rec.clip_hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
+    rec.has_clip, rec.mode = int(clip is not None), SAMPLER_HOLD if hold else SAMPLER_REVERSE
+    rec.eps_dtype = dtype_code(eps) if eps is not None else 2
+    return rec, out, x0, keep
+
+
+def sampler_step(coords, feats, t, table, deterministic):
+    """One step of the scheduled sampler for BOTH tensors in one launch (npcd_sampler_step).  `coords` / `feats` are dicts:
+         mode "reverse" (default): x_t fp32 [B, ...], eps fp32 or bf16, noise fp32 or None, clip (lo, hi) floats or None, want_x0
+         mode "hold"             : known fp32 [B, ...], noise fp32
+       and optionally out / x0_out, contiguous fp32 tensors to write into (otherwise from the arena).  t int64 [B]; table fp32 [T, 8]
+       and deterministic (eta == 0: every s of the table is 0, the only case in which a reverse tensor may come without noise) are
+       SamplingSchedule.table / .deterministic.  -> ((out, x0 or None) of coords, (out, x0 or None) of feats)."""
+    require_gpu(t, table)
+    if t.dtype != torch.int64 or table.dtype != _f32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise RuntimeError("sampler_step: t is int64 [B], table a contiguous fp32 [T, 8]")
+    t = t.contiguous()
+    B = t.shape[0]
+    rc, oc, x0c, keep_c = _sampler_tensor(coords, B)
+    rf, of, x0f, keep_f = _sampler_tensor(feats, B)
+    check(lib().npcd_sampler_step(ctypes.byref(rc), ctypes.byref(rf), ptr(t), ptr(table), table.shape[0], B, int(bool(deterministic)),
+                                  stream_ptr()), "npcd_sampler_step")
+    del keep_c, keep_f
+    return (oc, x0c), (of, x0f)
+
+
 def q_sample(x0, noise, t, tab_sqrt_acp, tab_sqrt_1macp):
     """x_t = sqrt(acp[t]) x_0 + sqrt(1 - acp[t]) noise in one launch (coefficients looked up on the device).  fp32 [B, ...]."""
     require_gpu(x0, noise, t)

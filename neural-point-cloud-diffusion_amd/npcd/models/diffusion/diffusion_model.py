@@ -80,11 +80,22 @@ class DiffusionModel(nn.Module):
         return self.diffusion_process.p_losses(self.denoiser, coords, feats, t, coords_noise, feats_noise, want_pointwise=want_pointwise)
 
     @torch.no_grad()
-    def generate(self, num, batch_size=8, progress=True, dtype=None, use_graph=False):
+    def generate(self, num, batch_size=8, progress=True, dtype=None, use_graph=False, sampling_steps=None, eta=None, coords=None, feats=None):
         """Reference :108-133.  Two options the reference does not have: `dtype` (e.g. torch.bfloat16) runs the denoiser under
         autocast on the MFMA attention kernels -- 6x faster per reverse step than the reference's fp32 sampling, eps within the
-        training-time bf16 tolerance; `use_graph` replays each reverse step from a captured HIP graph."""
+        training-time bf16 tolerance; `use_graph` replays each reverse step from a captured HIP graph.
+
+        Scheduled sampling (GaussianDiffusion.p_sample_loop(steps=, eta=, hold=); any of the four arguments selects it, none of them
+        leaves today's loop and bits): `sampling_steps` levels of a strided schedule instead of all of them, `eta` in [0, 1] (0: the
+        deterministic DDIM step, one launch and no noise; default 1), and ONE of `coords` [num, 3, N] / `feats` [num, F, N] in data
+        space (what generate returns, stacked): that tensor is held -- at every level the denoiser sees it forward-noised -- and the
+        other one is sampled; it comes back as the caller's values, unclipped, bit for bit."""
         assert not self.training, "Model must be in eval mode for generation"
+        if coords is not None and feats is not None:
+            raise ValueError("generate(coords=, feats=): at most one of the two tensors can be held")
+        for name, given, dim in (("coords", coords, self.coords_dim), ("feats", feats, self.feats_dim)):
+            if given is not None and tuple(given.shape) != (num, dim, self.num_points):
+                raise ValueError(f"generate({name}=...): expected shape {(num, dim, self.num_points)}, got {tuple(given.shape)}")
         device = next(self.parameters()).device
         sizes = [batch_size] * (num // batch_size) + ([num % batch_size] if num % batch_size else [])
         # dtype = "fp32_class": the reference's fp32 sampling with the backbone's Linear layers as split-operand bf16 GEMMs (two bf16 halves
@@ -98,22 +109,37 @@ class DiffusionModel(nn.Module):
         if backbone is not None:
             backbone.fp32_class = fp32_class
         try:
-            return self._generate(sizes, device, ctx, progress, use_graph)
+            return self._generate(sizes, device, ctx, progress, use_graph, sampling_steps, eta, coords, feats)
         finally:
             if backbone is not None:
                 backbone.fp32_class = prev_mode
 
-    def _generate(self, sizes, device, ctx, progress, use_graph):
+    def _generate(self, sizes, device, ctx, progress, use_graph, sampling_steps=None, eta=None, coords=None, feats=None):
         coords_out, feats_out = [], []
+        given = coords if coords is not None else feats
+        norm = self.coords_normalization if coords is not None else self.feats_normalization
+        done = 0
         for bs in sizes:
             c = torch.randn(bs, self.coords_dim, self.num_points, device=device)
             f = torch.randn(bs, self.feats_dim, self.num_points, device=device)
+            new = {}
+            if sampling_steps is not None or eta is not None or given is not None:
+                new = dict(steps=sampling_steps, eta=1.0 if eta is None else eta)
+            if given is not None:
+                part = given[done:done + bs].to(device=device, dtype=torch.float32)
+                # data -> model space, written out: the modules are in eval mode, where their forward is the inverse map
+                known = (part - norm.shift[None, :, None]) / norm.scale[None, :, None]
+                new["hold"] = ("coords" if coords is not None else "feats", known)
             with ctx:
                 c, f = self.diffusion_process.p_sample_loop(
                     self.denoiser, c, f,
                     coords_clip_range=(self.coords_normalization.min, self.coords_normalization.max),
                     feats_clip_range=(self.feats_normalization.min, self.feats_normalization.max), progress=progress,
-                    use_graph=use_graph)
-            coords_out += list(self.coords_normalization(c).unbind())
-            feats_out += list(self.feats_normalization(f).unbind())
+                    use_graph=use_graph, **new)
+            c, f = self.coords_normalization(c), self.feats_normalization(f)
+            if given is not None:                      # the caller's own values: the round trip through model space is not exact
+                c, f = (given[done:done + bs].to(c), f) if coords is not None else (c, given[done:done + bs].to(f))
+            coords_out += list(c.unbind())
+            feats_out += list(f.unbind())
+            done += bs
         return coords_out, feats_out

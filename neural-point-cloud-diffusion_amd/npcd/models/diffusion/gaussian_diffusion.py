@@ -21,6 +21,41 @@ def _linear_betas(steps: int) -> np.ndarray:
     return np.linspace(k * 1e-4, k * 0.02, steps, dtype=np.float64)
 
 
+SCHEDULE_COLUMNS = ("r", "m", "c1", "c2", "s", "h1", "h2")
+
+
+class SamplingSchedule:
+    """K levels tau_0 < ... < tau_{K-1} of a T-level chain (round(linspace(0, T - 1, K)); [T - 1] for K = 1) and, for the step from
+    tau_i to tau_{i-1} (tau_{-1}: the data, acp = 1), the DDIM coefficients with variance factor eta (Song et al. 2021, eq. 12 and 16),
+    in float64 from the float64 cumulative product of 1 - np_betas[:T], with a = acp[tau_i], p = acp[tau_{i-1}]:
+        sigma = eta sqrt((1 - p) / (1 - a)) sqrt(1 - a / p),   d = sqrt(1 - p - sigma^2)
+        x_prev = c1 x0 + c2 x_t + s z:   c1 = sqrt(p) - d / sqrt(1 / a - 1),  c2 = d sqrt(1 / a) / sqrt(1 / a - 1),  s = sigma
+        held   = h1 known + h2 z     :   h1 = sqrt(p),  h2 = sqrt(1 - p)       (the forward process at the level the step arrives at)
+    eta = 1 with K = T is the DDPM posterior of the reference.  `coef64[name]` are the float64 arrays [K]; `table` is the device
+    form, fp32 [T, 8], row tau_i = (r, m, c1, c2, s, h1, h2, 0) with each coefficient rounded once and r, m (x0 = r x_t - m eps)
+    taken from the module's fp32 tables, so that x0 has the bits of the DDPM kernel's; rows of levels off the schedule are NaN."""
+
+    def __init__(self, process, T, K, eta, device):
+        self.T, self.steps, self.eta, self.deterministic = T, K, eta, eta == 0.0
+        ts = np.array([T - 1], dtype=np.int64) if K == 1 else np.round(np.linspace(0.0, T - 1.0, K)).astype(np.int64)
+        self.timesteps = ts
+        acp = np.cumprod(1.0 - np.asarray(process.np_betas, dtype=np.float64)[:T])
+        a = acp[ts]
+        p = np.concatenate(([1.0], a[:-1]))
+        sigma = eta * np.sqrt((1.0 - p) / (1.0 - a)) * np.sqrt(1.0 - a / p)
+        d = np.sqrt(np.maximum(1.0 - p - sigma * sigma, 0.0))
+        rm1 = np.sqrt(1.0 / a - 1.0)
+        self.coef64 = {"c1": np.sqrt(p) - d / rm1, "c2": d * np.sqrt(1.0 / a) / rm1, "s": sigma, "h1": np.sqrt(p), "h2": np.sqrt(1.0 - p)}
+        table = torch.full((T, 8), float("nan"), dtype=torch.float32)
+        idx = torch.from_numpy(ts)
+        table[idx, 0] = process.sqrt_recip_alphas_cumprod.detach().cpu()[idx]
+        table[idx, 1] = process.sqrt_recipm1_alphas_cumprod.detach().cpu()[idx]
+        for j, name in enumerate(SCHEDULE_COLUMNS[2:], start=2):
+            table[idx, j] = torch.from_numpy(self.coef64[name]).float()
+        table[idx, 7] = 0.0
+        self.table = table.to(device).contiguous()
+
+
 class GaussianDiffusion(nn.Module):
     def __init__(self, num_timesteps: int = 1000):
         super().__init__()
@@ -141,11 +176,124 @@ class GaussianDiffusion(nn.Module):
         f_next, _ = ew.ddpm_reverse_step(feats_t, eps_f, torch.randn_like(feats_t), t, tabs, feats_clip)
         return c_next, f_next
 
+    # ---- scheduled sampler: strided DDIM schedule with eta in [0, 1], replacement conditioning ---------------------------------
+    def sampling_schedule(self, steps=None, eta=1.0, device=None):
+        """The SamplingSchedule of `steps` levels (None: all T = self.num_timesteps, read now) and `eta`, its table on `device`
+        (default: where the module's tables are); cached per (T, steps, eta, device)."""
+        T = int(self.num_timesteps)
+        K = T if steps is None else int(steps)
+        if steps is not None and K != steps:
+            raise ValueError(f"sampling steps must be an integer (got {steps!r})")
+        if not 1 <= K <= T:
+            raise ValueError(f"sampling steps must lie in 1..{T} (got {K})")
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"eta must lie in [0, 1] (got {eta})")
+        device = torch.device(self.sqrt_recip_alphas_cumprod.device if device is None else device)
+        key = (T, K, eta, str(device))
+        cache = self.__dict__.setdefault("_schedules", {})
+        if key not in cache:
+            cache[key] = SamplingSchedule(self, T, K, eta, device)
+        return cache[key]
+
+    @staticmethod
+    def _hold_spec(hold):
+        if hold is None:
+            return None, None
+        which, known = hold
+        if which not in ("coords", "feats") or not torch.is_tensor(known):
+            raise ValueError("hold is None, ('coords', known) or ('feats', known)")
+        return which, known
+
+    def _scheduled_step(self, denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused):
+        """One step of the scheduled loop.  RNG order: coords noise, then feats noise; a reverse-mode tensor draws only if eta > 0,
+        the held tensor at every step.  fused: ONE launch for both tensors (npcd_sampler_step), clip_* are (lo, hi) floats or None;
+        otherwise the same step in torch, clip_* are the ranges as given to p_sample_loop."""
+        eps_c, eps_f = denoise_fn(c, f, t)
+        draw = not sched.deterministic
+        zc = torch.randn_like(c) if (draw or which == "coords") else None
+        zf = torch.randn_like(f) if (draw or which == "feats") else None
+        if fused:
+            from ...hip import elementwise as ew
+            spec = []
+            for name, x, eps, z, clip in (("coords", c, eps_c, zc, clip_c), ("feats", f, eps_f, zf, clip_f)):
+                if which == name:
+                    spec.append(dict(mode="hold", known=known, noise=z))
+                else:
+                    eps = eps if eps.dtype in (torch.float32, torch.bfloat16) else eps.float()
+                    spec.append(dict(mode="reverse", x_t=x, eps=eps, noise=z, clip=clip))
+            (c_next, _), (f_next, _) = ew.sampler_step(spec[0], spec[1], t, sched.table, sched.deterministic)
+            return c_next, f_next
+        row = sched.table.to(t.device)[t]                                   # [B, 8]: r, m, c1, c2, s, h1, h2, 0
+        out = []
+        for name, x, eps, z, clip in (("coords", c, eps_c, zc, clip_c), ("feats", f, eps_f, zf, clip_f)):
+            k = [row[:, j].reshape((-1,) + (1,) * (x.dim() - 1)) for j in range(7)]
+            if which == name:
+                out.append(k[5] * known + k[6] * z)
+                continue
+            x0 = k[0] * x - k[1] * eps.float()
+            if clip is not None:
+                x0 = torch.clamp(x0, clip[0], clip[1])
+            nxt = k[2] * x0 + k[3] * x
+            out.append(nxt if z is None else nxt + k[4] * z)
+        return out[0], out[1]
+
+    def _p_sample_loop_scheduled(self, denoise_fn, coords_start, feats_start, coords_clip_range, feats_clip_range, progress, use_graph,
+                                 steps, eta, hold):
+        """The loop behind p_sample_loop(steps=, eta=, hold=): the schedule's levels in descending order, one _scheduled_step each."""
+        c, f = coords_start, feats_start
+        sched = self.sampling_schedule(steps, 1.0 if eta is None else eta, device=c.device)
+        which, known = self._hold_spec(hold)
+        levels = [int(i) for i in sched.timesteps[::-1]]
+        if progress:
+            from tqdm.auto import tqdm
+            levels = tqdm(levels)
+        t = torch.full((c.shape[0],), int(sched.timesteps[-1]), device=c.device, dtype=torch.long)
+        if which is not None:                 # the held tensor starts as the known one noised to the first level, its start tensor as the noise
+            known = known.to(device=c.device, dtype=torch.float32).contiguous()
+            start = self.q_sample(known, t, coords_start if which == "coords" else feats_start)
+            c, f = (start, f) if which == "coords" else (c, start)
+        has_c, clip_c = self._scalar_clip(coords_clip_range)
+        has_f, clip_f = self._scalar_clip(feats_clip_range)
+        fused = c.is_cuda and c.dtype == torch.float32 and f.dtype == torch.float32 and not (has_c and clip_c is None) and not (has_f and clip_f is None)
+        if not fused:
+            clip_c, clip_f = coords_clip_range, feats_clip_range
+        if not (fused and use_graph):
+            for i in levels:
+                t.fill_(i)
+                c, f = self._scheduled_step(denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused)
+            return c, f
+        # graph replay, as in p_sample_loop: static state buffers, warm-up on a side stream, one captured step, t refilled between replays
+        sc, sf = c.clone(), f.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._scheduled_step(denoise_fn, sc, sf, t, sched, which, known, clip_c, clip_f, True)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            oc, of = self._scheduled_step(denoise_fn, sc, sf, t, sched, which, known, clip_c, clip_f, True)
+        for i in levels:
+            t.fill_(i)
+            graph.replay()
+            sc.copy_(oc)
+            sf.copy_(of)
+        return sc.clone(), sf.clone()
+
     def p_sample_loop(self, denoise_fn, coords_start, feats_start, coords_clip_range=None, feats_clip_range=None,
-                      progress=False, use_graph=False):
+                      progress=False, use_graph=False, steps=None, eta=None, hold=None):
         """1000 reverse steps (reference :148-177 without the trajectory lists).  On the GPU with scalar clip ranges every step
         runs the fused posterior update; `use_graph` additionally captures one whole step (denoiser forward + update, fixed
-        batch) in a HIP graph and replays it -- the per-step launch work (~600 launches at 24 layers) leaves the host."""
+        batch) in a HIP graph and replays it -- the per-step launch work (~600 launches at 24 layers) leaves the host.
+
+        Any of `steps` (levels of a strided schedule, 1..T), `eta` (0 = deterministic DDIM .. 1 = DDPM variance; default 1) and
+        `hold` (("coords" | "feats", known in model space): that tensor is, at every level, the known one forward-noised, and ends
+        as `known`) selects the scheduled loop instead (sampling_schedule / _scheduled_step, whose docstring fixes the RNG order);
+        the held tensor's start tensor serves as its start noise.  Without them: today's loop, today's bits."""
+        if steps is not None or eta is not None or hold is not None:
+            return self._p_sample_loop_scheduled(denoise_fn, coords_start, feats_start, coords_clip_range, feats_clip_range, progress,
+                                                 use_graph, steps, eta, hold)
         steps = range(self.num_timesteps - 1, -1, -1)
         if progress:
             from tqdm.auto import tqdm
