@@ -682,6 +682,22 @@ int npcd_stage1_reg_bwd(const float* coords, const int32_t* nb, int64_t nb_ld, c
                         const float* g_tv_total, const float* g_tv_pointwise, const float* g_kl_total, const float* g_kl_pointwise,
                         float* dfeats, float* dmean, float* dlog_var, void* stream);
 
+/* ---- farthest point sampling (csrc/fps.hip): the operator of pytorch3d.ops.sample_farthest_points, which the
+ * reference's dataset uses to cut a raw surface cloud down to num_points points (npcd/data/srn.py:179-188).
+ * points [N, P, 3] fp32 contiguous.  lengths / ks / start: int32 [N] on the device, each may be NULL: valid points per cloud (P),
+ * picks per cloud (Kmax), index of the first pick (0).  Cloud i makes min(ks[i], lengths[i], Kmax) picks: the start index, then again
+ * and again the valid point whose squared distance to the nearest earlier pick, ((dx dx + dy dy) + dz dz) in fp32 without
+ * contraction, is largest -- the LOWEST index among equals.  idx_out [N, Kmax] int64, pts_out [N, Kmax, 3] fp32 (bit copies of the
+ * picked rows); the slots after a cloud's picks hold -1 and 0.0.  Both are fully written.  Integer-exact and the same on every run.
+ * lengths are clamped to [0, P] and start to [0, length) on the device, so that no value read there reaches outside the cloud;
+ * non-finite coordinates are not checked for (the result is then unspecified, never out of bounds).
+ * One workgroup per cloud: up to npcd_fps_resident_points() points the cloud lives in registers, up to npcd_fps_max_points() it is
+ * streamed from L2 at every pick.  NPCD_ERR_UNSUPPORTED for P above that, and for N, P or Kmax <= 0, before any pointer is looked at. */
+int npcd_fps_resident_points(void);
+int npcd_fps_max_points(void);
+int npcd_fps(const float* points, const int32_t* lengths, const int32_t* ks, const int32_t* start, int64_t* idx_out, float* pts_out,
+             int N, int P, int Kmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

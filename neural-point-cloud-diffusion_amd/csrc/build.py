@@ -43,6 +43,8 @@ SOURCES = {
     "points_x2.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     # the regularisers are compared with torch's fp32 operators term by term: evaluate the expressions as written
     "stage1_losses.hip": ["-ffp-contract=off"],
+    # farthest point sampling picks by comparing fp32 squared distances bit for bit with its spec: no FMA contraction
+    "fps.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

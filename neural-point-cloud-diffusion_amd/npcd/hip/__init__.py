@@ -138,6 +138,9 @@ SIGNATURES = {
     "npcd_stage1_reg_workspace_floats": (c_int64, [c_int]),
     "npcd_stage1_reg_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, c_int64] + [c_int] * 4 + [c_float, c_float, c_int] + [_P] * 5 + [_P]),
     "npcd_stage1_reg_bwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, c_int64] + [c_int] * 4 + [c_float, c_float, c_int] + [_P] * 7 + [_P]),
+    "npcd_fps_resident_points": (c_int, []),
+    "npcd_fps_max_points": (c_int, []),
+    "npcd_fps": (c_int, [_P] * 6 + [c_int, c_int, c_int, _P]),
 }
 
 _lib = None
