@@ -698,6 +698,21 @@ int npcd_fps_max_points(void);
 int npcd_fps(const float* points, const int32_t* lengths, const int32_t* ks, const int32_t* start, int64_t* idx_out, float* pts_out,
              int N, int P, int Kmax, void* stream);
 
+/* ---- all-pairs directed Chamfer matrix (csrc/chamfer.hip): the distance under the shape metrics MMD-CD / COV-CD /
+ * 1-NNA-CD of npcd/eval/shapes.py.  x [M, P, 3], y [N, Q, 3] fp32 contiguous; x_len / y_len: int32 [M] / [N] on the device, valid
+ * points per cloud, either may be NULL (P / Q).  out [M, N] fp32, fully written:
+ *   out[i, j] = ( sum_{p < Lx_i} min_{q < Ly_j} d(x_ip, y_jq) ) / Lx_i,   d(a, b) = ((dx dx + dy dy) + dz dz), dx = a.x - b.x ...
+ * in fp32 without contraction.  min is exact, so every per-point minimum is the bits of that expression; the sum over p has one fixed
+ * order (no float atomics: the same bits on every run) and, with the division, is all that rounds.  The norm-expansion form is not
+ * used.  Lengths are clamped to [1, P] and [1, Q] on the device; rows at or after a cloud's length are never looked at for the result
+ * and no read leaves the arrays whatever the lengths hold; non-finite coordinates are not checked for (the result is then
+ * unspecified, never out of bounds).  x and y are only read and may be the same pointer.  No workspace, no scratch.
+ * NPCD_ERR_UNSUPPORTED for M, N, P or Q <= 0, for P or Q above npcd_chamfer_max_points() (4,096) and for M or N above 16,384, before
+ * any pointer is looked at; NPCD_ERR_ARG for a NULL x, y or out. */
+int npcd_chamfer_max_points(void);
+int npcd_chamfer_directed(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, float* out, int M, int P, int N,
+                          int Q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,10 @@ SOURCES = {
     "stage1_losses.hip": ["-ffp-contract=off"],
     # farthest point sampling picks by comparing fp32 squared distances bit for bit with its spec: no FMA contraction
     "fps.hip": ["-ffp-contract=off"],
+    # the Chamfer kernel's per-point minima are the bits of its spec's fp32 distance expression, for the same reason.
+    # -fno-slp-vectorize: its loop is nothing but fp32 VALU; packed into v_pk_mul/add_f32 (plus the moves that pair the operands) the
+    # 2,000 x 512 self-matrix took 163 ms, as single operations 133 ms (docs/experiments.md R15.1)
+    "chamfer.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

@@ -9,6 +9,8 @@ from typing import Dict, Iterable, List
 
 import torch
 
+from .shapes import evaluate_shapes, metrics_from_chamfer, normalize_clouds, shape_metrics  # noqa: F401
+
 
 def psnr(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> float:
     """skimage.metrics.peak_signal_noise_ratio in float64 (:254): 10 log10(data_range^2 / mse)."""

@@ -1,0 +1,115 @@
+"""Shape metrics of generated point clouds: MMD-CD, COV-CD and 1-NNA-CD (Achlioptas et al. 2018; Yang et al. 2019, PointFlow) between a
+generated set and a reference set, through the all-pairs Chamfer kernel of npcd/hip/chamfer.py.  They need no outside
+assets: the reference set can be the stage-1 clouds (`model.pointnerf.get_all_coords()`) or the subsampled dataset clouds of
+npcd/data/pointclouds.py.
+
+Definitions follow PointFlow's evaluation: squared distances, means over points, CD(X, Y) = mean_x min_y d + mean_y min_x d.
+  MMD-CD    mean over the reference clouds of the distance to the nearest generated cloud            (lower is better)
+  COV-CD    share of the reference clouds that are the nearest reference of some generated cloud      (higher is better)
+  1-NNA-CD  leave-one-out accuracy of the 1-nearest-neighbour classifier "generated or reference?" on the union (0.5 is best)
+This module imports without a GPU; only `shape_metrics` and `evaluate_shapes` need one.
+"""
+import time
+from typing import Dict, Optional
+
+import torch
+
+
+def _first_argmin(m: torch.Tensor) -> torch.Tensor:
+    """Row-wise arg-min, the LOWEST index among equal minima (torch.argmin does not promise which one it returns)."""
+    cols = torch.arange(m.shape[1], device=m.device)
+    return torch.where(m == m.min(dim=1, keepdim=True).values, cols, m.shape[1]).min(dim=1).values
+
+
+def metrics_from_chamfer(cd_union: torch.Tensor, num_generated: int) -> Dict:
+    """cd_union [T, T]: the symmetric Chamfer matrix of the union set, rows and columns [:M] the generated clouds, [M:] the N
+    reference clouds (M = num_generated).  Device-agnostic torch; the reductions run in float64, ties go to the lowest index, one
+    small host read at the end.  -> mmd_cd, cov_cd = cov_matched / N, nna_cd = nna_correct / (M + N), the two counts, num_generated,
+    num_reference."""
+    if cd_union.dim() != 2 or cd_union.shape[0] != cd_union.shape[1]:
+        raise ValueError(f"metrics_from_chamfer: cd_union must be square; got {tuple(cd_union.shape)}")
+    T, M = cd_union.shape[0], int(num_generated)
+    N = T - M
+    if M < 1 or N < 1:
+        raise ValueError(f"metrics_from_chamfer: {M} generated and {N} reference clouds in a union of {T}")
+    cd = cd_union.detach().double()
+    gen_ref = cd[:M, M:]
+    mmd = gen_ref.min(dim=0).values.mean()
+    hit = torch.zeros(N, dtype=torch.float64, device=cd.device)
+    hit[_first_argmin(gen_ref)] = 1.0
+    others = cd.clone()
+    others.fill_diagonal_(float("inf"))
+    nearest = _first_argmin(others)
+    side = torch.arange(T, device=cd.device) < M
+    correct = (side[nearest] == side).double().sum()
+    mmd, matched, correct = torch.stack([mmd, hit.sum(), correct]).tolist()
+    matched, correct = int(round(matched)), int(round(correct))
+    return {"mmd_cd": mmd, "cov_cd": matched / N, "nna_cd": correct / T, "cov_matched": matched, "nna_correct": correct,
+            "num_generated": M, "num_reference": N}
+
+
+def normalize_clouds(clouds: torch.Tensor, mode: Optional[str] = "bbox") -> torch.Tensor:
+    """clouds [n, P, 3].  mode "bbox": every cloud shifted by the centre of its axis-aligned bounding box and divided by half its
+    longest side (it then fits [-1, 1]^3 and touches it on one axis).  None: unchanged.  Plain torch."""
+    if mode is None:
+        return clouds
+    if mode != "bbox":
+        raise ValueError(f"normalize_clouds: unknown mode {mode!r} (None or 'bbox')")
+    if clouds.dim() != 3 or clouds.shape[2] != 3:
+        raise ValueError(f"normalize_clouds: clouds must be [n, P, 3]; got {tuple(clouds.shape)}")
+    lo, hi = clouds.min(dim=1, keepdim=True).values, clouds.max(dim=1, keepdim=True).values
+    half = (hi - lo).max(dim=2, keepdim=True).values * 0.5
+    return (clouds - (lo + hi) * 0.5) / half
+
+
+def shape_metrics(generated: torch.Tensor, reference: torch.Tensor, normalize: Optional[str] = None, gen_lengths=None,
+                  ref_lengths=None) -> Dict:
+    """generated [M, P, 3], reference [N, Q, 3] fp32 on the GPU (P != Q allowed), optional valid lengths per cloud as for
+    npcd.hip.chamfer -> the dict of `metrics_from_chamfer`.  One kernel launch on the union set when P = Q and no lengths are given,
+    the four directed blocks otherwise.  `normalize` is applied to whole clouds and so cannot be combined with lengths."""
+    from ..hip.chamfer import chamfer_directed, chamfer_matrix
+    if normalize is not None:
+        if gen_lengths is not None or ref_lengths is not None:
+            raise ValueError("shape_metrics: normalize works on whole clouds; normalise the valid rows yourself when lengths are given")
+        generated, reference = normalize_clouds(generated, normalize), normalize_clouds(reference, normalize)
+    M = generated.shape[0]
+    if generated.dim() == 3 and generated.shape[1:] == reference.shape[1:] and gen_lengths is None and ref_lengths is None:
+        cd = chamfer_matrix(torch.cat([generated, reference]))
+    else:
+        gg = chamfer_matrix(generated, None, gen_lengths)
+        rr = chamfer_matrix(reference, None, ref_lengths)
+        gr = chamfer_directed(generated, reference, gen_lengths, ref_lengths) + chamfer_directed(reference, generated, ref_lengths,
+                                                                                                 gen_lengths).t()
+        cd = torch.cat([torch.cat([gg, gr], dim=1), torch.cat([gr.t(), rr], dim=1)])
+    return metrics_from_chamfer(cd, M)
+
+
+@torch.no_grad()
+def evaluate_shapes(model, reference: torch.Tensor, num_samples: int, generate_batch_size: int = 8, normalize: Optional[str] = None,
+                    return_clouds: bool = False, **generate_kwargs) -> Dict:
+    """Sample `num_samples` clouds with model.diffusion.generate (`model`: an NPCD, or its DiffusionModel itself;
+    `generate_batch_size` at a time; dtype, use_graph, sampling_steps, eta ... pass through untouched) and compare their shape
+    halves with `reference` [N, Q, 3].  -> the dict of
+    `shape_metrics` plus generate_seconds / metric_seconds (device-synchronised walls) and, with return_clouds, `clouds` [M, P, 3]."""
+    model.eval()
+    sampler = getattr(model, "diffusion", model)
+    dev = next(sampler.parameters()).device
+    clouds = []
+    t_gen = 0.0
+    for s0 in range(0, num_samples, generate_batch_size):
+        n = min(generate_batch_size, num_samples - s0)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        coords, _ = sampler.generate(num=n, batch_size=n, progress=False, **generate_kwargs)
+        torch.cuda.synchronize()
+        t_gen += time.time() - t0
+        clouds.append(torch.stack(list(coords)).permute(0, 2, 1))          # [n, 3, P] -> [n, P, 3]
+    generated = torch.cat(clouds).float().contiguous()
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = shape_metrics(generated, reference.to(dev).float(), normalize=normalize)
+    torch.cuda.synchronize()
+    out.update(generate_seconds=t_gen, metric_seconds=time.time() - t0)
+    if return_clouds:
+        out["clouds"] = generated
+    return out
