@@ -713,6 +713,19 @@ int npcd_chamfer_max_points(void);
 int npcd_chamfer_directed(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, float* out, int M, int P, int N,
                           int Q, void* stream);
 
+/* ---- all-pairs directed approximate earth mover's distance (csrc/emd.hip): the second distance under the shape
+ * metrics of npcd/eval/shapes.py (MMD-EMD / COV-EMD / 1-NNA-EMD).  Arguments, null lengths and the clamping of lengths as for
+ * npcd_chamfer_directed.  out [M, N] fp32, fully written: the cost of the approximate matching of Fan et al. between the valid rows
+ * of x_i and y_j -- ten levels exp(level d), level = -4^7 ... -4^0, -4^-1, 0, three passes each, d as above -- divided by
+ * T = max(Lx, Ly); directed, out(x, y) != out(y, x) in general.  All fp32; every sum has one fixed order and there are no float
+ * atomics: the same bits on every run.  The match matrix is never stored.  No read leaves the arrays whatever the lengths hold;
+ * non-finite coordinates are not checked for.  x and y are only read and may be the same pointer.  No workspace, no scratch.
+ * NPCD_ERR_UNSUPPORTED for M, N, P or Q <= 0, for P or Q above npcd_emd_max_points() (2,048) and for M or N above 16,384, before any
+ * pointer is looked at; NPCD_ERR_ARG for a NULL x, y or out. */
+int npcd_emd_max_points(void);
+int npcd_emd_directed(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, float* out, int M, int P, int N, int Q,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,9 @@ SOURCES = {
     # -fno-slp-vectorize: its loop is nothing but fp32 VALU; packed into v_pk_mul/add_f32 (plus the moves that pair the operands) the
     # 2,000 x 512 self-matrix took 163 ms, as single operations 133 ms (docs/experiments.md R15.1)
     "chamfer.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # the approximate earth mover's distance evaluates the same fp32 distance expression as written; its sums are
+    # explicit fused multiply-adds.  Single operations rather than packed ones, as for chamfer.hip
+    "emd.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

@@ -9,7 +9,7 @@ from typing import Dict, Iterable, List
 
 import torch
 
-from .shapes import evaluate_shapes, metrics_from_chamfer, normalize_clouds, shape_metrics  # noqa: F401
+from .shapes import evaluate_shapes, metrics_from_chamfer, metrics_from_distance, normalize_clouds, shape_metrics  # noqa: F401
 
 
 def psnr(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> float:

@@ -21,17 +21,14 @@ def _first_argmin(m: torch.Tensor) -> torch.Tensor:
     return torch.where(m == m.min(dim=1, keepdim=True).values, cols, m.shape[1]).min(dim=1).values
 
 
-def metrics_from_chamfer(cd_union: torch.Tensor, num_generated: int) -> Dict:
-    """cd_union [T, T]: the symmetric Chamfer matrix of the union set, rows and columns [:M] the generated clouds, [M:] the N
-    reference clouds (M = num_generated).  Device-agnostic torch; the reductions run in float64, ties go to the lowest index, one
-    small host read at the end.  -> mmd_cd, cov_cd = cov_matched / N, nna_cd = nna_correct / (M + N), the two counts, num_generated,
-    num_reference."""
+def _reduce(cd_union: torch.Tensor, num_generated: int, who: str):
+    """The three reductions on a symmetric distance matrix of the union set -> (mmd, matched, correct, M, N)."""
     if cd_union.dim() != 2 or cd_union.shape[0] != cd_union.shape[1]:
-        raise ValueError(f"metrics_from_chamfer: cd_union must be square; got {tuple(cd_union.shape)}")
+        raise ValueError(f"{who}: cd_union must be square; got {tuple(cd_union.shape)}")
     T, M = cd_union.shape[0], int(num_generated)
     N = T - M
     if M < 1 or N < 1:
-        raise ValueError(f"metrics_from_chamfer: {M} generated and {N} reference clouds in a union of {T}")
+        raise ValueError(f"{who}: {M} generated and {N} reference clouds in a union of {T}")
     cd = cd_union.detach().double()
     gen_ref = cd[:M, M:]
     mmd = gen_ref.min(dim=0).values.mean()
@@ -43,9 +40,25 @@ def metrics_from_chamfer(cd_union: torch.Tensor, num_generated: int) -> Dict:
     side = torch.arange(T, device=cd.device) < M
     correct = (side[nearest] == side).double().sum()
     mmd, matched, correct = torch.stack([mmd, hit.sum(), correct]).tolist()
-    matched, correct = int(round(matched)), int(round(correct))
-    return {"mmd_cd": mmd, "cov_cd": matched / N, "nna_cd": correct / T, "cov_matched": matched, "nna_correct": correct,
+    return mmd, int(round(matched)), int(round(correct)), M, N
+
+
+def metrics_from_chamfer(cd_union: torch.Tensor, num_generated: int) -> Dict:
+    """cd_union [T, T]: the symmetric Chamfer matrix of the union set, rows and columns [:M] the generated clouds, [M:] the N
+    reference clouds (M = num_generated).  Device-agnostic torch; the reductions run in float64, ties go to the lowest index, one
+    small host read at the end.  -> mmd_cd, cov_cd = cov_matched / N, nna_cd = nna_correct / (M + N), the two counts, num_generated,
+    num_reference."""
+    mmd, matched, correct, M, N = _reduce(cd_union, num_generated, "metrics_from_chamfer")
+    return {"mmd_cd": mmd, "cov_cd": matched / N, "nna_cd": correct / (M + N), "cov_matched": matched, "nna_correct": correct,
             "num_generated": M, "num_reference": N}
+
+
+def metrics_from_distance(matrix: torch.Tensor, num_generated: int, name: str) -> Dict:
+    """The reductions of `metrics_from_chamfer` on the symmetric union matrix of any distance, keys suffixed with `name`:
+    mmd_<name>, cov_<name>, nna_<name>, cov_matched_<name>, nna_correct_<name>, and num_generated, num_reference."""
+    mmd, matched, correct, M, N = _reduce(matrix, num_generated, "metrics_from_distance")
+    return {f"mmd_{name}": mmd, f"cov_{name}": matched / N, f"nna_{name}": correct / (M + N), f"cov_matched_{name}": matched,
+            f"nna_correct_{name}": correct, "num_generated": M, "num_reference": N}
 
 
 def normalize_clouds(clouds: torch.Tensor, mode: Optional[str] = "bbox") -> torch.Tensor:
@@ -62,35 +75,55 @@ def normalize_clouds(clouds: torch.Tensor, mode: Optional[str] = "bbox") -> torc
     return (clouds - (lo + hi) * 0.5) / half
 
 
+def _union_matrix(mod, matrix: str, directed: str, combine, generated, reference, gen_lengths, ref_lengths):
+    """The symmetric matrix of the union set from the kernels of `mod` (looked up at the call): one launch when P = Q and no lengths
+    are given, else the four directed blocks, the cross block `combine`d from its two directions."""
+    matrix, directed = getattr(mod, matrix), getattr(mod, directed)
+    if generated.dim() == 3 and generated.shape[1:] == reference.shape[1:] and gen_lengths is None and ref_lengths is None:
+        return matrix(torch.cat([generated, reference]))
+    gg = matrix(generated, None, gen_lengths)
+    rr = matrix(reference, None, ref_lengths)
+    gr = combine(directed(generated, reference, gen_lengths, ref_lengths), directed(reference, generated, ref_lengths, gen_lengths).t())
+    return torch.cat([torch.cat([gg, gr], dim=1), torch.cat([gr.t(), rr], dim=1)])
+
+
+def _emd_metrics(generated, reference, gen_lengths, ref_lengths) -> Dict:
+    """The EMD keys of `shape_metrics` on clouds that are already normalised."""
+    from ..hip import emd as emd_mod
+    return metrics_from_distance(_union_matrix(emd_mod, "emd_matrix", "emd_directed", lambda a, b: 0.5 * (a + b), generated, reference,
+                                               gen_lengths, ref_lengths), generated.shape[0], "emd")
+
+
 def shape_metrics(generated: torch.Tensor, reference: torch.Tensor, normalize: Optional[str] = None, gen_lengths=None,
-                  ref_lengths=None) -> Dict:
+                  ref_lengths=None, emd: bool = False) -> Dict:
     """generated [M, P, 3], reference [N, Q, 3] fp32 on the GPU (P != Q allowed), optional valid lengths per cloud as for
     npcd.hip.chamfer -> the dict of `metrics_from_chamfer`.  One kernel launch on the union set when P = Q and no lengths are given,
-    the four directed blocks otherwise.  `normalize` is applied to whole clouds and so cannot be combined with lengths."""
-    from ..hip.chamfer import chamfer_directed, chamfer_matrix
+    the four directed blocks otherwise.  `normalize` is applied to whole clouds and so cannot be combined with lengths.
+    emd = True adds mmd_emd, cov_emd, nna_emd, cov_matched_emd and nna_correct_emd, the same reductions on the approximate earth
+    mover's distance of npcd.hip.emd (clouds of up to 2,048 points), computed the same way; the other keys are
+    untouched."""
+    from ..hip import chamfer as chamfer_mod
     if normalize is not None:
         if gen_lengths is not None or ref_lengths is not None:
             raise ValueError("shape_metrics: normalize works on whole clouds; normalise the valid rows yourself when lengths are given")
         generated, reference = normalize_clouds(generated, normalize), normalize_clouds(reference, normalize)
     M = generated.shape[0]
-    if generated.dim() == 3 and generated.shape[1:] == reference.shape[1:] and gen_lengths is None and ref_lengths is None:
-        cd = chamfer_matrix(torch.cat([generated, reference]))
-    else:
-        gg = chamfer_matrix(generated, None, gen_lengths)
-        rr = chamfer_matrix(reference, None, ref_lengths)
-        gr = chamfer_directed(generated, reference, gen_lengths, ref_lengths) + chamfer_directed(reference, generated, ref_lengths,
-                                                                                                 gen_lengths).t()
-        cd = torch.cat([torch.cat([gg, gr], dim=1), torch.cat([gr.t(), rr], dim=1)])
-    return metrics_from_chamfer(cd, M)
+    out = metrics_from_chamfer(_union_matrix(chamfer_mod, "chamfer_matrix", "chamfer_directed", lambda a, b: a + b, generated,
+                                             reference, gen_lengths, ref_lengths), M)
+    if emd:
+        out.update(_emd_metrics(generated, reference, gen_lengths, ref_lengths))
+    return out
 
 
 @torch.no_grad()
 def evaluate_shapes(model, reference: torch.Tensor, num_samples: int, generate_batch_size: int = 8, normalize: Optional[str] = None,
-                    return_clouds: bool = False, **generate_kwargs) -> Dict:
+                    return_clouds: bool = False, emd: bool = False, **generate_kwargs) -> Dict:
     """Sample `num_samples` clouds with model.diffusion.generate (`model`: an NPCD, or its DiffusionModel itself;
     `generate_batch_size` at a time; dtype, use_graph, sampling_steps, eta ... pass through untouched) and compare their shape
     halves with `reference` [N, Q, 3].  -> the dict of
-    `shape_metrics` plus generate_seconds / metric_seconds (device-synchronised walls) and, with return_clouds, `clouds` [M, P, 3]."""
+    `shape_metrics` plus generate_seconds / metric_seconds (device-synchronised walls) and, with return_clouds, `clouds` [M, P, 3].
+    emd = True adds the EMD keys of `shape_metrics` and emd_seconds, the wall of the EMD part alone (metric_seconds stays the
+    wall of the Chamfer part)."""
     model.eval()
     sampler = getattr(model, "diffusion", model)
     dev = next(sampler.parameters()).device
@@ -110,6 +143,11 @@ def evaluate_shapes(model, reference: torch.Tensor, num_samples: int, generate_b
     out = shape_metrics(generated, reference.to(dev).float(), normalize=normalize)
     torch.cuda.synchronize()
     out.update(generate_seconds=t_gen, metric_seconds=time.time() - t0)
+    if emd:
+        t0 = time.time()
+        out.update(_emd_metrics(normalize_clouds(generated, normalize), normalize_clouds(reference.to(dev).float(), normalize), None, None))
+        torch.cuda.synchronize()
+        out["emd_seconds"] = time.time() - t0
     if return_clouds:
         out["clouds"] = generated
     return out

@@ -143,6 +143,8 @@ SIGNATURES = {
     "npcd_fps": (c_int, [_P] * 6 + [c_int, c_int, c_int, _P]),
     "npcd_chamfer_max_points": (c_int, []),
     "npcd_chamfer_directed": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
+    "npcd_emd_max_points": (c_int, []),
+    "npcd_emd_directed": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
 }
 
 _lib = None

@@ -4,13 +4,12 @@ under the shape metrics of npcd/eval/shapes.py.
 One launch per directed matrix, one float written per cloud pair, the same bits on every run.  There is no CPU fallback: a non-GPU
 tensor, a dtype other than fp32 or a cloud above `max_points()` raises RuntimeError.
 """
-from typing import Optional, Sequence, Union
+from typing import Optional
 
 import torch
 
-from . import check, lib, ptr, require_gpu, stream_ptr
-
-IntList = Union[int, Sequence[int], torch.Tensor]
+from . import check, lib, ptr, stream_ptr
+from ._clouds import IntList, prepare
 
 
 def max_points() -> int:
@@ -18,66 +17,8 @@ def max_points() -> int:
     return lib().npcd_chamfer_max_points()
 
 
-def _clouds(t, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        shape = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)
-        raise ValueError(f"chamfer: {name} must be [n, P, 3] with n, P >= 1; got {shape}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"HIP Chamfer distance supports fp32 coordinates; got {t.dtype} for {name}")
-    return t
-
-
-def _lengths(v, n: int, P: int, name: str):
-    """Valid points per cloud: host values (an int for every cloud, a sequence, a CPU tensor) are checked here and returned as a
-    list; a GPU tensor is returned as it is, never read back (the kernel clamps it to [1, P])."""
-    if v is None:
-        return None
-    if isinstance(v, torch.Tensor) and v.is_cuda:
-        if v.dim() != 1 or v.shape[0] != n or v.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"chamfer: {name} must be an integer tensor of shape [{n}]; got {v.dtype} {tuple(v.shape)}")
-        return v
-    if isinstance(v, int):
-        v = [v] * n
-    out = [int(a) for a in (v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else v)]
-    if len(out) != n:
-        raise ValueError(f"chamfer: {name} has {len(out)} entries for {n} clouds")
-    if min(out) < 1 or max(out) > P:
-        raise ValueError(f"chamfer: {name} must lie in [1, {P}]; got {out}")
-    return out
-
-
-def _device_i32(v, dev):
-    if v is None:
-        return None
-    if isinstance(v, torch.Tensor):
-        return v.to(device=dev, dtype=torch.int32).contiguous()
-    return torch.tensor(v, dtype=torch.int32).to(dev, non_blocking=True)
-
-
 def _prepare(x, y, x_lengths, y_lengths):
-    """Checked arguments -> (x, y, x_len, y_len) contiguous on the device; y is x itself (one tensor, one pointer) when not given."""
-    x = _clouds(x, "x")
-    xl = _lengths(x_lengths, x.shape[0], x.shape[1], "x_lengths")
-    if y is None:
-        if y_lengths is not None:
-            raise ValueError("chamfer: y_lengths given without y (the lengths of y = x are x_lengths)")
-        yl = xl
-    else:
-        y = _clouds(y, "y")
-        yl = _lengths(y_lengths, y.shape[0], y.shape[1], "y_lengths")
-    require_gpu(x, y, *(t for t in (xl, yl) if isinstance(t, torch.Tensor)))
-    limit = lib().npcd_chamfer_max_points()
-    if x.shape[1] > limit or (y is not None and y.shape[1] > limit):
-        raise RuntimeError(f"HIP Chamfer distance supports clouds of up to {limit} points; got {x.shape[1]}"
-                           + (f" and {y.shape[1]}" if y is not None else ""))
-    dev = x.device
-    x = x.detach().contiguous()
-    d_xl = _device_i32(xl, dev)
-    if y is None:
-        return x, x, d_xl, d_xl
-    if y.device != dev:
-        raise RuntimeError(f"chamfer: x is on {dev}, y on {y.device}")
-    return x, y.detach().contiguous(), d_xl, _device_i32(yl, dev)
+    return prepare(x, y, x_lengths, y_lengths, "chamfer", "Chamfer distance", max_points)
 
 
 def _directed(x, x_len, y, y_len):
