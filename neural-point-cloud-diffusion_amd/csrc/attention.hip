@@ -862,21 +862,7 @@ __device__ __forceinline__ void fwd64_flush(const FragAddr& fa, QBlk& A, QBlk& B
 // (m, l, O[64]) goes to scratch; attn_fwd_rowx_merge_kernel combines the partials of a (batch, head), adds the pair (x, x) and writes
 // the row and its LSE.
 
-// wave-wide max / sum on the vector ALU (no LDS crossbar): four DPP row rotations inside the 16-lane rows, then v_permlane16_swap
-// and v_permlane32_swap across them; every lane ends with the result
-template <class Op>
-__device__ __forceinline__ float wave_reduce64(float x, Op op) {
-    x = op(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128 /* row_ror:8 */, 0xf, 0xf, false)));
-    x = op(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124 /* row_ror:4 */, 0xf, 0xf, false)));
-    x = op(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x122 /* row_ror:2 */, 0xf, 0xf, false)));
-    x = op(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x121 /* row_ror:1 */, 0xf, 0xf, false)));
-    const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = op(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-    const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return op(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-}
-__device__ __forceinline__ float wave_max64(float x) { return wave_reduce64(x, [](float a, float b) { return fmaxf(a, b); }); }
-__device__ __forceinline__ float wave_sum64(float x) { return wave_reduce64(x, [](float a, float b) { return a + b; }); }
+// (wave_max64 / wave_sum64: the all-lanes reduction of wave.h)
 // The key tile is the one in ring slot SLOT; behind the ring: 256 bytes of scratch per wave (the row's P), then the 128-byte copy of
 // the last query row (made by the prologue).
 constexpr int kRowxFloats = 68;        // O[64], m, l, pad (272 B: records stay 16-byte aligned)

@@ -2,10 +2,10 @@
 //
 //   X [M, P, 3], Y [N, Q, 3] fp32;  Lx_i = clamp(x_len[i], 1, P) (P when NULL), Ly_j = clamp(y_len[j], 1, Q) (Q when NULL)
 //   out[i, j] = ( sum_{p < Lx_i}  min_{q < Ly_j}  d(x_ip, y_jq) ) / Lx_i
-//   d(a, b)   = ((dx dx + dy dy) + dz dz),  dx = a.x - b.x ...   (fp32, as written: this file is compiled without FMA contraction)
+//   d(a, b)   = ((dx dx + dy dy) + dz dz),  dx = a.x - b.x ...   (cloud_sqdist of clouds.h: fp32, as written, no FMA contraction)
 //
 // min is exact, so every per-point minimum is the bits of a numpy fp32 evaluation of d; only the sum over p and the division round.
-// The sum has one fixed order (the lane's points in ascending p, a fixed tree over the wave's lanes, the four waves in ascending
+// The sum has one fixed order (the lane's points in ascending p, wave_sum_tree of wave.h over the lanes, the four waves in ascending
 // order) and there is no atomic: the same bits on every run.  The norm-expansion form |a|^2 + |b|^2 - 2 a.b is not used anywhere: it
 // cancels exactly at the nearest pairs, the only distances that are kept.
 //
@@ -19,54 +19,16 @@
 // are summed and out[i, j] is stored once; nothing else is written.
 // No read leaves the arrays whatever the lengths hold: an X row at or after Lx_i is not loaded (the lane keeps zeros and its minima
 // are left out of the sum), Y rows are addressed through min(row, Ly_j - 1).  X and Y are only read and may be the same pointer.
-#include "common.h"
+#include "clouds.h"
 
 namespace npcd {
 
-constexpr int kChamferThreads = 256, kChamferWaves = kChamferThreads / kWave;
+constexpr int kChamferThreads = kCloudPairThreads, kChamferWaves = kChamferThreads / kWave;
 constexpr int kChamferTile = 512;                              // Y rows per LDS tile
 constexpr int kChamferTileWords = kChamferTile * 3;            // fp32 words of a tile: 6 KiB
 constexpr int kChamferStage = kChamferTileWords / kChamferThreads;          // words a lane stages per tile
 constexpr int kChamferMaxPoints = 16 * kChamferThreads;        // the largest instantiation
-constexpr int kChamferMaxClouds = 16384;                       // M and N
-constexpr int kChamferChunk = 32;                              // Y clouds per workgroup, at most
-constexpr int kChamferFill = 2048;                             // the chunk shrinks until the grid has this many workgroups
 static_assert(kChamferTileWords % kChamferThreads == 0 && kChamferTile % 4 == 0, "whole staging rounds, whole groups of four rows");
-// the grid is one-dimensional: the largest one, one X cloud per workgroup and whole chunks, stays below 2^32 threads
-static_assert((int64_t)kChamferMaxClouds * (kChamferMaxClouds / kChamferChunk) * kChamferThreads < (int64_t)1 << 32, "grid too large");
-
-struct ChamferArgs {
-    const float *x, *y;              // [M, P, 3], [N, Q, 3]
-    const int32_t *x_len, *y_len;    // [M], [N], either may be NULL
-    float* out;                      // [M, N]
-    int M, P, N, Q;
-    int chunk, nchunks;              // Y clouds per workgroup, workgroups per X group
-};
-
-__device__ __forceinline__ float chamfer_d(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// v + the lane that `ctrl` names; lanes without a source, or outside row_mask, add 0
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float chamfer_dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWMASK, 0xf, false));
-}
-
-// sum over the wave in one fixed tree, wave-uniform: row_shr:1,2,4,8, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and
-// 3, lane 63
-__device__ __forceinline__ float chamfer_wave_sum(float v) {
-    v = chamfer_dpp_add<0x111, 0xf>(v);
-    v = chamfer_dpp_add<0x112, 0xf>(v);
-    v = chamfer_dpp_add<0x114, 0xf>(v);
-    v = chamfer_dpp_add<0x118, 0xf>(v);
-    v = chamfer_dpp_add<0x142, 0xa>(v);
-    v = chamfer_dpp_add<0x143, 0xc>(v);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-__device__ __forceinline__ int chamfer_len(const int32_t* len, int i, int full) { return len ? min(max(len[i], 1), full) : full; }
 
 // tile `t` of a Y cloud of `L` valid rows at `yj`: the words this lane stages.  Word w of the tile is coordinate w % 3 of tile row
 // w / 3; rows past the cloud's end, up to the next multiple of four, repeat row L - 1; words past that are not used and not read.
@@ -81,7 +43,7 @@ __device__ __forceinline__ void chamfer_fetch(const float* __restrict__ yj, int 
 }
 
 template <int PPL, int G>
-__global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a) {
+__global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(CloudPairArgs a) {
     __shared__ __attribute__((aligned(16))) float tile[2][kChamferTileWords];
     __shared__ float part[2][G][kChamferWaves];
     const int tid = threadIdx.x;
@@ -96,7 +58,7 @@ __global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a)
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int i = group * G + g;
-        const int Lx = i < a.M ? chamfer_len(a.x_len, i, P) : 0;
+        const int Lx = i < a.M ? cloud_len(a.x_len, i, P) : 0;
         const float* __restrict__ xi = a.x + (int64_t)min(i, a.M - 1) * P * 3;
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
@@ -111,7 +73,7 @@ __global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a)
 
     // the first tile
     int j = j0, t = 0;
-    int Ly = chamfer_len(a.y_len, j, Q);
+    int Ly = cloud_len(a.y_len, j, Q);
     float pre[kChamferStage];
     chamfer_fetch(a.y + (int64_t)j * Q * 3, Ly, 0, tid, pre);
 #pragma unroll
@@ -125,7 +87,7 @@ __global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a)
         // the step after this one: the cloud's next tile, or the next cloud's first
         const int nj = last_tile ? j + 1 : j, nt = last_tile ? 0 : t + 1;
         const bool more = nj < j1;
-        const int nLy = more ? (last_tile ? chamfer_len(a.y_len, nj, Q) : Ly) : 1;
+        const int nLy = more ? (last_tile ? cloud_len(a.y_len, nj, Q) : Ly) : 1;
         if (more) chamfer_fetch(a.y + (int64_t)nj * Q * 3, nLy, nt, tid, pre);
 
         const int groups4 = (min(kChamferTile, Ly - t * kChamferTile) + 3) >> 2;
@@ -137,10 +99,10 @@ __global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a)
             for (int g = 0; g < G; ++g) {
 #pragma unroll
                 for (int k = 0; k < PPL; ++k) {
-                    const float d0 = chamfer_d(px[g][k], py[g][k], pz[g][k], u[0], u[1], u[2]);
-                    const float d1 = chamfer_d(px[g][k], py[g][k], pz[g][k], u[3], v[0], v[1]);
-                    const float d2 = chamfer_d(px[g][k], py[g][k], pz[g][k], v[2], v[3], w[0]);
-                    const float d3 = chamfer_d(px[g][k], py[g][k], pz[g][k], w[1], w[2], w[3]);
+                    const float d0 = cloud_sqdist(px[g][k], py[g][k], pz[g][k], u[0], u[1], u[2]);
+                    const float d1 = cloud_sqdist(px[g][k], py[g][k], pz[g][k], u[3], v[0], v[1]);
+                    const float d2 = cloud_sqdist(px[g][k], py[g][k], pz[g][k], v[2], v[3], w[0]);
+                    const float d3 = cloud_sqdist(px[g][k], py[g][k], pz[g][k], w[1], w[2], w[3]);
                     mn[g][k] = fminf(fminf(fminf(fminf(mn[g][k], d0), d1), d2), d3);
                 }
             }
@@ -156,7 +118,7 @@ __global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a)
                     s += valid[g][k] ? mn[g][k] : 0.f;
                     mn[g][k] = inf;
                 }
-                s = chamfer_wave_sum(s);
+                s = wave_sum_tree(s);
                 if ((tid & (kWave - 1)) == 0) part[j & 1][g][tid / kWave] = s;
             }
         }
@@ -174,7 +136,7 @@ __global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a)
                 float s = part[j & 1][tid][0];
 #pragma unroll
                 for (int wv = 1; wv < kChamferWaves; ++wv) s += part[j & 1][tid][wv];
-                a.out[(int64_t)i * a.N + j] = s / (float)chamfer_len(a.x_len, i, P);
+                a.out[(int64_t)i * a.N + j] = s / (float)cloud_len(a.x_len, i, P);
             }
         }
         if (!more) break;
@@ -185,12 +147,9 @@ __global__ __launch_bounds__(kChamferThreads) void chamfer_kernel(ChamferArgs a)
 }
 
 template <int PPL, int G>
-static void chamfer_launch(ChamferArgs a, hipStream_t st) {
+static void chamfer_launch(CloudPairArgs a, hipStream_t st) {
     const int64_t groups = (a.M + G - 1) / G;
-    int chunk = kChamferChunk;
-    while (chunk > 1 && groups * ((a.N + chunk - 1) / chunk) < kChamferFill) chunk /= 2;
-    a.chunk = chunk;
-    a.nchunks = (a.N + chunk - 1) / chunk;
+    cloud_pair_chunks(groups, a.N, &a.chunk, &a.nchunks);
     hipLaunchKernelGGL((chamfer_kernel<PPL, G>), dim3((unsigned)(groups * a.nchunks)), dim3(kChamferThreads), 0, st, a);
 }
 
@@ -202,11 +161,9 @@ extern "C" int npcd_chamfer_max_points(void) { return kChamferMaxPoints; }
 
 extern "C" int npcd_chamfer_directed(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, float* out, int M, int P,
                                      int N, int Q, void* stream) {
-    if (M <= 0 || N <= 0 || P <= 0 || Q <= 0 || P > kChamferMaxPoints || Q > kChamferMaxPoints || M > kChamferMaxClouds ||
-        N > kChamferMaxClouds)
-        return NPCD_ERR_UNSUPPORTED;
-    if (!x || !y || !out) return NPCD_ERR_ARG;
-    const ChamferArgs a{x, y, x_len, y_len, out, M, P, N, Q, 0, 0};
+    const int rc = cloud_pair_check(x, y, out, M, P, N, Q, kChamferMaxPoints);
+    if (rc != NPCD_OK) return rc;
+    const CloudPairArgs a{x, y, x_len, y_len, out, M, P, N, Q, 0, 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (P <= 1 * kChamferThreads)
         chamfer_launch<1, 8>(a, st);

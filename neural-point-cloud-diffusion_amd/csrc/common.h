@@ -6,6 +6,7 @@
 #include <atomic>
 
 #include "../../include/npcd_hip.h"
+#include "wave.h"
 
 namespace npcd {
 

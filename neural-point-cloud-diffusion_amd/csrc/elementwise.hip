@@ -24,24 +24,6 @@ namespace npcd {
 
 constexpr int kMaxChunks = 8;  // a wave covers 256 columns per chunk -> width <= 2048
 
-// sum over the 64 lanes, on every lane, entirely on the vector ALU: four DPP row rotations (16-lane rows), v_permlane16_swap,
-// v_permlane32_swap -- no ds_bpermute (LDS crossbar) round trips.  Fixed order: bitwise reproducible.
-__device__ __forceinline__ float wave_sum(float x) {
-#ifdef NPCD_WAVE_SUM_BPERMUTE       // the previous form (A/B builds)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-#else
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128 /* row_ror:8 */, 0xf, 0xf, false));
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124 /* row_ror:4 */, 0xf, 0xf, false));
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x122 /* row_ror:2 */, 0xf, 0xf, false));
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x121 /* row_ror:1 */, 0xf, 0xf, false));
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-#endif
-}
 // the 16-bit activation type of a training run: __bf16 (bf16 autocast) or _Float16 (the reference's default --dtype, with loss scaling)
 template <class E>
 struct V {
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict
                 s += (v[ch][0] + v[ch][1]) + (v[ch][2] + v[ch][3]);
             }
         }
-        const float mu = wave_sum(s) / (float)W;
+        const float mu = wave_sum64(s) / (float)W;
         float q = 0.f;
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
@@ -122,7 +104,7 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict
                 q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
             }
         }
-        const float rs = rsqrtf(wave_sum(q) / (float)W + eps);
+        const float rs = rsqrtf(wave_sum64(q) / (float)W + eps);
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
             const int c = ch * 256 + lane * 4;
@@ -212,7 +194,7 @@ __global__ __launch_bounds__(256, 2) void ln_bwd_kernel(const D* __restrict__ dy
                 s2 += (t[0] + t[1]) + (t[2] + t[3]);
             }
         }
-        const float c1 = wave_sum(s1) / (float)W, c2 = wave_sum(s2) / (float)W;
+        const float c1 = wave_sum64(s1) / (float)W, c2 = wave_sum64(s2) / (float)W;
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
             const int c = ch * 256 + lane * 4;

@@ -2,7 +2,7 @@
 // npcd/eval/shapes.py (MMD-EMD / COV-EMD / 1-NNA-EMD), the approximate matching of Fan et al. with its fixed trip count.
 //
 //   X [M, P, 3], Y [N, Q, 3] fp32;  Lx = clamp(x_len[i], 1, P) (P when NULL), Ly = clamp(y_len[j], 1, Q) (Q when NULL), T = max(Lx, Ly)
-//   d(l, k) = ((dx dx + dy dy) + dz dz) on direct differences (fp32, as written: this file is compiled without FMA contraction)
+//   d(l, k) = ((dx dx + dy dy) + dz dz) on direct differences (cloud_sqdist of clouds.h: fp32, as written, no FMA contraction)
 //   remainL[l] = T / Lx, remainR[k] = T / Ly, cost = 0; for level in -4^7, -4^6 ... -4^0, -4^-1, 0:
 //     e(l, k)   = exp(level d(l, k))
 //     ratioL[l] = remainL[l] / (1e-9 + sum_k e(l, k) remainR[k])                          pass A, rows
@@ -23,60 +23,24 @@
 // Sums: a row sum or a column sum is ONE accumulator in the owner lane, the walked points in ascending index, e times the weight
 // fused into the addition (one rounding); it never crosses lanes.  The row's factor ratioL is applied once to the finished row sums
 // of pass C.  cost is one accumulator per lane over the levels and the lane's rows in ascending order; it crosses lanes once per pair:
-// a fixed tree over the wave, then the four waves in ascending order.  No atomics: the same bits on every run.
+// a fixed tree over the wave (wave_sum_tree of wave.h), then the four waves in ascending order.  No atomics: the same bits on every run.
 // exp is v_exp_f32 on the level pre-multiplied by log2(e), sqrt is v_sqrt_f32.
 //
 // Tails: both clouds are staged whole, every row of the instantiation, through min(row, L - 1): rows at or after the length are
 // copies of the last valid row and carry weight 0 for ever (remainL = ratioL = 0, remainR = ratioR = 0), so walking them to the next
 // multiple of four adds exact zeros.  No read leaves the arrays whatever the lengths hold.  X and Y are only read and may be the same
 // pointer.
-#include "common.h"
+#include "clouds.h"
 
 namespace npcd {
 
-constexpr int kEmdThreads = 256, kEmdWaves = kEmdThreads / kWave;
+constexpr int kEmdThreads = kCloudPairThreads, kEmdWaves = kEmdThreads / kWave;
 constexpr int kEmdMaxPoints = 8 * kEmdThreads;              // the largest instantiation
-constexpr int kEmdMaxClouds = 16384;                        // M and N
-constexpr int kEmdChunk = 32;                               // Y clouds per workgroup, at most
-constexpr int kEmdFill = 2048;                              // the chunk shrinks until the grid has this many workgroups
 constexpr int kEmdLevels = 10;
-// the grid is one-dimensional: the largest one stays below 2^32 threads
-static_assert((int64_t)kEmdMaxClouds * (kEmdMaxClouds / kEmdChunk) * kEmdThreads < (int64_t)1 << 32, "grid too large");
 
 // dynamic LDS of emd_kernel<PPL, QPL>: both clouds as 12-byte rows, ratioL per X row, remainR and ratioR per Y row
 constexpr size_t emd_lds_bytes(int ppl, int qpl) { return (size_t)kEmdThreads * (16 * ppl + 20 * qpl); }
 static_assert(emd_lds_bytes(8, 8) + 64 <= 160 * 1024, "the largest pair does not fit the LDS of a compute unit");
-
-struct EmdArgs {
-    const float *x, *y;              // [M, P, 3], [N, Q, 3]
-    const int32_t *x_len, *y_len;    // [M], [N], either may be NULL
-    float* out;                      // [M, N]
-    int M, P, N, Q;
-    int chunk, nchunks;              // Y clouds per workgroup, workgroups per X cloud
-};
-
-__device__ __forceinline__ float emd_d(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float emd_dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWMASK, 0xf, false));
-}
-
-// sum over the wave in one fixed tree, wave-uniform (the tree of chamfer.hip)
-__device__ __forceinline__ float emd_wave_sum(float v) {
-    v = emd_dpp_add<0x111, 0xf>(v);
-    v = emd_dpp_add<0x112, 0xf>(v);
-    v = emd_dpp_add<0x114, 0xf>(v);
-    v = emd_dpp_add<0x118, 0xf>(v);
-    v = emd_dpp_add<0x142, 0xa>(v);
-    v = emd_dpp_add<0x143, 0xc>(v);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-__device__ __forceinline__ int emd_len(const int32_t* len, int i, int full) { return len ? min(max(len[i], 1), full) : full; }
 
 // a cloud of L valid rows into its LDS image of ROWS rows: row r is row min(r, L - 1) of the cloud
 template <int ROWS>
@@ -115,10 +79,10 @@ __device__ __forceinline__ void emd_walk(const float* __restrict__ mine, const f
 #pragma unroll
                 for (int o = 0; o < BLK; ++o) {
                     if (o0 + o < groups) {
-                        const float d0 = emd_d(px[o], py[o], pz[o], u[0], u[1], u[2]);
-                        const float d1 = emd_d(px[o], py[o], pz[o], u[3], v[0], v[1]);
-                        const float d2 = emd_d(px[o], py[o], pz[o], v[2], v[3], w[0]);
-                        const float d3 = emd_d(px[o], py[o], pz[o], w[1], w[2], w[3]);
+                        const float d0 = cloud_sqdist(px[o], py[o], pz[o], u[0], u[1], u[2]);
+                        const float d1 = cloud_sqdist(px[o], py[o], pz[o], u[3], v[0], v[1]);
+                        const float d2 = cloud_sqdist(px[o], py[o], pz[o], v[2], v[3], w[0]);
+                        const float d3 = cloud_sqdist(px[o], py[o], pz[o], w[1], w[2], w[3]);
                         const float e0 = __builtin_amdgcn_exp2f(lvl * d0), e1 = __builtin_amdgcn_exp2f(lvl * d1);
                         const float e2 = __builtin_amdgcn_exp2f(lvl * d2), e3 = __builtin_amdgcn_exp2f(lvl * d3);
                         if (COST) {
@@ -144,7 +108,7 @@ __device__ __forceinline__ void emd_walk(const float* __restrict__ mine, const f
 }
 
 template <int PPL, int QPL>
-__global__ __launch_bounds__(kEmdThreads) void emd_kernel(EmdArgs a) {
+__global__ __launch_bounds__(kEmdThreads) void emd_kernel(CloudPairArgs a) {
     constexpr int XR = PPL * kEmdThreads, YR = QPL * kEmdThreads;
     // the pair's images, emd_lds_bytes(PPL, QPL) of dynamic LDS; every part is a multiple of 1 KiB long
     extern __shared__ __attribute__((aligned(16))) float emd_lds[];
@@ -157,12 +121,12 @@ __global__ __launch_bounds__(kEmdThreads) void emd_kernel(EmdArgs a) {
     const int tid = threadIdx.x;
     const int i = blockIdx.x / a.nchunks, chunk = blockIdx.x - i * a.nchunks;          // i < M by the grid's size
     const int j0 = chunk * a.chunk, j1 = min(j0 + a.chunk, a.N);                       // j0 < N by the grid's size
-    const int Lx = emd_len(a.x_len, i, a.P);
+    const int Lx = cloud_len(a.x_len, i, a.P);
     const int xgroups = (Lx + kEmdThreads - 1) / kEmdThreads, x4 = (Lx + 3) >> 2;
     emd_stage<XR>(xs, a.x + (int64_t)i * a.P * 3, Lx, tid);
 
     for (int j = j0; j < j1; ++j) {
-        const int Ly = emd_len(a.y_len, j, a.Q);
+        const int Ly = cloud_len(a.y_len, j, a.Q);
         const int ygroups = (Ly + kEmdThreads - 1) / kEmdThreads, y4 = (Ly + 3) >> 2;
         const float T = (float)max(Lx, Ly);
         // behind the barrier at the end of the pair before: nobody reads ys, remr or ratr any more
@@ -207,7 +171,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_kernel(EmdArgs a) {
             // which was last read in pass B, behind the barrier above
         }
 
-        cost = emd_wave_sum(cost);
+        cost = wave_sum_tree(cost);
         if ((tid & (kWave - 1)) == 0) part[tid / kWave] = cost;
         __syncthreads();          // the partials are visible; every lane is done with this pair's ys, remr and ratr
         if (tid == 0) {
@@ -221,21 +185,18 @@ __global__ __launch_bounds__(kEmdThreads) void emd_kernel(EmdArgs a) {
 }
 
 template <int PPL, int QPL>
-static int emd_launch(EmdArgs a, hipStream_t st) {
+static int emd_launch(CloudPairArgs a, hipStream_t st) {
     static DynLds attr;
     const size_t lds = emd_lds_bytes(PPL, QPL);
     NPCD_HIP_CHECK(attr.ensure(reinterpret_cast<const void*>(emd_kernel<PPL, QPL>), lds));
-    int chunk = kEmdChunk;
-    while (chunk > 1 && (int64_t)a.M * ((a.N + chunk - 1) / chunk) < kEmdFill) chunk /= 2;
-    a.chunk = chunk;
-    a.nchunks = (a.N + chunk - 1) / chunk;
+    cloud_pair_chunks(a.M, a.N, &a.chunk, &a.nchunks);
     hipLaunchKernelGGL((emd_kernel<PPL, QPL>), dim3((unsigned)((int64_t)a.M * a.nchunks)), dim3(kEmdThreads), lds, st, a);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
 
 template <int PPL>
-static int emd_launch_q(const EmdArgs& a, hipStream_t st) {
+static int emd_launch_q(const CloudPairArgs& a, hipStream_t st) {
     if (a.Q <= 1 * kEmdThreads) return emd_launch<PPL, 1>(a, st);
     if (a.Q <= 2 * kEmdThreads) return emd_launch<PPL, 2>(a, st);
     if (a.Q <= 4 * kEmdThreads) return emd_launch<PPL, 4>(a, st);
@@ -250,10 +211,9 @@ extern "C" int npcd_emd_max_points(void) { return kEmdMaxPoints; }
 
 extern "C" int npcd_emd_directed(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, float* out, int M, int P, int N,
                                  int Q, void* stream) {
-    if (M <= 0 || N <= 0 || P <= 0 || Q <= 0 || P > kEmdMaxPoints || Q > kEmdMaxPoints || M > kEmdMaxClouds || N > kEmdMaxClouds)
-        return NPCD_ERR_UNSUPPORTED;
-    if (!x || !y || !out) return NPCD_ERR_ARG;
-    const EmdArgs a{x, y, x_len, y_len, out, M, P, N, Q, 0, 0};
+    const int rc = cloud_pair_check(x, y, out, M, P, N, Q, kEmdMaxPoints);
+    if (rc != NPCD_OK) return rc;
+    const CloudPairArgs a{x, y, x_len, y_len, out, M, P, N, Q, 0, 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (P <= 1 * kEmdThreads) return emd_launch_q<1>(a, st);
     if (P <= 2 * kEmdThreads) return emd_launch_q<2>(a, st);

@@ -3,7 +3,7 @@
 //
 //   cloud i, length L = lengths[i] (P when NULL), K = ks[i] (Kmax when NULL), start s = start[i] (0 when NULL)
 //   min_dist[p] = +inf for p < L;  pick_0 = s
-//   after pick c:  d = ((x_p - x_c)^2 + (y_p - y_c)^2) + (z_p - z_c)^2   (fp32, as written: this file is compiled without FMA contraction)
+//   after pick c:  d = ((x_p - x_c)^2 + (y_p - y_c)^2) + (z_p - z_c)^2   (fp32, as written: cloud_sqdist of clouds.h, no FMA contraction)
 //                  min_dist[p] = min(min_dist[p], d)
 //   next pick = the p < L with the largest min_dist, the LOWEST index on a tie
 //   min(K, L, Kmax) picks; the slots after them hold index -1 and point 0.0
@@ -19,12 +19,13 @@
 //              point-strided loads (a 100,000-point cloud is 1.2 MB: it stays in the XCD's 4 MiB L2).  Two instantiations: up to
 //              32 * 1024 points 32 registers of min_dist leave room for 8 points' loads in flight, above that 100 registers for 4
 // A pick: per-thread update and running best (strict > over ascending p keeps the lowest index), DPP max-reduction of the key across
-// the wave, one key per wave into a double-buffered 16-entry LDS slot, ONE barrier, then every wave reduces the 16 keys for itself
-// (nothing is broadcast back).  Buffer (k & 1) is written again at pick k + 2, i.e. after barrier k + 1, which no wave passes before
-// every wave has finished reading at pick k.  The winner's coordinates are read from global memory (wave-uniform, L2).
+// the wave (wave_max_u64 of wave.h), one key per wave into a double-buffered 16-entry LDS slot, ONE barrier, then every wave reduces
+// the 16 keys for itself (nothing is broadcast back).  Buffer (k & 1) is written again at pick k + 2, i.e. after barrier k + 1, which
+// no wave passes before every wave has finished reading at pick k.  The winner's coordinates are read from global memory
+// (wave-uniform, L2).
 // Inputs are assumed finite (not checked).  lengths and start are clamped to [0, P] and [0, L) so that no value of theirs can make
 // the kernel read outside the cloud.
-#include "common.h"
+#include "clouds.h"
 
 namespace npcd {
 
@@ -42,38 +43,6 @@ struct FpsArgs {
 };
 
 __device__ __forceinline__ uint64_t fps_key(float md, uint32_t p) { return ((uint64_t)__float_as_uint(md) << 32) | (0xFFFFFFFFu - p); }
-
-// max(v, the lane that `ctrl` names); lanes without a source, or outside row_mask, keep v (identity 0)
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ uint64_t fps_dpp_max(uint64_t v) {
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROWMASK, 0xf, false);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROWMASK, 0xf, false);
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
-    return o > v ? o : v;
-}
-
-// maximum over the 16 lanes of each row, in the row's lane 15 (row_shr:1,2,4,8)
-__device__ __forceinline__ uint64_t fps_row_max(uint64_t v) {
-    v = fps_dpp_max<0x111, 0xf>(v);
-    v = fps_dpp_max<0x112, 0xf>(v);
-    v = fps_dpp_max<0x114, 0xf>(v);
-    v = fps_dpp_max<0x118, 0xf>(v);
-    return v;
-}
-
-__device__ __forceinline__ uint64_t fps_read_lane(uint64_t v, int lane) {
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// maximum over the wave, wave-uniform: rows, then row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3, lane 63
-__device__ __forceinline__ uint64_t fps_wave_max(uint64_t v) {
-    v = fps_row_max(v);
-    v = fps_dpp_max<0x142, 0xa>(v);
-    v = fps_dpp_max<0x143, 0xc>(v);
-    return fps_read_lane(v, 63);
-}
 
 // a thread owns kOwned points: with their coordinates (STREAM = false), or min_dist only, the coordinates read kFpsChunk points at a
 // time at every pick (STREAM = true)
@@ -130,8 +99,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(FpsArgs a) {
                 if (j0 * kFpsThreads < L) {          // workgroup-uniform
 #pragma unroll
                     for (int j = j0; j < j0 + kFpsChunk; ++j) {
-                        const float dx = px[j] - cx, dy = py[j] - cy, dz = pz[j] - cz;
-                        const float d = (dx * dx + dy * dy) + dz * dz;
+                        const float d = cloud_sqdist(px[j], py[j], pz[j], cx, cy, cz);
                         md[j] = fminf(md[j], d);
                         if (md[j] > best) {
                             best = md[j];
@@ -165,8 +133,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(FpsArgs a) {
 #pragma unroll
                     for (int q = 0; q < kFpsChunk; ++q) {
                         const int j = j0 + q;
-                        const float dx = x[q] - cx, dy = y[q] - cy, dz = z[q] - cz;
-                        const float d = (dx * dx + dy * dy) + dz * dz;
+                        const float d = cloud_sqdist(x[q], y[q], z[q], cx, cy, cz);
                         md[j] = fminf(md[j], d);
                         if (md[j] > best) {
                             best = md[j];
@@ -176,12 +143,12 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(FpsArgs a) {
                 }
             }
         }
-        const uint64_t wkey = fps_wave_max(best < 0.f ? 0ull : fps_key(best, best_p));
+        const uint64_t wkey = wave_max_u64(best < 0.f ? 0ull : fps_key(best, best_p));
         int mine = tid;          // derived again at every pick (empty asm): the streaming form has no registers to keep LDS addresses in
         asm volatile("" : "+v"(mine));
         if ((mine & (kWave - 1)) == 0) slot[k & 1][mine / kWave] = wkey;
         __syncthreads();
-        const uint64_t all = fps_read_lane(fps_row_max(slot[k & 1][mine & (kFpsWaves - 1)]), 15);
+        const uint64_t all = read_lane(row_max_u64(slot[k & 1][mine & (kFpsWaves - 1)]), 15);
         // a valid point always exists here (L >= 1), so the key is never 0; the clamp keeps even a NaN-ridden cloud inside its rows
         cur = (int)min(0xFFFFFFFFu - (uint32_t)all, (uint32_t)(L - 1));
     }

@@ -1013,30 +1013,9 @@ __global__ __launch_bounds__(256) void ray_march_kernel(const float* __restrict_
 // / tree order instead of slot order: same values to a few fp32 ulps.  The depth limits leave the kernel as one (min, max) pair per
 // workgroup behind the two result words of `ws`; depth_clamp_kernel combines them (atomics on the two global words made that cache
 // line the bottleneck of the kernel: 104 us with a pair per ray, 47 / 30 / 20 us with a conditional pair per 4 / 8 / 16 rays).
-#define NPCD_DPP_F(IDENT, X, CTRL, ROWMASK) \
-    __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(IDENT), __float_as_int(X), CTRL, ROWMASK, 0xf, false))
-template <class Op>
-__device__ __forceinline__ float wave_scan_incl(float x, float ident, Op op) {
-    x = op(x, NPCD_DPP_F(ident, x, 0x111 /* row_shr:1 */, 0xf));
-    x = op(x, NPCD_DPP_F(ident, x, 0x112 /* row_shr:2 */, 0xf));
-    x = op(x, NPCD_DPP_F(ident, x, 0x114 /* row_shr:4 */, 0xf));
-    x = op(x, NPCD_DPP_F(ident, x, 0x118 /* row_shr:8 */, 0xf));
-    x = op(x, NPCD_DPP_F(ident, x, 0x142 /* row_bcast:15 */, 0xa));     // rows 1 and 3 take the total of the row before them
-    x = op(x, NPCD_DPP_F(ident, x, 0x143 /* row_bcast:31 */, 0xc));     // rows 2 and 3 take the total of rows 0-1
-    return x;
-}
+// (wave_scan_incl and wave_sum64: wave.h)
 __device__ __forceinline__ float wave_prev(float x, float first) {     // lane j gets lane j - 1's value, lane 0 gets `first`
-    return NPCD_DPP_F(first, x, 0x138 /* wave_shr:1 */, 0xf);
-}
-__device__ __forceinline__ float wave_total(float x) {                  // sum over the wave, on every lane (as csrc/elementwise.hip)
-    x += NPCD_DPP_F(0.f, x, 0x128 /* row_ror:8 */, 0xf);
-    x += NPCD_DPP_F(0.f, x, 0x124, 0xf);
-    x += NPCD_DPP_F(0.f, x, 0x122, 0xf);
-    x += NPCD_DPP_F(0.f, x, 0x121, 0xf);
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+    return dpp_mov<0x138 /* wave_shr:1 */, 0xf>(first, x);
 }
 #ifndef NPCD_MARCH_RAYS
 #define NPCD_MARCH_RAYS 1
@@ -1115,8 +1094,8 @@ __global__ __launch_bounds__(256) void ray_march_wave_kernel(const float* __rest
         const float alpha = step ? 1.f - expf(-(ps * (dj - pd))) : 0.f;
         const float prod = wave_scan_incl(step ? (1.f - alpha + 1e-10f) : 1.f, 1.f, [](float a, float b2) { return a * b2; });
         const float w = alpha * wave_prev(prod, 1.f);
-        const float total = wave_total(w), wd = wave_total(w * pd);
-        const float cr = wave_total(pv ? w * pr : 0.f), cg = wave_total(pv ? w * pg : 0.f), cb = wave_total(pv ? w * pb : 0.f);
+        const float total = wave_sum64(w), wd = wave_sum64(w * pd);
+        const float cr = wave_sum64(pv ? w * pr : 0.f), cg = wave_sum64(pv ? w * pg : 0.f), cb = wave_sum64(pv ? w * pb : 0.f);
         if (in) { dmin = fminf(dmin, dj); dmax = fmaxf(dmax, dj); any = true; }
         if (lane == 0) {
             mask[ray] = total;

@@ -1,10 +1,10 @@
-"""Argument preparation shared by the all-pairs cloud distances (npcd/hip/chamfer.py, npcd/hip/emd.py): the same checks, the same
-messages but for the operator's name."""
-from typing import Sequence, Union
+"""What the all-pairs cloud distances share (npcd/hip/chamfer.py, npcd/hip/emd.py): the argument preparation -- the same checks, the
+same messages but for the operator's name -- and the operator pair itself, `directed` and `matrix` on one C entry point."""
+from typing import Callable, Sequence, Union
 
 import torch
 
-from . import require_gpu
+from . import check, lib, ptr, require_gpu, stream_ptr
 
 IntList = Union[int, Sequence[int], torch.Tensor]
 
@@ -70,3 +70,30 @@ def prepare(x, y, x_lengths, y_lengths, op: str, title: str, limit):
     if y.device != dev:
         raise RuntimeError(f"{op}: x is on {dev}, y on {y.device}")
     return x, y.detach().contiguous(), d_xl, device_i32(yl, dev)
+
+
+def pair(op: str, title: str, max_points_symbol: str, directed_symbol: str, combine: Callable):
+    """-> (max_points, directed, matrix) of one distance: `directed(x, y, x_lengths, y_lengths)` is one launch of the library's
+    `directed_symbol`, `matrix` is combine(directed(x, y), directed(y, x).T), one launch when y is None."""
+    def max_points() -> int:
+        """Largest P (and Q) supported."""
+        return getattr(lib(), max_points_symbol)()
+
+    def launch(x, x_len, y, y_len):
+        out = torch.empty((x.shape[0], y.shape[0]), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            check(getattr(lib(), directed_symbol)(ptr(x), ptr(x_len), ptr(y), ptr(y_len), ptr(out), x.shape[0], x.shape[1], y.shape[0],
+                                                  y.shape[1], stream_ptr()), directed_symbol)
+        return out
+
+    def directed(x, y, x_lengths, y_lengths):
+        x, y, xl, yl = prepare(x, y, x_lengths, y_lengths, op, title, max_points)
+        return launch(x, xl, y, yl)
+
+    def matrix(x, y, x_lengths, y_lengths):
+        self_matrix = y is None
+        x, y, xl, yl = prepare(x, y, x_lengths, y_lengths, op, title, max_points)
+        d = launch(x, xl, y, yl)
+        return combine(d, (d if self_matrix else launch(y, yl, x, xl)).t())
+
+    return max_points, directed, matrix

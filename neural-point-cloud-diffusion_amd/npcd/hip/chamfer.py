@@ -8,25 +8,9 @@ from typing import Optional
 
 import torch
 
-from . import check, lib, ptr, stream_ptr
-from ._clouds import IntList, prepare
+from ._clouds import IntList, pair
 
-
-def max_points() -> int:
-    """Largest P (and Q) supported."""
-    return lib().npcd_chamfer_max_points()
-
-
-def _prepare(x, y, x_lengths, y_lengths):
-    return prepare(x, y, x_lengths, y_lengths, "chamfer", "Chamfer distance", max_points)
-
-
-def _directed(x, x_len, y, y_len):
-    out = torch.empty((x.shape[0], y.shape[0]), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib().npcd_chamfer_directed(ptr(x), ptr(x_len), ptr(y), ptr(y_len), ptr(out), x.shape[0], x.shape[1], y.shape[0],
-                                          y.shape[1], stream_ptr()), "npcd_chamfer_directed")
-    return out
+max_points, _directed, _matrix = pair("chamfer", "Chamfer distance", "npcd_chamfer_max_points", "npcd_chamfer_directed", lambda a, b: a + b)
 
 
 def chamfer_directed(x: torch.Tensor, y: Optional[torch.Tensor] = None, x_lengths: Optional[IntList] = None,
@@ -38,15 +22,11 @@ def chamfer_directed(x: torch.Tensor, y: Optional[torch.Tensor] = None, x_length
     sum over a cloud's points has one fixed order.  x_lengths / y_lengths: valid points per cloud (default all).  Given on the host
     (an int, a list, a CPU tensor) they are checked here, 1 <= length <= P; given as GPU tensors they are never read back -- the call
     waits for nothing -- and the kernel clamps them to [1, P] instead."""
-    x, y, xl, yl = _prepare(x, y, x_lengths, y_lengths)
-    return _directed(x, xl, y, yl)
+    return _directed(x, y, x_lengths, y_lengths)
 
 
 def chamfer_matrix(x: torch.Tensor, y: Optional[torch.Tensor] = None, x_lengths: Optional[IntList] = None,
                    y_lengths: Optional[IntList] = None) -> torch.Tensor:
     """-> [M, N] fp32, the symmetric Chamfer distance CD(x_i, y_j) = directed(x, y)[i, j] + directed(y, x)[j, i].  With y = None
     one launch, D + D.T, exactly symmetric with an exactly zero diagonal.  Arguments as for `chamfer_directed`."""
-    self_matrix = y is None
-    x, y, xl, yl = _prepare(x, y, x_lengths, y_lengths)
-    d = _directed(x, xl, y, yl)
-    return d + (d if self_matrix else _directed(y, yl, x, xl)).t()
+    return _matrix(x, y, x_lengths, y_lengths)

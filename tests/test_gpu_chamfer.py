@@ -74,7 +74,7 @@ def test_x_clouds_per_workgroup_edges(P, M):
 
 @pytest.mark.parametrize("M, N, P", [(520, 131, 8), (1024, 67, 4), (16384, 33, 2)])
 def test_y_chunk_edges(M, N, P):
-    """The launch gives a workgroup up to kChamferChunk = 32 Y clouds, halved until the grid has kChamferFill = 2,048 workgroups: here
+    """The launch gives a workgroup up to kCloudPairChunk = 32 Y clouds, halved until the grid has kCloudPairFill = 2,048 workgroups: here
     2, 4 and 32, and N is one more than a multiple so that the last workgroup of a row walks one cloud.  M = 16,384 is the number of
     clouds the launch geometry has to allow at least."""
     _check_directed(_clouds(M, P, M), _clouds(N, P, N), what="Y chunk")
