@@ -437,12 +437,19 @@ int npcd_adamw_ema_gated(float* p, float* g, float* m, float* v, float* ema, voi
  * reproducible.  NPCD_ERR_UNSUPPORTED for other shapes (the caller then uses the library). */
 int npcd_wgrad_slices(int T, int N, int K);
 int npcd_wgrad(const void* dy, const void* x, float* out, float* workspace, int T, int N, int K, int dtype, void* stream);
-/* (ABI 9) `count` (1..8) such weight gradients over the SAME token range in one launch: dW_g [N_g, K_g] = dy_g[T, N_g]^T x_g[T, K_g].
+/* (ABI 9) `count` (1..16; 1..8 before the multi-block launch) such weight gradients over the SAME token range in one launch: dW_g [N_g, K_g] = dy_g[T, N_g]^T x_g[T, K_g].
  * One workgroup per 256 x 256 output tile over all T tokens: no slices, no workspace, one fixed summation order.  Meant for the token
  * count of one rank of the strong-scaling job (T = 4,104: the four Linear layers of a block are 192 tiles = one round on 192 of 256
- * CUs, beside the backward's critical path on another stream).  dy / x / out / N / K: host arrays of `count` entries. */
+ * CUs, beside the backward's critical path on another stream) and for the four Linear layers of FOUR blocks at the token count of a
+ * whole batch (T = 32,832: 768 tiles = three full rounds of 256 CUs).  dy / x / out / N / K: host arrays of `count` entries; the
+ * `out` pointers must differ (NPCD_ERR_ARG otherwise, as for count > 16). */
 int npcd_wgrad_group(int count, const void* const* dy, const void* const* x, float* const* out, const int* N, const int* K, int T,
                      int dtype, void* stream);
+/* How many residual blocks of `tiles_per_block` output tiles (256 x 256) and `products_per_block` products each belong into one
+ * npcd_wgrad_group launch: the smallest G >= 1 with G * products_per_block <= min(max_products, 16) whose G * tiles_per_block
+ * workgroups fill whole rounds of the current device's compute units (hipDeviceGetAttribute) to at least 0.95; 0 when no G does or
+ * no device answers.  256 CUs: 192 tiles (width 1,024) -> 4, 768 tiles (width 2,048) -> 1, 48 tiles (width 512) -> 0. */
+int npcd_wgrad_group_blocks(int tiles_per_block, int max_products, int products_per_block);
 
 /* Linear layers of the residual block as own NT products with fused epilogues (csrc/gemm_nt.hip): 16-bit `dtype` operands
  * (NPCD_BF16 / NPCD_F16), fp32 accumulation, 16-bit outputs; x [M, K], w [N, K] row-major (the nn.Linear weight as stored), any

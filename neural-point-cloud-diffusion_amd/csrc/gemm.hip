@@ -17,6 +17,13 @@
 // at parity with the library, not ahead; it is an opt-in (NPCD_OWN_WGRAD=1) that makes the weight gradients bitwise reproducible
 // without a library dependency.
 //
+// Round 18, the unsliced form on the full chip (wgrad_group_kernel with 16 products, tools/probes/gpu_dev_wgrad_multiblock.py): the
+// four products of FOUR blocks are 768 tiles = three rounds of 256 CUs, one workgroup per tile over all 32,832 tokens (1,026 ring
+// stages), no slabs and no sum pass.  Measured on cold, rotating operands: 2.83 ms per launch = 707 us per block (1.17 PF/s) against
+// 870 us for the library's sliced products + slab sums and 841 us for one 192-tile launch per block; inside the training step the
+// launch averages 3.09 ms = 773 us per block against 874 us (docs/experiments.md R18.1).  That is the default of the fused backbone
+// from 20,000 token rows on.  The L2 hit rate of this form has not been measured.
+//
 // Structure:
 //   * workgroup = 8 waves = one 256 x 256 output tile over ONE slice of the token range (split-T: tiles x slices ~ 256 workgroups,
 //     one per CU); every slice writes its own fp32 slab, npcd_wgrad_reduce adds the slabs in slice order (bitwise reproducible, no
@@ -231,7 +238,10 @@ __global__ __launch_bounds__(512, 2) void wgrad_kernel(WgradParams p) {
 // one rank of the 8-GPU job): every 256 x 256 output tile of every product is ONE workgroup over the whole token range -- no slices,
 // no slabs, no second kernel, one fixed summation order per element.  4,104 tokens x (3072 + 1024 + 4096 + 1024) x 1024: 192 tiles,
 // i.e. one round on 192 of the 256 CUs; the launch runs on a side stream beside the backward's critical path, which takes the rest.
-constexpr int kWgradGroupMax = 8;
+// Up to 16 products: at the token count of a whole batch (T = 32,832) the four products of FOUR blocks are 768 tiles = three full
+// rounds of 256 CUs in one launch on the main stream (npcd_wgrad_group_blocks says how many blocks fill the chip).  The tile order is
+// product-major with k fastest inside a product, so the contiguous run of tiles xcd_remap hands an XCD shares dy panels and x.
+constexpr int kWgradGroupMax = 16;
 struct WgradGroup {
     const void* dy[kWgradGroupMax];
     const void* x[kWgradGroupMax];
@@ -314,9 +324,10 @@ extern "C" int npcd_wgrad(const void* dy, const void* x, float* out, float* work
     return NPCD_OK;
 }
 
-// count (<= 8) weight gradients dW_g [N_g, K_g] fp32 = dy_g[T, N_g]^T x_g[T, K_g] over one token range in ONE launch: one workgroup per
+// count (<= 16) weight gradients dW_g [N_g, K_g] fp32 = dy_g[T, N_g]^T x_g[T, K_g] over one token range in ONE launch: one workgroup per
 // 256 x 256 output tile over all T tokens (no slices, no workspace); meant for token counts of a few thousand, where the tiles of all
-// products together are about one round of the chip.  Same shape rules as npcd_wgrad per product.
+// products together are whole rounds of the chip (npcd_wgrad_group_blocks).  Same shape rules as npcd_wgrad per product; every product
+// writes its own output (two products with one `out` would be two workgroups storing to the same tile: NPCD_ERR_ARG).
 extern "C" int npcd_wgrad_group(int count, const void* const* dy, const void* const* x, float* const* out, const int* N, const int* K, int T,
                                 int dtype, void* stream) {
     if (count < 1 || count > kWgradGroupMax || !dy || !x || !out || !N || !K || T <= 0) return NPCD_ERR_ARG;
@@ -328,6 +339,8 @@ extern "C" int npcd_wgrad_group(int count, const void* const* dy, const void* co
         if (!dy[g] || !x[g] || !out[g] || N[g] <= 0 || K[g] <= 0) return NPCD_ERR_ARG;
         if (N[g] % 256 || K[g] % 256) return NPCD_ERR_UNSUPPORTED;
         if ((reinterpret_cast<uintptr_t>(dy[g]) & 15) || (reinterpret_cast<uintptr_t>(x[g]) & 15) || (reinterpret_cast<uintptr_t>(out[g]) & 15)) return NPCD_ERR_ARG;
+        for (int h = 0; h < g; ++h)
+            if (out[h] == out[g]) return NPCD_ERR_ARG;
         gp.dy[g] = dy[g]; gp.x[g] = x[g]; gp.out[g] = out[g]; gp.N[g] = N[g]; gp.K[g] = K[g];
         gp.first[g] = tiles;
         tiles += (N[g] / 256) * (K[g] / 256);
@@ -344,4 +357,24 @@ extern "C" int npcd_wgrad_group(int count, const void* const* dy, const void* co
     }
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
+}
+
+// How many residual blocks to put into one npcd_wgrad_group launch: the smallest G >= 1 with G * products_per_block <= max_products
+// whose G * tiles_per_block workgroups (one per 256 x 256 tile, one per CU at a time) fill whole rounds of the device's CUs to at
+// least 0.95; 0 when no G does (the caller keeps its per-product path).  Width 1,024: 192 tiles per block -> 4 on 256 CUs (768 tiles,
+// three full rounds); width 2,048: 768 tiles -> 1.
+static int wgrad_group_blocks_rule(int tiles_per_block, int max_products, int products_per_block, int cus) {
+    if (tiles_per_block <= 0 || products_per_block <= 0 || cus <= 0) return 0;
+    for (int G = 1; G * products_per_block <= max_products; ++G) {
+        const int64_t tiles = (int64_t)G * tiles_per_block, rounds = (tiles + cus - 1) / cus;
+        if (tiles * 100 >= rounds * cus * 95) return G;
+    }
+    return 0;
+}
+
+extern "C" int npcd_wgrad_group_blocks(int tiles_per_block, int max_products, int products_per_block) {
+    if (max_products > kWgradGroupMax) max_products = kWgradGroupMax;
+    int dev = 0, cus = 0;                                      // (the current device's: asked every time, the caller caches per shape)
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return wgrad_group_blocks_rule(tiles_per_block, max_products, products_per_block, cus);
 }

@@ -211,13 +211,16 @@ def wgrad(dy, x, out):
     return True
 
 
+WGRAD_GROUP_MAX = 16          # kWgradGroupMax of csrc/gemm.hip
+
+
 def wgrad_group(triples):
-    """[(dy [T, N_g], x [T, K_g], out [N_g, K_g] fp32), ...] (<= 8, one T and one 16-bit dtype): all weight gradients in ONE launch of the
-    own kernel, one workgroup per 256 x 256 tile over the whole token range (csrc/gemm.hip, npcd_wgrad_group); False if a shape is not
-    covered (the caller's per-product path then runs)."""
+    """[(dy [T, N_g], x [T, K_g], out [N_g, K_g] fp32), ...] (<= 16, one T and one 16-bit dtype, every product its own out): all weight
+    gradients in ONE launch of the own kernel, one workgroup per 256 x 256 tile over the whole token range (csrc/gemm.hip,
+    npcd_wgrad_group); False if a shape is not covered (the caller's per-product path then runs)."""
     import ctypes
     n = len(triples)
-    if not 1 <= n <= 8:
+    if not 1 <= n <= WGRAD_GROUP_MAX:
         return False
     T, dt = triples[0][0].shape[0], triples[0][0].dtype
     for dy, x, out in triples:
@@ -225,12 +228,38 @@ def wgrad_group(triples):
                 or not dy.is_contiguous() or not x.is_contiguous() or not out.is_contiguous() or out.dtype != _f32
                 or tuple(out.shape) != (dy.shape[1], x.shape[1])):
             return False
+    if len({t[2].data_ptr() for t in triples}) != n:          # two products into one output: two workgroups would store to the same tile
+        return False
     P = ctypes.c_void_p * n
     I = ctypes.c_int * n
     check(lib().npcd_wgrad_group(n, P(*[ptr(t[0]) for t in triples]), P(*[ptr(t[1]) for t in triples]), P(*[ptr(t[2]) for t in triples]),
                                  I(*[t[0].shape[1] for t in triples]), I(*[t[1].shape[1] for t in triples]), T, dtype_code(triples[0][0]), stream_ptr()),
           "npcd_wgrad_group")
     return True
+
+
+def wgrad_group_blocks_rule(tiles_per_block, max_products, products_per_block, cus):
+    """The rule of npcd_wgrad_group_blocks (csrc/gemm.hip) for a device of `cus` compute units: the smallest number of residual blocks
+    G >= 1 with G * products_per_block <= max_products whose G * tiles_per_block tiles fill whole rounds of `cus` workgroups to at
+    least 0.95, or 0 when no G does."""
+    if tiles_per_block <= 0 or products_per_block <= 0 or cus <= 0:
+        return 0
+    G = 1
+    while G * products_per_block <= max_products:
+        tiles = G * tiles_per_block
+        rounds = -(-tiles // cus)
+        if tiles * 100 >= rounds * cus * 95:
+            return G
+        G += 1
+    return 0
+
+
+def wgrad_group_blocks(shapes):
+    """[(N, K), ...] of the weight gradients of ONE residual block -> how many blocks go into one wgrad_group launch on the current
+    device (npcd_wgrad_group_blocks), 0 if no number fills the chip or a shape is not a multiple of the 256 x 256 tile."""
+    if not shapes or any(N % 256 or K % 256 for N, K in shapes):
+        return 0
+    return int(lib().npcd_wgrad_group_blocks(sum((N // 256) * (K // 256) for N, K in shapes), WGRAD_GROUP_MAX, len(shapes)))
 
 
 def sum_slices(part, out):

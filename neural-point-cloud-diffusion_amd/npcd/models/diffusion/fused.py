@@ -133,7 +133,10 @@ def _wgrad(dy, x, out):
     mlp.c_proj 308 -> 255 us.
     (Tried: the weight gradients on a second HIP stream, so that they run beside the HBM-bound GELU / LayerNorm backward
     kernels of the critical path -- 84.39 -> 84.14 ms per step on the same box, i.e. nothing: the GEMM's workgroups hold
-    every CU and the other stream's kernels are dispatched as they drain.)"""
+    every CU and the other stream's kernels are dispatched as they drain.)
+    Round 18: at T = 32,832 the four products of a block take 874 us this way inside the step (slab sums included); from
+    _WGRAD_MULTIBLOCK_MIN_T token rows on the backward sends whole groups of blocks to one ew.wgrad_group launch instead (773 us per
+    block, docs/experiments.md R18.1) and this function serves the L mod G blocks at the bottom and the fallback."""
     if _OWN_WGRAD and ew.wgrad(dy, x, out):
         return
     T = dy.shape[0]
@@ -209,6 +212,44 @@ _JOIN_PER_BLOCK = _env_on("NPCD_WGRAD_JOIN_PER_BLOCK")
 # allocated between steps (at 4,104 rows ~8 GB; the caching allocator would keep most of it anyway).  NPCD_STEP_ARENA=0: off.
 _STEP_ARENA = os.environ.get("NPCD_STEP_ARENA", "1") != "0"
 _STEP_ARENA_MAX_T = int(os.environ.get("NPCD_STEP_ARENA_MAX_T", "20000"))
+
+
+# Round 18: from _WGRAD_MULTIBLOCK_MIN_T token rows on -- where the side stream above is off and a product alone is 16-64 tiles for 256
+# CUs -- the weight gradients of G blocks are ONE launch of the grouped kernel on the main stream (csrc/gemm.hip, npcd_wgrad_group
+# with up to 16 products): at width 1,024 the four products of a block are 192 tiles of 256 x 256, four blocks 768 = three full rounds
+# of 256 CUs, one workgroup per tile over all token rows -- no token slices, no fp32 slabs, no sum pass, one fixed summation order.  G
+# comes from npcd_wgrad_group_blocks (0: no number of blocks fills the chip, the per-product path stays).  The (dy, x, out) triples of
+# a block are queued where _wgrad was called and launched behind the critical path of every G-th block, counting down from the last;
+# the L mod G blocks at the bottom keep the per-product calls.  The operands of up to G - 1 earlier blocks stay alive until their
+# launch (~1.07 GB per block at T = 32,832, width 1,024).  NPCD_WGRAD_MULTIBLOCK=0: off, =force: G = 4 whatever the fill rule says
+# (tests at small widths); NPCD_WGRAD_MULTIBLOCK_MIN_T: the threshold.  docs/experiments.md R18.1.
+def _parse_wgrad_multiblock(value):
+    """NPCD_WGRAD_MULTIBLOCK -> "on" (unset, "", "1"), "off" ("0") or "force"; anything else raises a ValueError that names the
+    variable.  Parsed once, here."""
+    modes = {None: "on", "": "on", "1": "on", "0": "off", "force": "force"}
+    if value not in modes:
+        raise ValueError(f"NPCD_WGRAD_MULTIBLOCK={value!r}: expected unset, 0 (off), 1 (on) or force (skip the fill rule)")
+    return modes[value]
+
+
+_WGRAD_MULTIBLOCK = _parse_wgrad_multiblock(os.environ.get("NPCD_WGRAD_MULTIBLOCK"))
+_WGRAD_MULTIBLOCK_MIN_T = int(os.environ.get("NPCD_WGRAD_MULTIBLOCK_MIN_T", "20000"))
+_multiblock_blocks = {}
+
+
+def _wgrad_multiblock_blocks(T, W, dtype, device):
+    """How many blocks share one grouped weight-gradient launch on the main stream at T token rows and width W; 0: none (the
+    per-product calls of _wgrad)."""
+    if (_WGRAD_MULTIBLOCK == "off" or T < _WGRAD_MULTIBLOCK_MIN_T or _wgrad_side_ok(T) or device.type != "cuda"
+            or dtype not in (torch.bfloat16, torch.float16)):
+        return 0
+    if _WGRAD_MULTIBLOCK == "force":
+        return ew.WGRAD_GROUP_MAX // len(_LINEARS)
+    key = (W, device.index)
+    if key not in _multiblock_blocks:
+        with torch.cuda.device(device):
+            _multiblock_blocks[key] = ew.wgrad_group_blocks([(3 * W, W), (W, W), (4 * W, W), (W, 4 * W)])
+    return _multiblock_blocks[key]
 
 
 def _wgrad_fork(pending, device, before=None):
@@ -569,12 +610,18 @@ class _BackboneFn(torch.autograd.Function):
                 if reducing:
                     for p in entry["params"]:
                         eng.reducer.mark_ready(p)
+            # the weight gradients of `group` blocks in one launch on the main stream (round 18): blocks [tail, L) in runs of `group`,
+            # counting down from the last; the `tail` blocks at the bottom keep the per-product calls
+            group = 0 if side else _wgrad_multiblock_blocks(T, W, eng.dtype, dx.device)
+            tail = len(eng.blocks) % group if group else len(eng.blocks)
+            queued, queued_blocks = [], []
             for bi in range(len(eng.blocks) - 1, -1, -1):
                 e = eng.blocks[bi]
                 x_cur, mean1, rstd1, y1, qkv, a, lse, x2, mean2, rstd2, y2, h, g = ctx.saved[bi]
                 ctx.saved[bi] = None
                 sums = ew.ColsumBatch()            # this block's 8 bias / LN-affine column sums: one finalize
-                wg = pending.append if side else (lambda t: _wgrad(*t))      # weight gradients: now, or queued for the side stream
+                # weight gradients: now, or queued for the side stream, or queued for the multi-block launch
+                wg = pending.append if side else queued.append if bi >= tail else (lambda t: _wgrad(*t))
                 # ---- MLP branch: x3 = x2 + c_proj(gelu(c_fc(ln_2(x2)))) ------------------------------
                 Tm = T - T % 256
                 w2 = e["mlp_c_proj_weight_16"]
@@ -642,6 +689,17 @@ class _BackboneFn(torch.autograd.Function):
                     # four products start there
                     above = eng.blocks[bi + 1] if (reducing and bi + 1 < len(eng.blocks)) else None
                     _wgrad_fork(pending, dx.device, before=None if above is None else (lambda: ready(above)))
+                elif bi >= tail:
+                    queued_blocks.append(e)
+                    if (len(eng.blocks) - bi) % group == 0:
+                        # 4 x group products, one launch; the blocks are handed on only behind it, in descending order
+                        if not ew.wgrad_group(queued):
+                            for t in queued:
+                                _wgrad(*t)
+                        queued.clear()
+                        for qe in queued_blocks:
+                            ready(qe)
+                        queued_blocks.clear()
                 else:
                     ready(e)       # this block's gradients are final (mlp.c_proj.bias was finished by the block above / the tail)
             if side:
