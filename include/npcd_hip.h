@@ -733,6 +733,25 @@ int npcd_emd_max_points(void);
 int npcd_emd_directed(const float* x, const int32_t* x_len, const float* y, const int32_t* y_len, float* out, int M, int P, int N, int Q,
                       void* stream);
 
+/* ---- occupancy grid of point clouds (csrc/occupancy.hip): the operator under the Jensen-Shannon divergence and the
+ * occupancy entropy of npcd/eval/shapes.py.  points [n, P, 3] fp32 contiguous; lengths int32 [n] on the device or NULL (P), clamped
+ * to [1, P].  lattice [R] fp32: the cell centres along an axis, ascending, the same on the three axes; cell (i, j, k) has the flat
+ * index (i R + j) R + k.  The valid cells are data: k_lo / k_hi [R * R] bytes, per column (i, j) the inclusive range of valid k,
+ * k_lo > k_hi an empty column (k_hi is read as min(k_hi, R - 1)).  Every point with finite coordinates in a row before its cloud's
+ * length goes to the valid cell whose centre is nearest (squared Euclidean distance, fp32 on direct differences; among equal
+ * distances the lowest index) and is counted:
+ *   counts [R^3] int32 += points in the cell;   clouds [R^3] int32 += clouds with at least one point in the cell;
+ *   cells [n, P] int32 or NULL, fully written: the point's cell, -1 for a row at or after the length and for a non-finite point.
+ * counts and clouds are accumulated into: the caller zeroes them, and may feed a set in several calls.  Integer atomics only: the
+ * same bits on every run.  A mask without a valid cell counts nothing.  No read leaves the arrays whatever the lengths or the mask
+ * hold.  A cloud is never split over workgroups: npcd_occupancy_clouds_per_workgroup(n, P, R) clouds go to each.
+ * NPCD_ERR_UNSUPPORTED for n or P <= 0, n P >= 2^31 and R outside [2, npcd_occupancy_max_resolution()] (32), before any pointer is
+ * looked at; NPCD_ERR_ARG for a NULL pointer other than lengths and cells.  Nothing is launched in either case. */
+int npcd_occupancy_max_resolution(void);
+int npcd_occupancy_clouds_per_workgroup(int n, int P, int R);
+int npcd_occupancy_grid(const float* points, const int32_t* lengths, const float* lattice, const uint8_t* k_lo, const uint8_t* k_hi,
+                        int32_t* counts, int32_t* clouds, int32_t* cells, int n, int P, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

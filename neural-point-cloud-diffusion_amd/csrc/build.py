@@ -52,6 +52,8 @@ SOURCES = {
     # the approximate earth mover's distance evaluates the same fp32 distance expression as written; its sums are
     # explicit fused multiply-adds.  Single operations rather than packed ones, as for chamfer.hip
     "emd.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # the occupancy grid searches the valid cells with the same fp32 distance expression as written (clouds.h)
+    "occupancy.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

@@ -9,7 +9,8 @@ from typing import Dict, Iterable, List
 
 import torch
 
-from .shapes import evaluate_shapes, metrics_from_chamfer, metrics_from_distance, normalize_clouds, shape_metrics  # noqa: F401
+from .shapes import (evaluate_shapes, jensen_shannon_divergence, jsd_from_counts, metrics_from_chamfer,  # noqa: F401
+                     metrics_from_distance, normalize_clouds, occupancy_entropy, shape_metrics)
 
 
 def psnr(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> float:

@@ -146,6 +146,9 @@ SIGNATURES = {
     "npcd_chamfer_directed": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
     "npcd_emd_max_points": (c_int, []),
     "npcd_emd_directed": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
+    "npcd_occupancy_max_resolution": (c_int, []),
+    "npcd_occupancy_clouds_per_workgroup": (c_int, [c_int, c_int, c_int]),
+    "npcd_occupancy_grid": (c_int, [_P] * 8 + [c_int] * 3 + [_P]),
 }
 
 _lib = None
