@@ -752,6 +752,35 @@ int npcd_occupancy_clouds_per_workgroup(int n, int P, int R);
 int npcd_occupancy_grid(const float* points, const int32_t* lengths, const float* lattice, const uint8_t* k_lo, const uint8_t* k_hi,
                         int32_t* counts, int32_t* clouds, int32_t* cells, int n, int P, int R, void* stream);
 
+/* ---- image metrics of rendered views (csrc/ssim.hip): the structural similarity index (SSIM) and the mean squared
+ * error under npcd.eval.ssim / psnr and the ssim= switch of evaluate_pointnerf.  pred, target: fp32 images of V views, C channels,
+ * H x W pixels, element (v, c, i, j) at v sv + c sc + i sh + j sw of its own four ELEMENT strides -- [V, C, H, W] and the renderer's
+ * pixel-interleaved [V, H, W, C] are both read in place; only read, and may be the same pointer.  taps [w] float64 on the device: a
+ * separable window, w odd in [3, 15], the taps summing to 1.  With x = pred, y = target read as float64, at each of the
+ * (H - w + 1) (W - w + 1) valid positions, where the window lies inside the image,
+ *   ux, uy, uxx, uyy, uxy = window means of x, y, x x, y y, x y with weights taps[i] taps[j];
+ *   vx = n (uxx - ux ux), vy = n (uyy - uy uy), vxy = n (uxy - ux uy);
+ *   S = (2 ux uy + C1)(2 vxy + C2) / ((ux ux + uy uy + C1)(vx + vy + C2)),  C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;
+ * all float64, evaluated as written.  Outputs, float64, fully written:
+ *   ssim [V, C] = mean of S over the valid positions;   mse [V] = mean of (x - y)^2 over all C H W pixels of the view;
+ *   map [V, C, H - w + 1, W - w + 1] or NULL = S.
+ * n = w^2 / (w^2 - 1) with uniform taps 1 / w is skimage.metrics.structural_similarity at its defaults (sample covariance), n = 1 with
+ * Gaussian taps the setting of Wang et al.  Identical images give ssim = 1 and mse = 0 exactly.  A non-finite pixel makes the mse of
+ * its view, the ssim of its (view, channel) and S at every window that holds it NaN, and touches no other view.
+ * workspace: npcd_image_metrics_workspace_bytes(V, C, H, W, w) bytes, 8-byte aligned, contents irrelevant before and after: two
+ * partial sums per tile of npcd_image_metrics_tile() = (rows, cols) valid positions of one (view, channel), added by a second small
+ * launch in a fixed order.  No float atomics: the same bits on every run, and a view's numbers do not depend on the other views of the
+ * call.  No scratch.
+ * NPCD_ERR_UNSUPPORTED (the workspace query returns it too) for V, C, H or W <= 0, H or W < w, w even or outside [3, 15] and
+ * V C H W >= 2^31, before any pointer is looked at; NPCD_ERR_ARG for a NULL pointer other than map and for data_range or n not positive
+ * and finite.  Nothing is launched in either case.  rows_host / cols_host are host pointers. */
+int npcd_image_metrics_tile(int* rows_host, int* cols_host);
+int64_t npcd_image_metrics_workspace_bytes(int V, int C, int H, int W, int w);
+int npcd_image_metrics(const float* pred, const float* target, int V, int C, int H, int W, int64_t pred_sv, int64_t pred_sc,
+                       int64_t pred_sh, int64_t pred_sw, int64_t target_sv, int64_t target_sc, int64_t target_sh, int64_t target_sw,
+                       const double* taps, int w, double n, double data_range, double* workspace, double* mse, double* ssim, double* map,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

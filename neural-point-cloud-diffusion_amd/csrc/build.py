@@ -54,6 +54,9 @@ SOURCES = {
     "emd.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # the occupancy grid searches the valid cells with the same fp32 distance expression as written (clouds.h)
     "occupancy.hip": ["-ffp-contract=off"],
+    # the image metrics evaluate their float64 expressions as written: with identical images the numerator and the denominator of
+    # SSIM are then the same bits and the index is 1 exactly
+    "ssim.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

@@ -36,6 +36,10 @@ __device__ __forceinline__ uint64_t dpp_mov(uint64_t ident, uint64_t v) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)ident, (int)(uint32_t)v, CTRL, ROWMASK, 0xf, false);
     return ((uint64_t)hi << 32) | lo;
 }
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ double dpp_mov(double ident, double v) {
+    return __builtin_bit_cast(double, dpp_mov<CTRL, ROWMASK>(__builtin_bit_cast(uint64_t, ident), __builtin_bit_cast(uint64_t, v)));
+}
 template <int CTRL, int ROWMASK, class T, class Op>
 __device__ __forceinline__ T dpp_step(T v, T ident, Op op) {
     return op(v, dpp_mov<CTRL, ROWMASK>(ident, v));
@@ -70,6 +74,11 @@ __device__ __forceinline__ uint64_t read_lane(uint64_t v, int lane) {
 // sum over the wave in that one fixed tree, wave-uniform (read from lane 63); lanes without a source, or outside the row mask, add 0
 __device__ __forceinline__ float wave_sum_tree(float v) {
     return read_lane(wave_scan_incl(v, 0.f, [](float a, float b) { return a + b; }), 63);
+}
+// the same tree on float64 (csrc/ssim.hip)
+__device__ __forceinline__ double wave_sum_tree(double v) {
+    const double s = wave_scan_incl(v, 0.0, [](double a, double b) { return a + b; });
+    return __builtin_bit_cast(double, read_lane(__builtin_bit_cast(uint64_t, s), 63));
 }
 // maximum of unsigned keys: over the 16 lanes of each row, in the row's lane 15; and over the wave, wave-uniform.  Lanes without a
 // source keep their own value: the identity is key 0

@@ -9,6 +9,7 @@ from typing import Dict, Iterable, List
 
 import torch
 
+from ..hip.image_metrics import image_metrics
 from .shapes import (evaluate_shapes, jensen_shannon_divergence, jsd_from_counts, metrics_from_chamfer,  # noqa: F401
                      metrics_from_distance, normalize_clouds, occupancy_entropy, shape_metrics)
 
@@ -26,11 +27,29 @@ def unflatten_pred(channels: torch.Tensor) -> torch.Tensor:
     return x.reshape(*x.shape[:-1], side, side)
 
 
+def ssim(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, window: str = "uniform", **kw) -> float:
+    """Structural similarity index, the mean over the views of npcd.hip.image_metrics: with window "uniform"
+    skimage.metrics.structural_similarity(..., data_range=data_range, channel_axis=...) at its defaults, with "gaussian" the setting of
+    Wang et al.  pred, target: fp32 images on the GPU, [..., C, H, W] or with layout="hwc" [..., H, W, C]; `kw` goes to image_metrics."""
+    views = image_metrics(pred, target, window=window, data_range=data_range, **kw).ssim
+    return float(views.sum() / views.numel())          # a true division: views of exactly 1 give 1
+
+
+def _psnr_of(mse: float, data_range: float = 1.0) -> float:
+    return float("inf") if mse == 0 else 10.0 * math.log10(data_range ** 2 / mse)
+
+
 @torch.no_grad()
-def evaluate_pointnerf(pointnerf, samples: Iterable[Dict[str, torch.Tensor]], eval_batch_size: int = 1, burn_in_samples: int = 3) -> Dict:
+def evaluate_pointnerf(pointnerf, samples: Iterable[Dict[str, torch.Tensor]], eval_batch_size: int = 1, burn_in_samples: int = 3,
+                       ssim: bool = False, ssim_window: str = "uniform") -> Dict:
     """samples: dicts with obj_idx [1], intrinsics [1,V,3,3], extrinsics [1,V,4,4], images [1,V,3,H,W] (one object each, like the
     reference's dataloader).  Returns {'psnr': mean over all views, 'runtime_model_in_msec': mean over the timed calls (NaN-free),
-    'views': per-view records}."""
+    'views': per-view records}.  ssim=True: every rendered batch is measured by one fused launch of npcd.hip.image_metrics on the
+    renderer's channels where they lie, outside the timed region; an object's numbers stay on the device and are read back once.
+    Every record gains 'ssim' and takes its 'psnr' from the launch's mean squared error; the result gains 'ssim' (mean over all
+    views) and 'ssim_window'."""
+    if ssim:
+        return _evaluate_pointnerf_ssim(pointnerf, samples, eval_batch_size, burn_in_samples, ssim_window)
     records: List[Dict] = []
     levels = set()
     dev = next(pointnerf.parameters()).device
@@ -54,6 +73,41 @@ def evaluate_pointnerf(pointnerf, samples: Iterable[Dict[str, torch.Tensor]], ev
     return {"psnr": sum(r["psnr"] for r in records) / max(1, len(records)),
             "runtime_model_in_msec": sum(times) / len(times) if times else float("nan"), "views": records,
             "grid_level": sorted(str(l) for l in levels)}
+
+
+def _evaluate_pointnerf_ssim(pointnerf, samples, eval_batch_size: int, burn_in_samples: int, window: str) -> Dict:
+    """evaluate_pointnerf(ssim=True): the same protocol and timing rule; the views are measured on the device."""
+    records: List[Dict] = []
+    levels = set()
+    dev = next(pointnerf.parameters()).device
+    for num, sample in enumerate(samples):
+        sample = {k: v.to(dev) for k, v in sample.items()}
+        V = sample["extrinsics"].shape[1]
+        target = sample["images"][0].permute(0, 2, 3, 1)                            # [V, H, W, 3], a view
+        measured, first = [], len(records)
+        for v0 in range(0, V, eval_batch_size):
+            sl = slice(v0, min(V, v0 + eval_batch_size))
+            torch.cuda.synchronize()
+            t0 = time.time()
+            pred, _ = pointnerf(sample["obj_idx"], sample["intrinsics"][:, sl], sample["extrinsics"][:, sl], sample_rays=False)
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+            timed = eval_batch_size == 1 and num >= burn_in_samples
+            levels.add(pred.get("grid_level"))
+            channels = pred["channels"][0]                                            # [v, R, 3]: ray r = i * res + j is pixel (i, j)
+            side = round(channels.shape[1] ** 0.5)
+            got = image_metrics(channels.unflatten(1, (side, side)), target[sl], window=window, layout="hwc")
+            measured.append(torch.stack((got.mse, got.ssim)))
+            records.extend({"sample": num, "view": v0 + j, "runtime_model_in_msec": 1000 * dt if timed else float("nan")}
+                           for j in range(channels.shape[0]))
+        mse, index = torch.cat(measured, dim=1).cpu().tolist()                      # the object's one read-back
+        for r, m, s in zip(records[first:], mse, index):
+            r["psnr"], r["ssim"] = _psnr_of(m), s
+    times = [r["runtime_model_in_msec"] for r in records if not math.isnan(r["runtime_model_in_msec"])]
+    return {"psnr": sum(r["psnr"] for r in records) / max(1, len(records)),
+            "runtime_model_in_msec": sum(times) / len(times) if times else float("nan"), "views": records,
+            "grid_level": sorted(str(l) for l in levels),
+            "ssim": sum(r["ssim"] for r in records) / max(1, len(records)), "ssim_window": window}
 
 
 # ---- generate -> render: the loop of the reference's DiffusionEvaluation (npcd/eval/diffusion_evaluation.py:146-183) ---------------

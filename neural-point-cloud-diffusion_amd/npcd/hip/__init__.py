@@ -149,6 +149,9 @@ SIGNATURES = {
     "npcd_occupancy_max_resolution": (c_int, []),
     "npcd_occupancy_clouds_per_workgroup": (c_int, [c_int, c_int, c_int]),
     "npcd_occupancy_grid": (c_int, [_P] * 8 + [c_int] * 3 + [_P]),
+    "npcd_image_metrics_tile": (c_int, [POINTER(c_int), POINTER(c_int)]),
+    "npcd_image_metrics_workspace_bytes": (c_int64, [c_int] * 5),
+    "npcd_image_metrics": (c_int, [_P, _P] + [c_int] * 4 + [c_int64] * 8 + [_P, c_int, c_double, c_double] + [_P] * 4 + [_P]),
 }
 
 _lib = None
