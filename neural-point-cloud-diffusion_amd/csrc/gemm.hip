@@ -8,7 +8,8 @@
 // 16-64 tiles of 256 x 256 for 256 CUs), both operands have the reduction index as their SLOW index, and the result must be fp32.
 // The library runs this at 0.74-0.98 PF/s (row-split batched GEMM + a sum pass; its fp32-output kernels are outside TunableOp).
 //
-// What bounds it (measured, tools/probes/gpu_dev_wgrad_own.py + diagnostic builds -DNPCD_WGRAD_DIAG=1..4, c_fc shape, T = 32,832):
+// What bounded the split-T form in round 6 (measured, tools/probes/gpu_dev_wgrad_own.py + timing-only builds without the DMA / the
+// matrix instructions / the reads, c_fc shape, T = 32,832; those switches left the file with the tile body they were written for):
 // a 256 x 256 tile streams 128 FLOP per byte through LDS whatever the split, i.e. 2.15 GB per call; the LDS-DMA stream ALONE (no
 // fragment reads, no matrix instructions) takes 170-190 us = 49 GB/s per CU, which is what 63 % L2 hits (70 GB/s per CU) and 37 %
 // misses to the Infinity Cache / HBM (30 GB/s) give (rocprofv3: TCP_TCC_READ_REQ 2.15 GB, FETCH_SIZE x 2 = 788 MB -- the minimum for
@@ -22,17 +23,32 @@
 // stages), no slabs and no sum pass.  Measured on cold, rotating operands: 2.83 ms per launch = 707 us per block (1.17 PF/s) against
 // 870 us for the library's sliced products + slab sums and 841 us for one 192-tile launch per block; inside the training step the
 // launch averages 3.09 ms = 773 us per block against 874 us (docs/experiments.md R18.1).  That is the default of the fused backbone
-// from 20,000 token rows on.  The L2 hit rate of this form has not been measured.
+// from 20,000 token rows on.
+//
+// Round 21, the tile body re-pipelined (tools/probes/gpu_dev_wgrad_pipeline.py, docs/experiments.md R21.1).  Timing-only builds of
+// the round-18 body in the 768-tile launch: matrix instructions + reads + barriers WITHOUT the in-loop DMA 667 us per block, DMA +
+// reads without matrix instructions 516 us, the DMA stream with its waits and barriers alone 440 us, everything 759 us (826 GFLOP
+// are 330 us at the 2.5 PF/s peak): the unsliced form is NOT bound by the L2 -> LDS stream; its loop lost 40 % of the matrix pipe
+// with no DMA in it at all -- a barrier and two full lgkmcnt(0) drains per 32 tokens, all eight waves in lockstep, every burst of 12
+// fragment reads issued with the pipe idle.  The body below runs 64 tokens per barrier and issues the reads of the next 16-token group
+// between the pairs of matrix instructions of the current one, each pair behind a counted lgkmcnt: 697 against 771 us per block
+// (1.19 against 1.07 PF/s, same box, alternating), every output bit the same.  Either half alone is slower than the round-18 body
+// (64 tokens per barrier with burst reads 790 against 759 us; interleaved reads on 32-token steps 775 against 759 us), s_setprio
+// around the pairs costs 5 % (773 against 733 us).  What bounds it now: still the issue stream of the loop rather than a unit -- the
+// DMA stream alone and the matrix instructions alone are each far shorter than the launch (R21.1 has the counters of both bodies).
 //
 // Structure:
 //   * workgroup = 8 waves = one 256 x 256 output tile over ONE slice of the token range (split-T: tiles x slices ~ 256 workgroups,
 //     one per CU); every slice writes its own fp32 slab, npcd_wgrad_reduce adds the slabs in slice order (bitwise reproducible, no
 //     atomics);
 //   * both operands stream as [32 tokens][64 columns] sub-tiles (128-byte rows, the XOR-swizzled image of the attention kernels)
-//     through a four-stage LDS ring by LDS-DMA (one stage read, three in flight, counted vmcnt); BOTH MFMA operands are transposed reads (ds_read_b64_tr_b16) of those row-major
-//     images -- the contraction order is the same permutation of the 16 token rows for A and B, so it drops out;
-//   * wave = 128 (N) x 64 (K) of the tile: 8 accumulators of 32 x 32, v_mfma_f32_32x32x16; the fragment reads of a stage's first
-//     half are issued right behind the barrier that says it has landed and hide behind the previous stage's second half;
+//     through a five-stage LDS ring (the CU's 160 KiB) by LDS-DMA: a step of 64 tokens = two stages is read while up to three stages
+//     are in flight, one counted vmcnt and one barrier per step (the counts are argued in wgrad_tile); BOTH MFMA operands are transposed
+//     reads (ds_read_b64_tr_b16) of those row-major images -- the contraction order is the same permutation of the 16 token rows for A
+//     and B, so it drops out;
+//   * wave = 128 (N) x 64 (K) of the tile: 8 accumulators of 32 x 32, v_mfma_f32_32x32x16, two fragment sets: the 12 reads of the
+//     next 16-token group go out between the four pairs of matrix instructions of the current one (wgrad_group16); every accumulator
+//     takes its 16-token groups in ascending token order, so the bits do not depend on the pipeline;
 //   * workgroup -> (tile, slice) mapping keeps the workgroups that read the same dy panel on one XCD (its L2 then serves the
 //     panel to all of them; x is small enough for the Infinity Cache).
 #include <type_traits>
@@ -78,39 +94,98 @@ struct WgradParams {
     int T, N, K, S;
     int tiles_n, tiles_k;
 };
-#ifndef NPCD_WGRAD_DIAG
-#define NPCD_WGRAD_DIAG 0      // DIAGNOSTIC builds (wrong results, timing only): 1 no DMA inside the loop, 2 no matrix instructions, 3 no slab stores,
-                               // 4 neither matrix instructions nor fragment reads (the DMA stream + its waits and barriers alone)
-#endif
-
 constexpr int kStage = 32768;          // one ring stage = 32 tokens: 4 dy sub-tiles + 4 x sub-tiles of [32 tokens][64 columns] = 4 KiB each
 constexpr int kSub = 4096;
-constexpr int kRing = 4;               // stages: one being read, up to three in flight
+constexpr int kRing = 5;               // stages = the CU's 160 KiB: the two of the 64-token step being read, up to three in flight
+constexpr uint32_t kRingBytes = kRing * kStage;
 
-// the 4 DMA pieces (8 rows x 128 B each) of one [32 token][64 column] sub-tile; rows past T come from a page of zeros
+// where a wave's share of a stage's DMA comes from: sub-tile `wave` (waves 0..3: dy columns n0 + 64 wave; waves 4..7: x columns
+// k0 + 64 (wave - 4)); rows from T on come from a page of zeros
 template <class E>
-__device__ __forceinline__ void dma_subtile(uint32_t lds_dst, const E* base, int64_t ld, int t0, int T, int col0, int lane, const E* zeros) {
-    const int rowin = lane >> 3;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int prow = i * 8 + rowin;
-        const int chunk = (lane & 7) ^ tile_swz(prow);
-        if (t0 + i * 8 + 8 <= T) {                                  // (wave-uniform) all eight rows exist
-            const char* sb = reinterpret_cast<const char*>(base + (int64_t)(t0 + i * 8) * ld + col0);
-            g_dma16(sb, (uint32_t)((rowin * ld + chunk * 8) * (int64_t)sizeof(E)), __builtin_amdgcn_readfirstlane(lds_dst + i * 1024));
-        } else {
-            // the ragged end of the token range: per-lane choice between the row and the zero page (64-bit per-lane address form)
-            const E* src = (t0 + prow < T) ? base + (int64_t)(t0 + prow) * ld + col0 + chunk * 8 : zeros + (lane & 7) * 8;
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_dst + i * 1024)) : "memory");
-        }
+struct DmaSrc {
+    const E* base;
+    const E* zeros;
+    int64_t ld;
+    int col0, lane, T;
+};
+
+// piece i (8 rows x 128 B) of the [32 token][64 column] sub-tile that starts at token t0: one DMA wave-instruction
+template <class E>
+__device__ __forceinline__ void dma_piece(const DmaSrc<E>& d, int i, uint32_t lds_dst, int t0) {
+    const int rowin = d.lane >> 3, prow = i * 8 + rowin;
+    const int chunk = (d.lane & 7) ^ tile_swz(prow);
+    if (t0 + i * 8 + 8 <= d.T) {                                    // (wave-uniform) all eight rows exist
+        const char* sb = reinterpret_cast<const char*>(d.base + (int64_t)(t0 + i * 8) * d.ld + d.col0);
+        g_dma16(sb, (uint32_t)((rowin * d.ld + chunk * 8) * (int64_t)sizeof(E)), __builtin_amdgcn_readfirstlane(lds_dst + i * 1024));
+    } else {
+        // the ragged end of the token range: per-lane choice between the row and the zero page (64-bit per-lane address form)
+        const E* src = (t0 + prow < d.T) ? d.base + (int64_t)(t0 + prow) * d.ld + d.col0 + chunk * 8 : d.zeros + (d.lane & 7) * 8;
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_dst + i * 1024)) : "memory");
     }
+}
+template <class E>
+__device__ __forceinline__ void dma_subtile(const DmaSrc<E>& d, uint32_t lds_dst, int t0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dma_piece<E>(d, i, lds_dst, t0);
 }
 
 __device__ unsigned char g_zero_page[128];      // (zero-initialised device memory)
 
-// (Tried: touching the 32 cache lines of a sub-tile a few stages ahead of its LDS-DMA with one plain load per wave and stage, so that
-//  the DMA finds them in the XCD's L2.  c_fc 269 -> 360 us at every distance tried (4, 6, 10 stages): vmcnt retires in order, and the
-//  far-ahead loads that miss the L2 hold the counted waits of the ring behind them.  Removed.)
+// The 12 transposed reads of one 16-token group (G16 = 0 / 1: token rows [0, 16) / [16, 32) of a stage) go out in the order the matrix
+// instructions take them -- the two B fragments, then A[0..3] -- so that a counted lgkmcnt can release each pair of matrix
+// instructions as soon as its own operands are there.  ta / tb: the lane's four fragment addresses inside the stage's first dy / its x
+// sub-tile.
+template <int G16>
+__device__ __forceinline__ void rd_b(GFrag (&fb)[2], const uint32_t (&tb)[2][2]) {
+    fb[0].lo = g_tr<G16 * 2048>(tb[0][0]); fb[0].hi = g_tr<G16 * 2048>(tb[0][1]);
+    fb[1].lo = g_tr<G16 * 2048>(tb[1][0]); fb[1].hi = g_tr<G16 * 2048>(tb[1][1]);
+}
+template <int G16, int M>
+__device__ __forceinline__ void rd_a(GFrag (&fa)[4], const uint32_t (&ta)[2][2]) {
+    fa[M].lo = g_tr<(M >> 1) * kSub + G16 * 2048>(ta[M & 1][0]);
+    fa[M].hi = g_tr<(M >> 1) * kSub + G16 * 2048>(ta[M & 1][1]);
+}
+#define NPCD_G_LGKM(N)                                           \
+    do {                                                         \
+        asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); \
+        __builtin_amdgcn_sched_barrier(0);                       \
+    } while (0)
+// Rows 32 M .. 32 M + 31 of the wave's tile take one 16-token group: two matrix instructions, behind a wait for at most WAIT outstanding
+// LDS operations (WAIT < 0: none).  A matrix instruction touches no memory, so neither a memory clobber nor the order of the source
+// keeps it behind the wait that covers its operands; what does is a data dependence: the wait (an asm volatile statement, ordered with
+// every read and every other wait) takes the two accumulators as read-write operands, and so does an empty statement behind the pair,
+// which keeps the pair in front of the reads that follow it in the source.
+template <class TR, int M, int WAIT>
+__device__ __forceinline__ void mma_pair(f32x16 (&acc)[4][2], const GFrag (&ca)[4], const GFrag (&cb)[2]) {
+    if (WAIT >= 0) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(acc[M][0]), "+v"(acc[M][1]) : "n"(WAIT < 0 ? 0 : WAIT) : "memory");
+    else asm volatile("" : "+v"(acc[M][0]), "+v"(acc[M][1]));
+    acc[M][0] = TR::mfma32(g_vec<TR>(ca[M]), g_vec<TR>(cb[0]), acc[M][0]);
+    acc[M][1] = TR::mfma32(g_vec<TR>(ca[M]), g_vec<TR>(cb[1]), acc[M][1]);
+    asm volatile("" : "+v"(acc[M][0]), "+v"(acc[M][1]));
+}
+// One 16-token group of the wave: its 8 matrix instructions from (ca, cb) while the 12 reads of the NEXT group (half G16N of the stage
+// ta / tb point into) go out into (na, nb) between the pairs, and -- DMA, when `dma` -- the four pieces of one stage's sub-tile.
+// OWN: the 12 reads of (ca, cb) are the youngest LDS operations of the wave and may all be outstanding on entry; each pair then waits
+// for its own operands only: outstanding <= (own reads behind the ones it needs) + (reads of the next group issued so far).  Not OWN:
+// the caller has waited lgkmcnt(0).  The waits are correct because LDS operations return in issue order and every one of them in this
+// loop is an asm volatile statement (issue order = source order); mma_pair ties each pair to its wait.
+template <class TR, int G16N, bool OWN, bool DMA, class E>
+__device__ __forceinline__ void wgrad_group16(f32x16 (&acc)[4][2], const GFrag (&ca)[4], const GFrag (&cb)[2], GFrag (&na)[4], GFrag (&nb)[2],
+                                              const uint32_t (&ta)[2][2], const uint32_t (&tb)[2][2], const DmaSrc<E>& d, bool dma,
+                                              uint32_t dma_dst, int dma_t0) {
+    mma_pair<TR, 0, OWN ? 6 : -1>(acc, ca, cb);       // B[0], B[1], A[0] of this group: the first 6 of its 12
+    rd_b<G16N>(nb, tb);                               // + 4 of the next group
+    if (DMA && dma) dma_piece<E>(d, 0, dma_dst, dma_t0);
+    mma_pair<TR, 1, OWN ? 8 : -1>(acc, ca, cb);       // A[1]: behind it A[2], A[3] (4) + 4
+    rd_a<G16N, 0>(na, ta); rd_a<G16N, 1>(na, ta);
+    if (DMA && dma) dma_piece<E>(d, 1, dma_dst, dma_t0);
+    mma_pair<TR, 2, OWN ? 10 : -1>(acc, ca, cb);      // A[2]: behind it A[3] (2) + 8
+    rd_a<G16N, 2>(na, ta); rd_a<G16N, 3>(na, ta);
+    if (DMA && dma) dma_piece<E>(d, 2, dma_dst, dma_t0);
+    mma_pair<TR, 3, OWN ? 12 : -1>(acc, ca, cb);      // A[3]: behind it the 12 of the next group
+    if (DMA && dma) dma_piece<E>(d, 3, dma_dst, dma_t0);
+}
+
 // one 256 x 256 output tile at (n0, k0) over the ring stages [s_lo, s_hi) of the token range, written to `out` (row pitch p.K)
 template <class TR>
 __device__ __forceinline__ void wgrad_tile(const WgradParams& p, float* out, int n0, int k0, int s_lo, int s_hi) {
@@ -119,18 +194,21 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, float* out, int
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;                                   // wave tile: rows [128 wm, +128) x columns [64 wn, +64)
-    const E* dy = static_cast<const E*>(p.dy);
-    const E* xx = static_cast<const E*>(p.x);
-    const E* zeros = reinterpret_cast<const E*>(g_zero_page);
     const uint32_t lds0 = g_lds_addr(smem);
-    // this wave's share of a stage's DMA: sub-tile `wave` (waves 0..3: dy columns n0 + 64 wave; waves 4..7: x columns k0 + 64 (wave - 4))
+    // 64-token steps: an odd number of stages is padded with one stage of zeros (rows from s_hi * 32 on read the zero page like the
+    // rows from T on; a matrix instruction on zero operands leaves its accumulator as it is)
+    const int nsteps = (s_hi - s_lo + 1) >> 1, n2 = 2 * nsteps;
     const bool isx = wave >= 4;
-    const E* dbase = isx ? xx : dy;
-    const int64_t dld = isx ? p.K : p.N;
-    const int dcol = isx ? k0 + 64 * (wave - 4) : n0 + 64 * wave;
+    DmaSrc<E> d;
+    d.base = isx ? static_cast<const E*>(p.x) : static_cast<const E*>(p.dy);
+    d.zeros = reinterpret_cast<const E*>(g_zero_page);
+    d.ld = isx ? p.K : p.N;
+    d.col0 = isx ? k0 + 64 * (wave - 4) : n0 + 64 * wave;
+    d.lane = lane;
+    d.T = p.T < s_hi * 32 ? p.T : s_hi * 32;
     const uint32_t ddst = lds0 + wave * kSub;
 
-    // fragment addresses inside a sub-tile (stage / sub-tile / 16-row step go into immediates or one add)
+    // fragment addresses inside a sub-tile (sub-tile / 16-row step go into immediates, the stage into one add)
     uint32_t tr[2][2];
     {
         const int grp = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3, h = grp >> 1;
@@ -142,6 +220,15 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, float* out, int
         }
     }
     const uint32_t a_off = (2 * wm) * kSub, b_off = (4 + wn) * kSub;
+    uint32_t ta[2][2], tb[2][2];
+#define NPCD_G_ADDR(SO)                                       \
+    do {                                                      \
+        _Pragma("unroll") for (int db = 0; db < 2; ++db)      \
+            _Pragma("unroll") for (int hi = 0; hi < 2; ++hi) { \
+                ta[db][hi] = tr[db][hi] + ((SO) + a_off);     \
+                tb[db][hi] = tr[db][hi] + ((SO) + b_off);     \
+            }                                                 \
+    } while (0)
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -149,71 +236,70 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, float* out, int
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = f32x16{0};
 
-    // ring protocol: stage st is read while st + 1 .. st + 3 are in flight; the slot of st + 3 is the one of st - 1, free after the
-    // barrier that ended iteration st - 1.  A wave issues 4 DMA instructions per stage: "stage st + 1 has landed" = at most the 8
-    // instructions of the two younger stages outstanding.
+    // Ring protocol.  Stage q (32 tokens) lives in slot q mod 5; step j (64 tokens) reads stages 2 j and 2 j + 1 and ends with the one
+    // barrier B_j of the step; the last 16-token group of step j runs BEHIND B_j (from registers) while the first reads of step j + 1 go
+    // out.  A wave issues 4 DMA instructions per stage, and VMEM operations retire in issue order:
+    //   issue order   prologue: stages 0, 1, 2, 3.  Step j issues stage 2 j + 4 in its first group and stage 2 j + 5 in its last, behind
+    //                 B_j: in front of B_j the youngest stage out is 2 j + 4, and 2 j + 3 went out behind B_(j-1) (or in the prologue).
+    //   RAW           before B_j a wave waits vmcnt(4): at most the 4 instructions of stage 2 j + 4, the youngest, are outstanding, so
+    //                 its share of stages 2 j + 2 and 2 j + 3 has landed (vmcnt(0) when stage 2 j + 4 does not exist); every wave has
+    //                 done so when B_j releases, and stages 2 j + 2 / 2 j + 3 are read only behind B_j.  Prologue: vmcnt(8) leaves
+    //                 stages 2 and 3 outstanding, stages 0 and 1 are read behind its barrier.
+    //   WAR           stage 2 j + 4 goes to the slot of stage 2 j - 1 and is issued behind B_(j-1); stage 2 j + 5 goes to the slot of
+    //                 stage 2 j and is issued behind B_j.  Every read of stages 2 j and 2 j + 1 is issued before B_j and retired by
+    //                 the lgkmcnt(0) in front of it, by every wave.  (Slots 3 and 4 are first filled by stages 3 and 4: nothing to wait for.)
+    //   in flight     behind step j's first group: stages 2 j + 2, 2 j + 3, 2 j + 4 -- three, as with the four-stage ring of 32-token
+    //                 steps; a stage is issued at least one step (two stage times) before the wait that needs it.
 #define NPCD_G_VMWAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-    if (s_lo < s_hi) {
-        dma_subtile<E>(ddst, dbase, dld, s_lo * 32, p.T, dcol, lane, zeros);
-        if (s_lo + 1 < s_hi) dma_subtile<E>(ddst + kStage, dbase, dld, (s_lo + 1) * 32, p.T, dcol, lane, zeros);
-        if (s_lo + 2 < s_hi) dma_subtile<E>(ddst + 2 * kStage, dbase, dld, (s_lo + 2) * 32, p.T, dcol, lane, zeros);
-        if (s_lo + 2 < s_hi) NPCD_G_VMWAIT(8);
-        else if (s_lo + 1 < s_hi) NPCD_G_VMWAIT(4);
+    if (nsteps > 0) {
+        // prologue: stages 0 .. 3 into slots 0 .. 3 (nothing has read them); stages 0 and 1 have landed when at most the 8
+        // instructions of stages 2 and 3 are outstanding
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q < n2) dma_subtile<E>(d, ddst + q * kStage, (s_lo + q) * 32);
+        if (n2 > 2) NPCD_G_VMWAIT(8);
         else NPCD_G_VMWAIT(0);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
-    // Software pipeline over the stages: the fragments of a stage's FIRST 16 tokens are read at the end of the previous
-    // iteration, right behind the barrier that says the stage has landed, and their latency hides behind the matrix instructions
-    // of the previous stage's second half; the second half's fragments are read behind the first half's matrix instructions.
     GFrag fa0[4] = {}, fb0[2] = {}, fa1[4] = {}, fb1[2] = {};
-#define NPCD_G_ISSUE(FA, FB, SO, G16)                                                                     \
-    do {                                                                                                  \
-        if (NPCD_WGRAD_DIAG == 4) break;                                                                  \
-        FA[0].lo = g_tr<(G16) * 2048>(tr[0][0] + (SO) + a_off);        FA[0].hi = g_tr<(G16) * 2048>(tr[0][1] + (SO) + a_off);        \
-        FA[1].lo = g_tr<(G16) * 2048>(tr[1][0] + (SO) + a_off);        FA[1].hi = g_tr<(G16) * 2048>(tr[1][1] + (SO) + a_off);        \
-        FA[2].lo = g_tr<kSub + (G16) * 2048>(tr[0][0] + (SO) + a_off); FA[2].hi = g_tr<kSub + (G16) * 2048>(tr[0][1] + (SO) + a_off); \
-        FA[3].lo = g_tr<kSub + (G16) * 2048>(tr[1][0] + (SO) + a_off); FA[3].hi = g_tr<kSub + (G16) * 2048>(tr[1][1] + (SO) + a_off); \
-        FB[0].lo = g_tr<(G16) * 2048>(tr[0][0] + (SO) + b_off);        FB[0].hi = g_tr<(G16) * 2048>(tr[0][1] + (SO) + b_off);        \
-        FB[1].lo = g_tr<(G16) * 2048>(tr[1][0] + (SO) + b_off);        FB[1].hi = g_tr<(G16) * 2048>(tr[1][1] + (SO) + b_off);        \
-    } while (0)
-#define NPCD_G_MMA(FA, FB)                                                                                 \
-    do {                                                                                                  \
-        _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                  \
-            _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                              \
-                if (NPCD_WGRAD_DIAG != 2 && NPCD_WGRAD_DIAG != 4) acc[mi][ni] = TR::mfma32(g_vec<TR>(FA[mi]), g_vec<TR>(FB[ni]), acc[mi][ni]);   \
-                else if (NPCD_WGRAD_DIAG == 2) acc[mi][ni][0] += __uint_as_float(FA[mi].lo[0] ^ FB[ni].hi[1]);          \
-    } while (0)
-#define NPCD_G_WAIT()                                       \
-    do {                                                    \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-        __builtin_amdgcn_sched_barrier(0);                  \
-    } while (0)
-    if (s_lo < s_hi) NPCD_G_ISSUE(fa0, fb0, 0u, 0);
-    for (int st = s_lo; st < s_hi; ++st) {
-        const uint32_t so = ((st - s_lo) & (kRing - 1)) * kStage, so1 = ((st - s_lo + 1) & (kRing - 1)) * kStage;
-        if (st + 3 < s_hi && NPCD_WGRAD_DIAG != 1)
-            dma_subtile<E>(ddst + (((st - s_lo + 3) & (kRing - 1)) * kStage), dbase, dld, (st + 3) * 32, p.T, dcol, lane, zeros);
-        NPCD_G_WAIT();                                   // first-half fragments of stage st
-        NPCD_G_ISSUE(fa1, fb1, so, 1);
-        NPCD_G_MMA(fa0, fb0);
-        NPCD_G_WAIT();                                   // second-half fragments: this wave has read everything it needs of stage st
-        // stage st + 1 must have landed (the younger ones stay in flight); every wave is done reading stage st
-        if (st + 3 < s_hi) NPCD_G_VMWAIT(8);
-        else if (st + 2 < s_hi) NPCD_G_VMWAIT(4);
+    uint32_t r0 = 0;                                     // byte offset of the slot of stage 2 j
+    NPCD_G_ADDR(r0);
+    if (nsteps > 0) {
+        rd_b<0>(fb0, tb);
+        rd_a<0, 0>(fa0, ta); rd_a<0, 1>(fa0, ta); rd_a<0, 2>(fa0, ta); rd_a<0, 3>(fa0, ta);
+    }
+    for (int j = 0; j < nsteps; ++j) {
+        uint32_t r1 = r0 + kStage; r1 = r1 >= kRingBytes ? r1 - kRingBytes : r1;
+        uint32_t r2 = r1 + kStage; r2 = r2 >= kRingBytes ? r2 - kRingBytes : r2;
+        uint32_t r4 = r2 + 2 * kStage; r4 = r4 >= kRingBytes ? r4 - kRingBytes : r4;
+        const bool more = 2 * j + 4 < n2;                // stages 2 j + 4 and 2 j + 5 exist (n2 is even)
+        const int t4 = (s_lo + 2 * j + 4) * 32;
+        // tokens [0, 16) of stage 2 j; reads: [16, 32) of stage 2 j; DMA: stage 2 j + 4 -> the slot of stage 2 j - 1
+        wgrad_group16<TR, 1, true, true, E>(acc, fa0, fb0, fa1, fb1, ta, tb, d, more, ddst + r4, t4);
+        NPCD_G_ADDR(r1);
+        // tokens [16, 32) of stage 2 j; reads: [0, 16) of stage 2 j + 1
+        wgrad_group16<TR, 0, true, false, E>(acc, fa1, fb1, fa0, fb0, ta, tb, d, false, 0u, 0);
+        // tokens [0, 16) of stage 2 j + 1; reads: [16, 32) of stage 2 j + 1
+        wgrad_group16<TR, 1, true, false, E>(acc, fa0, fb0, fa1, fb1, ta, tb, d, false, 0u, 0);
+        NPCD_G_ADDR(r2);
+        // this wave has read everything it needs of stages 2 j and 2 j + 1; its share of stages 2 j + 2 and 2 j + 3 has landed when at
+        // most the 4 instructions of stage 2 j + 4 are outstanding
+        NPCD_G_LGKM(0);
+        if (more) NPCD_G_VMWAIT(4);
         else NPCD_G_VMWAIT(0);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (st + 1 < s_hi) NPCD_G_ISSUE(fa0, fb0, so1, 0);
-        NPCD_G_MMA(fa1, fb1);
+        // tokens [16, 32) of stage 2 j + 1; reads: [0, 16) of stage 2 j + 2 (past the last step: of a slot nobody waits for; the
+        // values are not used); DMA: stage 2 j + 5 -> the slot of stage 2 j
+        wgrad_group16<TR, 0, false, true, E>(acc, fa1, fb1, fa0, fb0, ta, tb, d, more, ddst + r0, t4 + 32);
+        r0 = r2;
     }
-#undef NPCD_G_ISSUE
-#undef NPCD_G_MMA
-#undef NPCD_G_WAIT
+    NPCD_G_LGKM(0);
+#undef NPCD_G_ADDR
 #undef NPCD_G_VMWAIT
     // ---- row n0 + 128 wm + 32 mi + acc_row(i, hh), column k0 + 64 wn + 32 ni + (lane & 31)
     const int r = lane & 31, hh = lane >> 5;
-    if (NPCD_WGRAD_DIAG == 3 && acc[0][0][0] != 12345.678f) return;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -223,6 +309,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, float* out, int
             for (int i = 0; i < 16; ++i) o[(int64_t)acc_row(i, hh) * p.K] = acc[mi][ni][i];
         }
 }
+#undef NPCD_G_LGKM
 
 template <class TR>
 __global__ __launch_bounds__(512, 2) void wgrad_kernel(WgradParams p) {
