@@ -456,26 +456,32 @@ def test_pair_input_and_aggregate_kernels_vs_torch():
     assert float(agg[7].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("F_", [32, 128])
-def test_fused_pair_mlp_fp32_class_mode(F_):
-    """precision = PAIR_MLP_X2 of csrc/pairs_mlp.hip: every operand as two bf16 halves, three matrix instructions per product, fp32
-    accumulation.  Against a float64 restatement of the same network (npcd_pair_input's rows -> four Linear + LeakyReLU(0.01) ->
-    weighted mean):
-      forward: G to rel-L2 <= 5e-5 (bf16 mode: 2e-2; an fp32 GEMM chain sits at ~1e-6);
-      backward, layer by layer from the kernels' own stored activations (so that a LeakyReLU unit whose tiny pre-activation falls on
-      the other side of zero does not decide the comparison): every gradient to rel-L2 <= 1e-4;
-      backward end to end against float64 autograd: <= 5e-3 -- what is left are those units (slope 1 against 0.01), the same
-      effect two fp32 implementations with different summation orders show at ~3e-4.
-    Same ragged lists as the bf16 test; bitwise reproducible weight gradients."""
-    import torch.nn.functional as F
-    from npcd.hip import render as hr
-    torch.manual_seed(F_ + 1)
-    P, k, Nt = 1237, 8, 300
+# ---- the per-pair MLP kernels (csrc/pairs_mlp.hip): lists, step-by-step restatements and their bars, shared with
+# tests/test_gpu_tile_rounds.py, which runs the same checks where a workgroup takes several tiles
+PAIR_NAMES = ["feat"] + [f"{n}{i}" for i in range(4) for n in ("W", "b")]
+
+
+def pair_rel(a, b):
+    return float((a.double() - b.double()).norm() / b.double().norm())
+
+
+def ragged_neighbour_lists(P, k, Nt):
+    """1..k neighbours per point, valid entries first, points 16..31 with one neighbour each (a tile whose pairs fill less than
+    one 32-row block); drawn from torch's global CPU generator"""
     cnt = torch.randint(1, k + 1, (P,))
     cnt[16:32] = 1
     nb = torch.full((P, k), -1, dtype=torch.long)
     for p in range(P):
         nb[p, :cnt[p]] = torch.randperm(Nt)[:cnt[p]]
+    return nb
+
+
+def pair_case(nb, F_, Nt):
+    """nb [P, k] int64 on the CPU (valid entries first) -> everything a call of the pair-MLP kernels takes: the compact pair lists of
+    csrc/pairs.hip (owner, flat, off, per-point counts c), sample points, table positions and features, the four Linear layers and
+    an upstream gradient -- drawn from torch's global CPU generator in this order."""
+    from types import SimpleNamespace
+    P = nb.shape[0]
     nb = nb.cuda()
     pts = (torch.rand(P, 3) - 0.5).cuda()
     pos = (torch.rand(Nt, 3) - 0.5).cuda()
@@ -488,63 +494,180 @@ def test_fused_pair_mlp_fp32_class_mode(F_):
     c = valid.sum(dim=1)
     off = torch.cumsum(c, 0) - c
     gout = torch.randn(P, 256).cuda()
-    rel = lambda a, b: float((a.double() - b.double()).norm() / b.double().norm())
-    names = ["feat"] + [f"{n}{i}" for i in range(4) for n in ("W", "b")]
-    X2 = hr.PAIR_MLP_X2
-    layers = [(lin.weight, lin.bias) for lin in lins]
-    G = hr.pair_mlp(feat, layers, nb, pts, pos, off, owner, flat, X2)
-    (G * gout).sum().backward()
-    got = [feat.grad.clone()] + [p_.grad.clone() for lin in lins for p_ in (lin.weight, lin.bias)]
-    feat.grad = None
-    for lin in lins:
+    return SimpleNamespace(F=F_, Nt=Nt, P=P, Q=int(flat.numel()), nb=nb, pts=pts, pos=pos, feat=feat, lins=lins, owner=owner, flat=flat,
+                           c=c, off=off, gout=gout, weights=[l_.weight for l_ in lins], biases=[l_.bias for l_ in lins],
+                           layers=[(l_.weight, l_.bias) for l_ in lins])
+
+
+def pair_case_grads(cs):
+    """the gradients autograd left on the case's leaves (PAIR_NAMES order), cleared afterwards"""
+    out = [cs.feat.grad.clone()] + [p_.grad.clone() for lin in cs.lins for p_ in (lin.weight, lin.bias)]
+    cs.feat.grad = None
+    for lin in cs.lins:
         lin.weight.grad = lin.bias.grad = None
-    # ---- float64 restatement (the input rows and weights of the fp32 kernel npcd_pair_input, everything after in float64)
-    x0, w = hr.pair_input(feat.detach(), flat, owner, pts, pos, 10)
-    f64 = feat.detach().double().requires_grad_(True)
-    x64 = torch.cat((f64[flat], x0[:, F_:].double()), dim=1)
-    W64 = [lin.weight.detach().double().requires_grad_(True) for lin in lins]
-    b64 = [lin.bias.detach().double().requires_grad_(True) for lin in lins]
-    h = x64
-    for Wl, bl in zip(W64, b64):
-        h = F.leaky_relu(h @ Wl.t() + bl, 0.01)
-    wn64 = (w.double() / torch.zeros(P, device="cuda", dtype=torch.float64).index_add_(0, owner, w.double())[owner])
-    G64 = torch.zeros(P, 256, device="cuda", dtype=torch.float64).index_add_(0, owner, wn64[:, None] * h)
-    (G64 * gout.double()).sum().backward()
+    return out
+
+
+def bf16_forward_vs_restatement(cs, raw):
+    """bf16 mode, forward: what npcd_pair_mlp_fwd stored (raw = pair_mlp_forward_raw's tuple) against a torch restatement with the SAME
+    rounding points, every layer from the PREVIOUS layer's stored activations.  Bars: normalised weights 1e-6, input rows 1e-2 abs /
+    2e-3 rel-L2 (v_sin / v_cos + one bf16 rounding), each layer's output 3e-3 (one bf16 rounding), G 1e-5 from the stored last layer.
+    Returns (worst figure / bar, layer inputs)."""
+    import torch.nn.functional as F
+    from npcd.hip import render as hr
+    Gk, _, x0k, actk, wnk = raw
+    F_, Q = cs.F, cs.Q
+    r16 = lambda t: t.bfloat16().float()
+    with torch.no_grad():
+        x0, w = hr.pair_input(cs.feat.detach(), cs.flat, cs.owner, cs.pts, cs.pos, 10)
+        wsum = torch.zeros(cs.P, device="cuda").index_add_(0, cs.owner, w)
+        worst = pair_rel(wnk, w / wsum[cs.owner]) / 1e-6
+        assert worst < 1, ("wn", worst * 1e-6)
+        x0p = torch.cat((x0, torch.zeros(Q, 1, device="cuda")), dim=1)                           # the kernel pads the input to F + 64 columns
+        e_abs, e_rel = float((x0k.float() - r16(x0p)).abs().max()), pair_rel(x0k.float(), r16(x0p))
+        assert e_abs < 1e-2 and e_rel < 2e-3, ("x0", e_abs, e_rel)                                 # v_sin / v_cos + bf16 rounding
+        worst = max(worst, e_abs / 1e-2, e_rel / 2e-3)
+        layer_in = [x0k.float()[:, :F_ + 63]] + [actk[l].float() for l in range(3)]
+        for l, lin in enumerate(cs.lins):
+            a_e = F.leaky_relu(layer_in[l] @ r16(lin.weight).t() + lin.bias, 0.01)
+            e = pair_rel(actk[l].float(), a_e)
+            assert e < 3e-3, (l, e)                                                                # one bf16 rounding apart
+            worst = max(worst, e / 3e-3)
+        G_e = torch.zeros(cs.P, 256, device="cuda").index_add_(0, cs.owner, wnk[:Q, None] * actk[3].float())
+        e = pair_rel(Gk, G_e)
+        assert e < 1e-5, ("G", e)
+        worst = max(worst, e / 1e-5)
+    return worst, layer_in
+
+
+def bf16_backward_restatement(cs, raw, layer_in):
+    """bf16 mode, backward from the kernels' own stored activations (a LeakyReLU unit whose tiny output rounds to the other sign would
+    otherwise dominate the sums): dZ / dA rounded to bf16 where the kernels round them, fp32 sums.
+    Returns ({name: gradient}, [dZ_l for l = 0..3])."""
+    _, _, x0k, actk, wnk = raw
+    r16 = lambda t: t.bfloat16().float()
+    with torch.no_grad():
+        dA = wnk[:cs.Q, None] * cs.gout[cs.owner]
+        emu, dZs = {}, [None] * 4
+        for l in (3, 2, 1, 0):
+            dZ = r16(dA * torch.where(actk[l].float() > 0, 1.0, 0.01))
+            dZs[l] = dZ
+            emu[f"b{l}"] = dZ.sum(0)
+            emu[f"W{l}"] = dZ.t() @ layer_in[l]
+            dA = dZ @ r16(cs.lins[l].weight)
+            if l > 0:
+                dA = r16(dA)
+        emu["dfeat_rows"] = dA[:, :cs.F]
+        emu["feat"] = torch.zeros(cs.Nt, cs.F, device="cuda").index_add_(0, cs.flat, dA[:, :cs.F])
+    return emu, dZs
+
+
+def x2_float64_network(cs, grad=False):
+    """fp32-class mode: the float64 restatement of the whole network (the input rows and weights of the fp32 kernel npcd_pair_input,
+    everything after in float64) -> (G64, x0, [feat leaf, W leaves, b leaves]); with grad the leaves take part in autograd."""
+    import torch.nn.functional as F
+    from npcd.hip import render as hr
+    with torch.no_grad():
+        x0, w = hr.pair_input(cs.feat.detach(), cs.flat, cs.owner, cs.pts, cs.pos, 10)
+    with torch.set_grad_enabled(grad):
+        f64 = cs.feat.detach().double().requires_grad_(grad)
+        x64 = torch.cat((f64[cs.flat], x0[:, cs.F:].double()), dim=1)
+        W64 = [lin.weight.detach().double().requires_grad_(grad) for lin in cs.lins]
+        b64 = [lin.bias.detach().double().requires_grad_(grad) for lin in cs.lins]
+        h = x64
+        for Wl, bl in zip(W64, b64):
+            h = F.leaky_relu(h @ Wl.t() + bl, 0.01)
+        wn64 = (w.double() / torch.zeros(cs.P, device="cuda", dtype=torch.float64).index_add_(0, cs.owner, w.double())[cs.owner])
+        G64 = torch.zeros(cs.P, 256, device="cuda", dtype=torch.float64).index_add_(0, cs.owner, wn64[:, None] * h)
+    return G64, x0, (f64, W64, b64)
+
+
+def x2_forward_vs_float64(cs, raw, G64, x0):
+    """fp32-class mode, forward: G to rel-L2 5e-5 of the float64 network; the stored planes (hi + lo) layer by layer from the PREVIOUS
+    layer's stored activations: input rows and every layer's output to 2e-5.  Returns (worst figure / bar, layer inputs in float64)."""
+    import torch.nn.functional as F
+    Gk, _, x0k, actk, _ = raw
+    F_, Q = cs.F, cs.Q
+    with torch.no_grad():
+        e = pair_rel(Gk, G64.detach())
+        assert e < 5e-5, ("G", e)
+        worst = e / 5e-5
+        assert x0k.shape == (2, max(Q, 1), F_ + 64) and actk.shape == (4, 2, max(Q, 1), 256)
+        x0s = x0k[0].double() + x0k[1].double()
+        x0p = torch.cat((x0.double(), torch.zeros(Q, 1, device="cuda", dtype=torch.float64)), dim=1)
+        e = pair_rel(x0s, x0p)
+        assert e < 2e-5, ("x0", e)                                   # two halves of the fp32 input rows (v_sin / v_cos included)
+        worst = max(worst, e / 2e-5)
+        acts = [actk[l, 0].double() + actk[l, 1].double() for l in range(4)]
+        layer_in = [x0s[:, :F_ + 63]] + acts[:3]
+        for l, lin in enumerate(cs.lins):
+            a_e = F.leaky_relu(layer_in[l] @ lin.weight.double().t() + lin.bias.double(), 0.01)
+            e = pair_rel(acts[l], a_e)
+            assert e < 2e-5, (l, e)
+            worst = max(worst, e / 2e-5)
+    return worst, layer_in
+
+
+def x2_backward_restatement(cs, raw, layer_in):
+    """fp32-class mode, backward in float64 from the kernels' own stored activations (so that a LeakyReLU unit whose tiny
+    pre-activation falls on the other side of zero does not decide the comparison).  Returns ({name: gradient}, [dZ_l])."""
+    _, _, _, actk, wnk = raw
+    with torch.no_grad():
+        dA = wnk[:cs.Q].double()[:, None] * cs.gout.double()[cs.owner]
+        emu, dZs = {}, [None] * 4
+        for l in (3, 2, 1, 0):
+            dZ = dA * torch.where(actk[l, 0].double() > 0, 1.0, 0.01)
+            dZs[l] = dZ
+            emu[f"b{l}"] = dZ.sum(0)
+            emu[f"W{l}"] = dZ.t() @ layer_in[l]
+            dA = dZ @ cs.lins[l].weight.double()
+        emu["dfeat_rows"] = dA[:, :cs.F]
+        emu["feat"] = torch.zeros(cs.Nt, cs.F, device="cuda", dtype=torch.float64).index_add_(0, cs.flat, dA[:, :cs.F])
+    return emu, dZs
+
+
+@pytest.mark.parametrize("F_", [32, 128])
+def test_fused_pair_mlp_fp32_class_mode(F_):
+    """precision = PAIR_MLP_X2 of csrc/pairs_mlp.hip: every operand as two bf16 halves, three matrix instructions per product, fp32
+    accumulation.  Against a float64 restatement of the same network (npcd_pair_input's rows -> four Linear + LeakyReLU(0.01) ->
+    weighted mean):
+      forward: G to rel-L2 <= 5e-5 (bf16 mode: 2e-2; an fp32 GEMM chain sits at ~1e-6);
+      backward, layer by layer from the kernels' own stored activations (so that a LeakyReLU unit whose tiny pre-activation falls on
+      the other side of zero does not decide the comparison): every gradient to rel-L2 <= 1e-4;
+      backward end to end against float64 autograd: <= 5e-3 -- what is left are those units (slope 1 against 0.01), the same
+      effect two fp32 implementations with different summation orders show at ~3e-4.
+    Same ragged lists as the bf16 test; bitwise reproducible weight gradients."""
+    from npcd.hip import render as hr
+    torch.manual_seed(F_ + 1)
+    P, k, Nt = 1237, 8, 300
+    cs = pair_case(ragged_neighbour_lists(P, k, Nt), F_, Nt)
+    X2 = hr.PAIR_MLP_X2
+    G = hr.pair_mlp(cs.feat, cs.layers, cs.nb, cs.pts, cs.pos, cs.off, cs.owner, cs.flat, X2)
+    (G * cs.gout).sum().backward()
+    got = pair_case_grads(cs)
+    # ---- float64 restatement of the whole network under autograd
+    G64, x0, (f64, W64, b64) = x2_float64_network(cs, grad=True)
+    (G64 * cs.gout.double()).sum().backward()
     ref = [f64.grad] + [t.grad for pair in zip(W64, b64) for t in pair]
-    assert rel(G, G64.detach()) < 5e-5, rel(G, G64.detach())
-    errs = {n: rel(a, b) for n, a, b in zip(names, got, ref)}
+    assert pair_rel(G, G64.detach()) < 5e-5, pair_rel(G, G64.detach())
+    errs = {n: pair_rel(a, b) for n, a, b in zip(PAIR_NAMES, got, ref)}
     assert max(errs.values()) < 5e-3, errs
     # ---- layer by layer from the stored activations (hi + lo planes)
     with torch.no_grad():
-        Q = flat.numel()
-        Gk, wpack, x0k, actk, wnk = hr.pair_mlp_forward_raw(feat, [l_.weight for l_ in lins], [l_.bias for l_ in lins], nb, pts, pos, off, Q, X2)
-        assert torch.equal(Gk, G) and x0k.shape == (2, Q, F_ + 64) and actk.shape == (4, 2, Q, 256)
-        x0s = x0k[0].double() + x0k[1].double()
-        x0p = torch.cat((x0.double(), torch.zeros(Q, 1, device="cuda", dtype=torch.float64)), dim=1)
-        assert rel(x0s, x0p) < 2e-5, rel(x0s, x0p)                   # two halves of the fp32 input rows (v_sin / v_cos included)
-        acts = [actk[l, 0].double() + actk[l, 1].double() for l in range(4)]
-        layer_in = [x0s[:, :F_ + 63]] + acts[:3]
-        for l, lin in enumerate(lins):
-            a_e = F.leaky_relu(layer_in[l] @ lin.weight.double().t() + lin.bias.double(), 0.01)
-            assert rel(acts[l], a_e) < 2e-5, (l, rel(acts[l], a_e))
-        dA = wnk.double()[:, None] * gout.double()[owner]
-        emu = {}
-        for l in (3, 2, 1, 0):
-            dZ = dA * torch.where(actk[l, 0].double() > 0, 1.0, 0.01)
-            emu[f"b{l}"] = dZ.sum(0)
-            emu[f"W{l}"] = dZ.t() @ layer_in[l]
-            dA = dZ @ lins[l].weight.double()
-        emu["feat"] = torch.zeros(Nt, F_, device="cuda", dtype=torch.float64).index_add_(0, flat, dA[:, :F_])
-    errs_k = {n: rel(a, emu[n]) for n, a in zip(names, got)}
+        raw = hr.pair_mlp_forward_raw(cs.feat, cs.weights, cs.biases, cs.nb, cs.pts, cs.pos, cs.off, cs.Q, X2)
+        assert torch.equal(raw[0], G)
+        _, layer_in = x2_forward_vs_float64(cs, raw, G64, x0)
+        emu, _ = x2_backward_restatement(cs, raw, layer_in)
+    errs_k = {n: pair_rel(a, emu[n]) for n, a in zip(PAIR_NAMES, got)}
     assert max(errs_k.values()) < 1e-4, errs_k
-    print("x2 pair MLP: forward", rel(G, G64.detach()), "gradients vs float64 autograd", errs, "vs stored activations", errs_k)
+    print("x2 pair MLP: forward", pair_rel(G, G64.detach()), "gradients vs float64 autograd", errs, "vs stored activations", errs_k)
     # ---- bitwise reproducible
-    G2 = hr.pair_mlp(feat, layers, nb, pts, pos, off, owner, flat, X2)
-    (G2 * gout).sum().backward()
-    again = [p_.grad.clone() for lin in lins for p_ in (lin.weight, lin.bias)]
-    assert torch.equal(G, G2) and all(torch.equal(a, b) for a, b in zip(got[1:], again))
+    G2 = hr.pair_mlp(cs.feat, cs.layers, cs.nb, cs.pts, cs.pos, cs.off, cs.owner, cs.flat, X2)
+    (G2 * cs.gout).sum().backward()
+    again = pair_case_grads(cs)
+    assert torch.equal(G, G2) and all(torch.equal(a, b) for a, b in zip(got[1:], again[1:]))
     # ---- forward only (rendering): nothing saved, same G
-    G3, _, x3, a3, w3 = hr.pair_mlp_forward_raw(feat, [l_.weight for l_ in lins], [l_.bias for l_ in lins], nb, pts, pos, off, Q, X2, save=False)
+    G3, _, x3, a3, w3 = hr.pair_mlp_forward_raw(cs.feat, cs.weights, cs.biases, cs.nb, cs.pts, cs.pos, cs.off, cs.Q, X2, save=False)
     assert x3 is None and a3 is None and w3 is None and torch.equal(G3, G)
 
 
@@ -562,81 +685,35 @@ def test_fused_pair_mlp_forward_and_backward(F_):
     from npcd.hip import render as hr
     torch.manual_seed(F_)
     P, k, Nt = 1237, 8, 300
-    cnt = torch.randint(1, k + 1, (P,))
-    cnt[16:32] = 1                                                   # a tile whose pairs fill less than one 32-row block
-    nb = torch.full((P, k), -1, dtype=torch.long)
-    for p in range(P):
-        nb[p, :cnt[p]] = torch.randperm(Nt)[:cnt[p]]
-    nb = nb.cuda()
-    pts = (torch.rand(P, 3) - 0.5).cuda()
-    pos = (torch.rand(Nt, 3) - 0.5).cuda()
-    feat = torch.randn(Nt, F_).cuda().requires_grad_(True)
-    dims = [F_ + 63, 256, 256, 256, 256]
-    lins = [torch.nn.Linear(dims[i], dims[i + 1]).cuda() for i in range(4)]
-    valid = nb >= 0
-    owner, col = torch.nonzero(valid, as_tuple=True)
-    flat = nb[owner, col]
-    c = valid.sum(dim=1)
-    off = torch.cumsum(c, 0) - c
-    gout = torch.randn(P, 256).cuda()
-    rel = lambda a, b: float((a.double() - b.double()).norm() / b.double().norm())
-    names = ["feat"] + [f"{n}{i}" for i in range(4) for n in ("W", "b")]
-
-    def grads():
-        out = [feat.grad.clone()] + [p_.grad.clone() for lin in lins for p_ in (lin.weight, lin.bias)]
-        feat.grad = None
-        for lin in lins:
-            lin.weight.grad = lin.bias.grad = None
-        return out
-
+    cs = pair_case(ragged_neighbour_lists(P, k, Nt), F_, Nt)
     # ---- the kernels
-    G = hr.pair_mlp(feat, [(lin.weight, lin.bias) for lin in lins], nb, pts, pos, off, owner, flat)
-    (G * gout).sum().backward()
-    got = grads()
+    G = hr.pair_mlp(cs.feat, cs.layers, cs.nb, cs.pts, cs.pos, cs.off, cs.owner, cs.flat)
+    (G * cs.gout).sum().backward()
+    got = pair_case_grads(cs)
     # ---- (b) fp32 formulation
-    x0, w = hr.pair_input(feat, flat, owner, pts, pos, 10)
+    x0, w = hr.pair_input(cs.feat, cs.flat, cs.owner, cs.pts, cs.pos, 10)
     h = x0
-    for lin in lins:
+    for lin in cs.lins:
         h = F.leaky_relu(lin(h), 0.01)
-    G_ref = hr.pair_aggregate(h, w, off, c)
-    (G_ref * gout).sum().backward()
-    ref32 = grads()
-    assert rel(G, G_ref.detach()) < 2e-2, rel(G, G_ref.detach())
-    errs32 = {n: rel(a, b) for n, a, b in zip(names, got, ref32)}
+    G_ref = hr.pair_aggregate(h, w, cs.off, cs.c)
+    (G_ref * cs.gout).sum().backward()
+    ref32 = pair_case_grads(cs)
+    assert pair_rel(G, G_ref.detach()) < 2e-2, pair_rel(G, G_ref.detach())
+    errs32 = {n: pair_rel(a, b) for n, a, b in zip(PAIR_NAMES, got, ref32)}
     assert max(errs32.values()) < 1.5e-1, errs32
     # ---- (a) same rounding points, step by step.  Forward: every layer from the PREVIOUS layer's stored activations; backward: from
     # the stored activations too (a LeakyReLU unit whose tiny output rounds to the other sign would otherwise dominate the sums)
     with torch.no_grad():
-        r16 = lambda t: t.bfloat16().float()
-        Q = flat.numel()
-        Gk, wpack, x0k, actk, wnk = hr.pair_mlp_forward_raw(feat, [l_.weight for l_ in lins], [l_.bias for l_ in lins], nb, pts, pos, off, Q)
-        assert torch.equal(Gk, G)
-        wsum = torch.zeros(P, device="cuda").index_add_(0, owner, w)
-        assert rel(wnk, w / wsum[owner]) < 1e-6
-        x0p = torch.cat((x0.detach(), torch.zeros(Q, 1, device="cuda")), dim=1)                  # the kernel pads the input to F + 64 columns
-        assert float((x0k.float() - r16(x0p)).abs().max()) < 1e-2 and rel(x0k.float(), r16(x0p)) < 2e-3   # v_sin / v_cos + bf16 rounding
-        layer_in = [x0k.float()[:, :F_ + 63]] + [actk[l].float() for l in range(3)]
-        for l, lin in enumerate(lins):
-            a_e = F.leaky_relu(layer_in[l] @ r16(lin.weight).t() + lin.bias, 0.01)
-            assert rel(actk[l].float(), a_e) < 3e-3, (l, rel(actk[l].float(), a_e))               # one bf16 rounding apart
-        G_e = torch.zeros(P, 256, device="cuda").index_add_(0, owner, wnk[:, None] * actk[3].float())
-        assert rel(G, G_e) < 1e-5
-        dA = wnk[:, None] * gout[owner]
-        emu = {}
-        for l in (3, 2, 1, 0):
-            dZ = r16(dA * torch.where(actk[l].float() > 0, 1.0, 0.01))
-            emu[f"b{l}"] = dZ.sum(0)
-            emu[f"W{l}"] = dZ.t() @ layer_in[l]
-            dA = dZ @ r16(lins[l].weight)
-            if l > 0:
-                dA = r16(dA)
-        emu["feat"] = torch.zeros(Nt, F_, device="cuda").index_add_(0, flat, dA[:, :F_])
-    errs = {n: rel(a, emu[n]) for n, a in zip(names, got)}
+        raw = hr.pair_mlp_forward_raw(cs.feat, cs.weights, cs.biases, cs.nb, cs.pts, cs.pos, cs.off, cs.Q)
+        assert torch.equal(raw[0], G)
+        _, layer_in = bf16_forward_vs_restatement(cs, raw)
+        emu, _ = bf16_backward_restatement(cs, raw, layer_in)
+    errs = {n: pair_rel(a, emu[n]) for n, a in zip(PAIR_NAMES, got)}
     assert max(errs.values()) < 2e-3, errs
     # ---- bitwise reproducible weight gradients (slabs summed in a fixed order; the feature scatter uses float atomics like the reference's)
-    G2 = hr.pair_mlp(feat, [(lin.weight, lin.bias) for lin in lins], nb, pts, pos, off, owner, flat)
-    (G2 * gout).sum().backward()
-    again = grads()
+    G2 = hr.pair_mlp(cs.feat, cs.layers, cs.nb, cs.pts, cs.pos, cs.off, cs.owner, cs.flat)
+    (G2 * cs.gout).sum().backward()
+    again = pair_case_grads(cs)
     assert torch.equal(G, G2) and all(torch.equal(a, b) for a, b in zip(got[1:], again[1:]))
 
 
