@@ -19,7 +19,7 @@
  *   - `stream` is a hipStream_t passed as void*; kernels are enqueued on it and never synchronise
  *   - return value: 0 on success, a negative NPCD_ERR_* otherwise (no exceptions cross the ABI)
  *   - strides are in ELEMENTS, the innermost (head_dim / channel) dimension is contiguous
- *   - dtype codes: NPCD_BF16 = 0, NPCD_F16 = 1, NPCD_F32 = 2
+ *   - dtype codes: NPCD_BF16 = 0, NPCD_F16 = 1, NPCD_F32 = 2, NPCD_F64 = 3 (feature statistics only)
  */
 #ifndef NPCD_HIP_H
 #define NPCD_HIP_H
@@ -38,6 +38,7 @@ extern "C" {
 #define NPCD_BF16 0
 #define NPCD_F16 1
 #define NPCD_F32 2
+#define NPCD_F64 3
 
 int npcd_abi_version(void);
 const char* npcd_error_string(int code);
@@ -780,6 +781,40 @@ int npcd_image_metrics(const float* pred, const float* target, int V, int C, int
                        int64_t pred_sh, int64_t pred_sw, int64_t target_sv, int64_t target_sc, int64_t target_sh, int64_t target_sw,
                        const double* taps, int w, double n, double data_range, double* workspace, double* mse, double* ssim, double* map,
                        void* stream);
+
+/* ---- feature statistics: the moments of the Frechet distance and the subset sums of the kernel inception distance --------------------
+ * (csrc/feature_stats.hip).  Features are rows of [N, D] matrices on the device, dtype NPCD_F32 or NPCD_F64, a row
+ * stride in elements (>= D) and unit column stride, only read.  All arithmetic is float64 on the float64 matrix instruction; every
+ * accumulator element is owned by one lane of one workgroup: no float atomics, no fence, the same bits on every run.
+ *
+ * npcd_moments_update: over the rows [r0, r1) of x, with s = shift [D] (float64, NULL = 0),
+ *   sum[j] += SUM_r (x_rj - s_j);    gram[i][j] += SUM_r (x_ri - s_i)(x_rj - s_j)   where tile(j) >= tile(i),
+ * tile(c) = c / T with T of npcd_moments_tile; entries of gram [D, D] in tiles below the diagonal are not touched.  One launch;
+ * r1 == r0 launches nothing.  sum [D] and gram are float64 and must hold the totals so far (zeros at first).
+ * npcd_moments_finish: mean[j] = s_j + sum[j] / n;  cov[i][j] = cov[j][i] = (gram[i][j] - n m_i m_j) / (n - 1), m = sum / n, from the
+ * upper tiles of gram: the full symmetric [D, D], both halves written from one computed value.  n is the number of rows summed.
+ *
+ * npcd_kid_subsets: idx_f, idx_r int32 [S, m] on the device, entries in [0, Nf) and [0, Nr).  With x_i = fake[idx_f[s, i]],
+ * y_j = real[idx_r[s, j]], k(a, b) = t t t, t = (a . b) / D + 1,
+ *   out[s] = (SUM_{i != j} k(x_i, x_j),  SUM_{i != j} k(y_i, y_j),  SUM_{i, j} k(x_i, y_j)),   out float64 [S, 3], fully written.
+ * workspace: npcd_kid_workspace_bytes(S, m) bytes, 8-byte aligned, contents irrelevant before and after: one partial sum per tile of
+ * npcd_kid_tile = T x T pairs, S (t (t + 1) + t t) of them with t = ceil(m / T) (only the tiles on or above the diagonal of the two
+ * symmetric matrices are computed), added by a second small launch in a fixed order.
+ *
+ * NPCD_ERR_UNSUPPORTED for D < 1 or D > npcd_moments_max_features() (4,096), a dtype other than the two, n < 2, m < 2, m > 2^20, S < 1
+ * and S times the tiles of a subset >= 2^31 (the workspace query returns it too), before any pointer is looked at; NPCD_ERR_ARG for a
+ * NULL pointer other than shift, r0 < 0, r1 < r0, a row stride below D, Nf or Nr < 1.  Nothing is launched in either case.  tile_host
+ * is a host pointer. */
+int npcd_moments_tile(int* tile_host);
+int npcd_moments_max_features(void);
+int npcd_moments_update(const void* x, int dtype, int64_t ld, int64_t r0, int64_t r1, int D, const double* shift, double* sum, double* gram,
+                        void* stream);
+int npcd_moments_finish(const double* sum, const double* gram, const double* shift, int D, int64_t n, double* mean, double* cov,
+                        void* stream);
+int npcd_kid_tile(int* tile_host);
+int64_t npcd_kid_workspace_bytes(int S, int m);
+int npcd_kid_subsets(const void* fake, const void* real, int dtype, int Nf, int Nr, int D, int64_t ldf, int64_t ldr, const int32_t* idx_f,
+                     const int32_t* idx_r, int S, int m, double* workspace, double* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,9 @@ SOURCES = {
     # the image metrics evaluate their float64 expressions as written: with identical images the numerator and the denominator of
     # SSIM are then the same bits and the index is 1 exactly
     "ssim.hip": ["-ffp-contract=off"],
+    # the feature statistics evaluate their float64 epilogues as written (cov from the raw moments, the cubic kernel): the exact-integer
+    # tests and cov == cov.T rest on it; the products themselves are the float64 matrix instruction's
+    "feature_stats.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

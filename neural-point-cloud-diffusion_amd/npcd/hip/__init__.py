@@ -15,6 +15,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__fi
 LIB_PATH = os.environ.get("NPCD_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libnpcd_hip.so")
 
 NPCD_BF16, NPCD_F16, NPCD_F32 = 0, 1, 2
+NPCD_F64 = 3          # the feature statistics only (feature_stats.py)
 NPCD_GRID_FINE, NPCD_GRID_SCALED = 0, 1
 _DTYPE_CODE = {torch.bfloat16: NPCD_BF16, torch.float16: NPCD_F16, torch.float32: NPCD_F32}
 
@@ -152,6 +153,13 @@ SIGNATURES = {
     "npcd_image_metrics_tile": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "npcd_image_metrics_workspace_bytes": (c_int64, [c_int] * 5),
     "npcd_image_metrics": (c_int, [_P, _P] + [c_int] * 4 + [c_int64] * 8 + [_P, c_int, c_double, c_double] + [_P] * 4 + [_P]),
+    "npcd_moments_tile": (c_int, [POINTER(c_int)]),
+    "npcd_moments_max_features": (c_int, []),
+    "npcd_moments_update": (c_int, [_P, c_int, c_int64, c_int64, c_int64, c_int, _P, _P, _P, _P]),
+    "npcd_moments_finish": (c_int, [_P, _P, _P, c_int, c_int64, _P, _P, _P]),
+    "npcd_kid_tile": (c_int, [POINTER(c_int)]),
+    "npcd_kid_workspace_bytes": (c_int64, [c_int, c_int]),
+    "npcd_kid_subsets": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, c_int, _P, _P, _P]),
 }
 
 _lib = None

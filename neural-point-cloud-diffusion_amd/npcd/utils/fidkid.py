@@ -6,7 +6,10 @@ distance and the kernel inception distance (cubic polynomial kernel, random subs
 Inception-v3 network and its weights (`data/inception-2015-12-05.pt`, the per-dataset `*_inception_stylegan.pkl`): they are not part
 of the reference repository and not available in this environment, so `feed` takes FEATURES, or images plus a caller-supplied
 `feature_extractor`; without one it raises instead of guessing.  Hook for npcd.eval.sample_and_render:
-`feed=lambda images: fidkid.feed(images * 2 - 1, "fakes")` (diffusion_evaluation.py:179)."""
+`feed=lambda images: fidkid.feed(images * 2 - 1, "fakes")` (diffusion_evaluation.py:179).
+
+`FIDKID` keeps the features and computes on the host.  `DeviceFIDKID` is the same surface with the statistics on the GPU
+(npcd.hip.feature_stats): `feed` leaves nothing on the host and waits for nothing, `summary` reads back once."""
 import pickle
 from typing import Callable, Optional
 
@@ -110,6 +113,112 @@ class FIDKID:
         fake_np = fake.numpy()
         fid, mean, cov = frechet_distance(np.mean(fake_np, 0), np.cov(fake_np, rowvar=False), self.real_mean, self.real_cov)
         kid = kernel_inception_distance(self.real_feats_np, fake_np, self.num_subsets, self.max_subset_size) * 1000
+        self._result_str = f"{fid:.4f} ({mean:.5f}/{cov:.5f}), {kid:.4f}"
+        self._result_dict = dict(fid=fid, fid_mean=mean, fid_cov=cov, kid=kid)
+        return fid, mean, cov, kid
+
+
+class DeviceFIDKID:
+    """`FIDKID`'s surface with the statistics on the GPU.  `feed` keeps the features on the device -- a 2-D batch is
+    features, images go through `feature_extractor` -- and accumulates their moments there; it issues no device-to-host copy and no
+    host wait.  `summary()` finalises the moments, draws the KID subsets on the host from `rng` in the reference's order (per subset
+    first choice(n_fake, m, replace=False), then choice(n_real, ...), so a seeded run reproduces `FIDKID`'s subsets), runs one
+    `kid_subsets` launch, reads back once and calls `frechet_distance` in float64 on the host.
+
+    Hook for npcd.eval.sample_and_render: `feed=lambda im: m.feed(im * 2 - 1, "fakes")`."""
+    name = "FIDKID"
+
+    def __init__(self, num_images: int, num_subsets: int = 100, max_subset_size: int = 1000, inception_pkl: Optional[str] = None,
+                 feature_extractor: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, device=None, block_rows: int = 1024,
+                 rng=None, **_):
+        self.num_images, self.num_subsets, self.max_subset_size = num_images, num_subsets, max_subset_size
+        self.inception_pkl, self.feature_extractor = inception_pkl, feature_extractor
+        self.device = torch.device("cuda" if device is None else device)
+        self.block_rows, self.rng = block_rows, rng
+        self.real_mean = self.real_cov = self.real_feats_np = None
+        self._real_feats = None                                          # the pickle's features on the device
+        self._moments = {"reals": None, "fakes": None}                   # FeatureMoments, made at the first feed of a side
+        self.num_real_feeded = self.num_fake_feeded = 0
+        self._result_str, self._result_dict = None, None
+
+    def prepare(self):
+        if self.inception_pkl is not None:
+            with open(self.inception_pkl, "rb") as f:
+                ref = pickle.load(f)
+            self.real_mean, self.real_cov, self.real_feats_np = ref["mean"], ref["cov"], ref["feats_np"]
+            self.num_real_feeded = self.real_feats_np.shape[0]
+            feats = np.ascontiguousarray(self.real_feats_np)
+            if feats.dtype not in (np.float32, np.float64):
+                feats = feats.astype(np.float64)
+            self._real_feats = torch.from_numpy(feats).to(self.device)
+
+    def _features(self, batch: torch.Tensor) -> torch.Tensor:
+        if batch.dim() == 2:
+            feats = batch.detach()                                       # already features [n, D]
+        elif self.feature_extractor is None:
+            raise RuntimeError("FIDKID.feed was given images but no feature_extractor: the Inception-v3 network of the reference's evaluation "
+                               "(data/inception-2015-12-05.pt) is not part of this package -- pass feature_extractor= or feed features [n, D]")
+        else:
+            with torch.no_grad():
+                feats = self.feature_extractor(batch).detach()
+        return feats if feats.dtype in (torch.float32, torch.float64) else feats.float()
+
+    def _accumulator(self, mode, feats):
+        from npcd.hip.feature_stats import FeatureMoments
+        if self._moments[mode] is None:
+            # the reals' mean is known before the first fake arrives: the shift that keeps the raw moments from cancelling
+            shift = self.real_mean if mode == "fakes" and self.real_mean is not None else None
+            self._moments[mode] = FeatureMoments(feats.shape[1], feats.device, shift=shift, max_rows=self.num_images,
+                                                 block_rows=self.block_rows)
+        return self._moments[mode]
+
+    def feed(self, batch: torch.Tensor, mode: str):
+        """mode "reals" / "fakes"; at most num_images per side are kept (mmgen Metric.feed)."""
+        if mode not in ("reals", "fakes"):
+            raise ValueError(mode)
+        if mode == "reals" and self.real_feats_np is not None:
+            return 0
+        have = self.num_real_feeded if mode == "reals" else self.num_fake_feeded
+        take = min(batch.shape[0], self.num_images - have)
+        if take <= 0:
+            return 0
+        feats = self._features(batch[:take])
+        self._accumulator(mode, feats).add(feats)
+        if mode == "reals":
+            self.num_real_feeded += take
+        else:
+            self.num_fake_feeded += take
+        return take
+
+    def summary(self):
+        from npcd.hip.feature_stats import kid_from_sums, kid_subsets
+        fakes, reals = self._moments["fakes"], self._moments["reals"]
+        assert fakes is not None and fakes.rows == self.num_images
+        if self._real_feats is None:
+            assert reals is not None and reals.rows >= self.num_images
+            real_feats, real_stats = reals.features(), reals.finalize()
+        else:
+            real_feats, real_stats = self._real_feats, ()
+        fake_feats = fakes.features()
+        fake_mean, fake_cov = fakes.finalize()
+        if real_feats.dtype != fake_feats.dtype:
+            real_feats, fake_feats = real_feats.double(), fake_feats.double()
+        rng = np.random if self.rng is None else self.rng
+        n_fake, n_real = fake_feats.shape[0], real_feats.shape[0]
+        m = min(min(n_real, n_fake), self.max_subset_size)
+        idx_f, idx_r = np.empty((self.num_subsets, m), dtype=np.int64), np.empty((self.num_subsets, m), dtype=np.int64)
+        for s in range(self.num_subsets):
+            idx_f[s] = rng.choice(n_fake, m, replace=False)
+            idx_r[s] = rng.choice(n_real, m, replace=False)
+        sums = kid_subsets(fake_feats, real_feats, idx_f, idx_r)
+        kid = (kid_from_sums(sums, m) * 1000).reshape(1)
+        back = torch.cat([t.reshape(-1) for t in (kid, fake_mean, fake_cov, *real_stats)]).cpu().numpy()          # the one read-back
+        D = fake_mean.shape[0]
+        kid, fake_mean, fake_cov = float(back[0]), back[1:1 + D], back[1 + D:1 + D + D * D].reshape(D, D)
+        if real_stats:
+            rest = back[1 + D + D * D:]
+            self.real_mean, self.real_cov = rest[:D], rest[D:].reshape(D, D)
+        fid, mean, cov = frechet_distance(fake_mean, fake_cov, self.real_mean, self.real_cov)
         self._result_str = f"{fid:.4f} ({mean:.5f}/{cov:.5f}), {kid:.4f}"
         self._result_dict = dict(fid=fid, fid_mean=mean, fid_cov=cov, kid=kid)
         return fid, mean, cov, kid
