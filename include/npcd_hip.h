@@ -24,6 +24,8 @@
 #ifndef NPCD_HIP_H
 #define NPCD_HIP_H
 
+#include <assert.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -47,102 +49,77 @@ const char* npcd_last_hip_error(void);
 /* ------------------------------------------------------------------------------------------
  * Attention over points: out = softmax(q k^T * scale) v, non-causal, no mask, no dropout.
  * Replaces flash_attn_func(q, k, v, causal=False, dropout_p=0) (transformer.py:75) and its
- * autograd backward.  q/k/v are [B, n, H, d] views (typically of one interleaved [B,n,H,3d]
- * buffer, transformer.py:71-72) sharing the stride triple (sb, sn, sh).  Head dims: d = 64 runs the specialised kernels of
- * csrc/attention.hip; d = 32 and d = 128 (ABI 9; the reference's attention takes any width / heads, transformer.py:68-84) run
- * csrc/attention_gen.hip in the 16-bit types, forward and backward (for those the first B H n floats of `delta` hold
- * rowsum(dout * out); no edge scratch is used) and the vector-ALU form of the exact fp32 FORWARD; anything else, and the fp32
- * backward at d != 64, is NPCD_ERR_UNSUPPORTED.
- * lse [B, H, n] fp32 receives log(sum_j exp(scale * <q_i, k_j>)).
+ * autograd backward.  Every entry point takes one argument block; a member an entry point does not use is ignored.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct npcd_attn_args {
+    /* q/k/v: [B, n, H, d] views (typically of one interleaved [B,n,H,3d] buffer, transformer.py:71-72) sharing the qkv strides */
+    const void *q, *k, *v;
+    void* out;        /* [B, n, H, d]: written by the forwards, read by the backwards */
+    float* lse;       /* [B, H, n] fp32, log(sum_j exp(scale * <q_i, k_j>)): written by the forwards, read by the backwards */
+    const void* dout; /* out's strides */
+    void *dq, *dk, *dv;  /* share the g strides */
+    /* fp32 scratch of npcd_attn_bwd_workspace_floats(B, n, H) elements, written by the backward.  First [2, B, H, npad] (npad = n
+     * rounded up to a multiple of 64): the per-row constants the dK/dV pass starts its accumulators from, plane 0 = -lse / scale,
+     * plane 1 = -rowsum(dout * out), pad rows -inf / 0.  Behind them, for sequences of 128 j + 1 tokens (the denoiser's 512 points +
+     * timestep token): 192 floats per (batch, head, 32-row block), the partial sums of the last token's dK / dV / dQ rows (that
+     * token gets no workgroup of its own; csrc/attention.hip, 'the edge token').  The fp32 kernels and head dims 32 / 128 use the
+     * first B H n floats only, for rowsum(dout * out). */
+    float* delta;
+    /* NULL, or the COLUMN SUMS of the packed gradient as a by-product of npcd_attn_bwd (the bias gradient of c_qkv, transformer.py:
+     * 67-72; replaces a separate npcd_colsum_dt pass over dqkv in the fused backbone).  Only for the packed layout (dk = dq + 64
+     * elements, dv = dq + 128, g_sh = 192), the 16-bit types and d = 64, and dq must be given whatever `passes` says.
+     * fp32 [npcd_attn_bwd_colsum_rows(B, n, H) + npcd_colsum_scratch_rows(), 3 H 64]; every wave writes the sums of the ROUNDED
+     * rows it stores (fixed order); finish with npcd_colsum_finalize(colsum_part, rows, 3 H 64, out, ...). */
+    float* colsum_part;
+    /* scratch (uninitialised, 16-byte aligned) whose meaning belongs to the entry point:
+     *   npcd_attn_fwd        NULL, or npcd_attn_fwd_workspace_floats(B, n, H) floats: the row-split scratch
+     *   npcd_attn_fwd_fp8    npcd_attn_fwd_fp8_workspace_bytes(B, n, H) bytes: the e4m3 copies of k and v^T
+     *   npcd_attn_bwd_fused  npcd_attn_bwd_fused_slab_floats(B, n, H) floats (0 for n <= 256: may be NULL): the running dQ */
+    void* workspace;
+    int64_t qkv_sb, qkv_sn, qkv_sh;  /* strides of q / k / v  */
+    int64_t out_sb, out_sn, out_sh;  /* of out / dout         */
+    int64_t g_sb, g_sn, g_sh;        /* of dq / dk / dv       */
+    int32_t B, n, H, d, dtype;
+    float scale;
+} npcd_attn_args;
+static_assert(sizeof(npcd_attn_args) == 192 && offsetof(npcd_attn_args, scale) == 188, "npcd_attn_args is part of the ABI");
+
+/* Forward.  Head dims: d = 64 runs the specialised kernels of csrc/attention.hip; d = 32 and d = 128 (the reference's attention takes
+ * any width / heads, transformer.py:68-84) run csrc/attention_gen.hip in the 16-bit types, forward and backward, and the vector-ALU
+ * form of the exact fp32 FORWARD; anything else, and the fp32 backward at d != 64, is NPCD_ERR_UNSUPPORTED.
  * dtype NPCD_F32 selects the exact-fp32 kernels on the fp32 matrix instruction (the reference's fp32 sampling path,
  * diffusion_model.py:108-133, and `--dtype float32` training through its einsum attention, transformer.py:76-81): nothing is rounded
  * to 16 bits; lse is written when given (may be NULL for inference); strides multiples of 4 elements and 16-byte aligned pointers
- * take the matrix-instruction form, any other layout a vector-ALU form of the forward.  npcd_attn_bwd accepts NPCD_F32 as well
- * (two kernels, dq and dk/dv; `delta` then needs B*H*n floats and is written by the dq kernel).
- * ------------------------------------------------------------------------------------------ */
-int npcd_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
-                  int B, int n, int H, int d,
-                  int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh,
-                  int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                  float scale, int dtype, void* stream);
-
-/* The same with caller-provided scratch (uninitialised): npcd_attn_fwd_workspace_floats(B, n, H) floats, 0 when the shape needs none.
- * Non-zero exactly when the sequence has 256 j + 1 > 256 tokens AND the 64-rows-per-wave form of the forward takes it (n >= 1024, or
- * NPCD_ATTN_FWD=64; the variable is read at every call, by the sizing function too).  With the scratch, that form runs without a
- * workgroup for the last query row: the waves of each (batch, head) split that row's keys and a small second kernel merges their
- * partial softmax states.  workspace == NULL is npcd_attn_fwd. */
+ * take the matrix-instruction form, any other layout a vector-ALU form of the forward.
+ * workspace: npcd_attn_fwd_workspace_floats is non-zero exactly when the sequence has 256 j + 1 > 256 tokens AND the 64-rows-per-wave
+ * form of the forward takes it (n >= 1024, or NPCD_ATTN_FWD=64; the variable is read at every call, by the sizing function too).
+ * With the scratch, that form runs without a workgroup for the last query row: the waves of each (batch, head) split that row's keys
+ * and a small second kernel merges their partial softmax states. */
 int64_t npcd_attn_fwd_workspace_floats(int B, int n, int H);
-int npcd_attn_fwd_ws(const void* q, const void* k, const void* v, void* out, float* lse, float* workspace,
-                     int B, int n, int H, int d,
-                     int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh,
-                     int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                     float scale, int dtype, void* stream);
+int npcd_attn_fwd(const npcd_attn_args* a, void* stream);
 
 /* The same forward with fp8 (e4m3) operands on the block-scaled matrix instruction (v_mfma_scale_f32_32x32x64_f8f6f4; BASELINE
  * configs[4] names fp8 attention; opt-in, csrc/attention.hip attn_fwd_fp8_kernel): k is quantised to e4m3 and v to e4m3
- * transposed by a packing pass into `workspace`, q and P (with a 2^-8 block scale) inside the kernel (npcd_attn_fwd_fp8_workspace_bytes(B, n, H)
- * bytes; 0 = this length is not covered, use npcd_attn_fwd: n or n - 1 must be a multiple of 64).  bf16 only; out / lse as above;
+ * transposed by a packing pass into `workspace`, q and P (with a 2^-8 block scale) inside the kernel.  A workspace size of 0 = this
+ * length is not covered, use npcd_attn_fwd: n or n - 1 must be a multiple of 64.  bf16 only; out / lse as above;
  * the backward is npcd_attn_bwd on the bf16 operands.  Measured slower than the bf16 kernel at head_dim 64. */
 int64_t npcd_attn_fwd_fp8_workspace_bytes(int B, int n, int H);
-int npcd_attn_fwd_fp8(const void* q, const void* k, const void* v, void* out, float* lse, void* workspace,
-                      int B, int n, int H, int d,
-                      int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh,
-                      int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                      float scale, int dtype, void* stream);
+int npcd_attn_fwd_fp8(const npcd_attn_args* a, void* stream);
 
-/* Backward of the above.  dq/dk/dv share (g_sb, g_sn, g_sh); out/dout share the out strides.
- * delta: fp32 scratch of npcd_attn_bwd_workspace_floats(B, n, H) elements, written by the call.  First [2, B, H, npad]
- * (npad = n rounded up to a multiple of 64): the per-row constants the dK/dV pass starts its accumulators from, plane 0 =
- * -lse / scale, plane 1 = -rowsum(dout * out), pad rows -inf / 0.  Behind them, for sequences of 128 j + 1 tokens (the
- * denoiser's 512 points + timestep token): 192 floats per (batch, head, 32-row block), the partial sums of the last token's
- * dK / dV / dQ rows (that token gets no workgroup of its own; csrc/attention.hip, 'the edge token').  Bitwise reproducible. */
+/* Backward of the above, two kernels.  passes: 1 = the dq pass (also writes delta), 2 = the dk/dv pass (reads delta, so pass 1 must
+ * have run), 3 = both; the single passes let a caller time / schedule the two kernels separately.  NPCD_F32 is accepted as well
+ * (d = 64).  Bitwise reproducible, colsum_part included. */
 int64_t npcd_attn_bwd_workspace_floats(int B, int n, int H);
-int npcd_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                  const float* lse, void* dq, void* dk, void* dv, float* delta,
-                  int B, int n, int H, int d,
-                  int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh,
-                  int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                  int64_t g_sb, int64_t g_sn, int64_t g_sh,
-                  float scale, int dtype, void* stream);
-
-/* The backward with the COLUMN SUMS of the packed gradient as a by-product (the bias gradient of c_qkv; replaces the separate
- * npcd_colsum_bf16 pass over dqkv in the fused backbone; reference: nn.Linear bias gradient of c_qkv, transformer.py:67-72).
- * Only for the packed layout (dk = dq + 64 elements, dv = dq + 128, g_sh = 192).  passes: 1 = dq pass, 2 = dk/dv pass, 3 = both.
- * colsum_part: fp32 [npcd_attn_bwd_colsum_rows(B, n, H) + npcd_colsum_scratch_rows(), 3 H 64]; every wave writes the sums of the
- * ROUNDED rows it stores (fixed order); finish with npcd_colsum_finalize(colsum_part, rows, 3 H 64, out, ...).  Bitwise reproducible. */
 int npcd_attn_bwd_colsum_rows(int B, int n, int H);
-int npcd_attn_bwd_colsum(int passes, const void* q, const void* k, const void* v, const void* out, const void* dout,
-                         const float* lse, void* dq, void* dk, void* dv, float* delta, float* colsum_part,
-                         int B, int n, int H, int d,
-                         int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh,
-                         int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                         int64_t g_sb, int64_t g_sn, int64_t g_sh,
-                         float scale, int dtype, void* stream);
-
-/* One pass of the backward on its own: pass 1 = dq (also writes delta), pass 2 = dk/dv (reads delta,
- * so pass 1 must have run).  Same arguments as npcd_attn_bwd.  Lets a caller time / schedule the two
- * kernels separately. */
-int npcd_attn_bwd_pass(int pass, const void* q, const void* k, const void* v, const void* out, const void* dout,
-                       const float* lse, void* dq, void* dk, void* dv, float* delta,
-                       int B, int n, int H, int d,
-                       int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh,
-                       int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                       int64_t g_sb, int64_t g_sn, int64_t g_sh,
-                       float scale, int dtype, void* stream);
+int npcd_attn_bwd(const npcd_attn_args* a, int passes, void* stream);
 
 /* Single-pass backward (csrc/attention.hip, attn_bwd_fused_kernel): the same gradients as npcd_attn_bwd from FIVE matrix products per
  * (query, key) tile instead of seven -- S and dP are formed once, dV / dK are accumulated from them with the keys on the lanes,
  * dS crosses LDS once and dQ is summed over the keys inside the matrix instruction; one workgroup per (batch, head), 256 keys per
- * pass.  dq_slab: fp32 scratch of npcd_attn_bwd_fused_slab_floats(B, n, H) elements (0 for n <= 256: may be NULL), the running
- * dQ between passes.  delta: the [2, B, H, npad] planes above (written by the kernel's prologue).  Bitwise reproducible. */
+ * pass, the running dQ between passes in `workspace`.  delta: the [2, B, H, npad] planes above (written by the kernel's prologue).
+ * 16-bit types, d = 64; colsum_part is not produced.  Bitwise reproducible. */
 int64_t npcd_attn_bwd_fused_slab_floats(int B, int n, int H);
-int npcd_attn_bwd_fused(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                        const float* lse, void* dq, void* dk, void* dv, float* delta, float* dq_slab,
-                        int B, int n, int H, int d,
-                        int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh,
-                        int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                        int64_t g_sb, int64_t g_sn, int64_t g_sh,
-                        float scale, int dtype, void* stream);
+int npcd_attn_bwd_fused(const npcd_attn_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Voxel grid (torch_knnquery.VoxelGrid).  The grid description is passed by value.
@@ -329,18 +306,20 @@ int npcd_ray_march_bwd(const float* sigma, const float* rgb, const uint8_t* slot
 /* ------------------------------------------------------------------------------------------
  * Elementwise / normalisation / optimizer kernels of the denoiser training step (HBM-bound).
  * They fuse the eager op chains of transformer.py:169-172,136-137 (under autocast) and of
- * diffusion_training.py:169-174 + utils/ema.py:114-138.  bf16 tensors are passed as void*.
+ * diffusion_training.py:169-174 + utils/ema.py:114-138.  16-bit tensors are passed as void*; dtype = their type: NPCD_BF16 (bf16
+ * autocast) or NPCD_F16 (float16 autocast with loss scaling -- the reference's default --dtype, train_diffusion.py:78,
+ * train/diffusion_training.py:60-62).
  * ------------------------------------------------------------------------------------------ */
-/* x_out = x_in (+ delta); y = LayerNorm(x_out)*gamma+beta as bf16; mean/rstd [T] saved.
- * delta (bf16 [T,W]) and x_out may be NULL.  W % 4 == 0, W <= 2048. */
-int npcd_add_ln_fwd(const float* x_in, const void* delta, const float* gamma, const float* beta,
-                    float* x_out, void* y, float* mean, float* rstd, int T, int W, float eps, void* stream);
-/* LayerNorm backward: dx = LNbwd(dy) (+ dres), optionally also as bf16 (dxb); column partials
+/* x_out = x_in (+ delta); y = LayerNorm(x_out)*gamma+beta in `dtype`; mean/rstd [T] saved.
+ * delta (`dtype` [T,W]) and x_out may be NULL.  W % 4 == 0, W <= 2048. */
+int npcd_add_ln_fwd_dt(const float* x_in, const void* delta, const float* gamma, const float* beta,
+                       float* x_out, void* y, float* mean, float* rstd, int T, int W, float eps, int dtype, void* stream);
+/* LayerNorm backward: dx = LNbwd(dy) (+ dres), optionally also in `dtype` (dxb); column partials
  * [npcd_ln_bwd_blocks(T)][W] of dgamma, dbeta and of dx (any may be NULL). */
 int npcd_ln_bwd_blocks(int T);
-int npcd_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                const float* dres, float* dx, void* dxb, float* part_gamma, float* part_beta,
-                float* part_col, int T, int W, void* stream);
+int npcd_ln_bwd_dt(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                   const float* dres, float* dx, void* dxb, float* part_gamma, float* part_beta,
+                   float* part_col, int T, int W, int dtype, void* stream);
 /* out[c] (+)= sum_b part[b][c], fixed summation order.  `part` [nblk][N] must be followed by
  * npcd_colsum_scratch_rows() more rows of N floats (used as the stage buffer of the 2-stage sum). */
 int npcd_colsum_scratch_rows(void);
@@ -355,34 +334,19 @@ typedef struct NpcdColsumJob {
     int nblk, N, accumulate, reserved;
 } NpcdColsumJob;
 int npcd_colsum_finalize_batch(const NpcdColsumJob* jobs, int njobs, void* stream);
-/* GELU (exact erf form) on bf16; backward also emits column partials [npcd_colsum_blocks(T)][N] of dh */
-int npcd_gelu_fwd(const void* h, void* g, int64_t numel, void* stream);
+/* GELU (exact erf form); the backward also emits column partials [npcd_colsum_blocks(T)][N] of dh, npcd_colsum_dt those of a [T, N] */
+int npcd_gelu_fwd_dt(const void* h, void* g, int64_t numel, int dtype, void* stream);
 int npcd_colsum_blocks(int T);
-int npcd_gelu_bwd(const void* dg, const void* h, void* dh, float* part, int T, int N, void* stream);
-int npcd_colsum_bf16(const void* a, float* part, int T, int N, void* stream);
+int npcd_gelu_bwd_dt(const void* dg, const void* h, void* dh, float* part, int T, int N, int dtype, void* stream);
+int npcd_colsum_dt(const void* a, float* part, int T, int N, int dtype, void* stream);
 /* Weight gradient of a Linear layer with J <= 4 outputs (the PointNeRF field's heads: fields/mlp.py:38-72, last layers 256 -> 1 and
  * 256 -> 3) over T rows: part [npcd_small_wgrad_blocks(T) + npcd_colsum_scratch_rows(), J * K] fp32 partial sums of
  * dW[j][k] = sum_p dy[p][j] x[p][k] (dy [T, J], x [T, K] bf16 row-major, K a power of two in 64..2048); finish with
  * npcd_colsum_finalize(part, blocks, J * K, dW, ...).  Replaces the library GEMM (350 us for one workgroup's worth of work). */
 int npcd_small_wgrad_blocks(int T);
 int npcd_small_wgrad(const void* dy, const void* x, float* part, int T, int J, int K, void* stream);
-/* AdamW (torch semantics) + EMA lerp + bf16 shadow copy + optional gradient zeroing, one pass.
- * ema and shadow_bf16 may be NULL; step is the 1-based step count (bias correction). */
-int npcd_adamw_ema(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t numel,
-                   float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                   float ema_decay, int zero_grad, void* stream);
-int npcd_cast_f32_bf16(const float* src, void* dst, int64_t numel, void* stream);
-/* The same kernels for either 16-bit activation type of a training run: dtype = NPCD_BF16 (bf16 autocast; the names above) or
- * NPCD_F16 (float16 autocast with loss scaling -- the reference's default --dtype, train_diffusion.py:78,
- * train/diffusion_training.py:60-62).  Same arguments otherwise; shadow_dtype = the type of the 16-bit parameter shadow. */
-int npcd_add_ln_fwd_dt(const float* x_in, const void* delta, const float* gamma, const float* beta,
-                       float* x_out, void* y, float* mean, float* rstd, int T, int W, float eps, int dtype, void* stream);
-int npcd_ln_bwd_dt(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                   const float* dres, float* dx, void* dxb, float* part_gamma, float* part_beta,
-                   float* part_col, int T, int W, int dtype, void* stream);
-int npcd_gelu_fwd_dt(const void* h, void* g, int64_t numel, int dtype, void* stream);
-int npcd_gelu_bwd_dt(const void* dg, const void* h, void* dh, float* part, int T, int N, int dtype, void* stream);
-int npcd_colsum_dt(const void* a, float* part, int T, int N, int dtype, void* stream);
+/* AdamW (torch semantics) + EMA lerp + 16-bit shadow copy + optional gradient zeroing, one pass.
+ * ema and shadow may be NULL; shadow_dtype = the type of the 16-bit parameter shadow; step is the 1-based step count (bias correction). */
 int npcd_adamw_ema_dt(float* p, float* g, float* m, float* v, float* ema, void* shadow, int shadow_dtype, int64_t numel,
                       float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                       float ema_decay, int zero_grad, void* stream);

@@ -41,10 +41,10 @@ struct AttnParams {
     int64_t osb, osn, osh;  // out / dout strides
     int64_t gsb, gsn, gsh;  // dq/dk/dv strides
     float scale, scale_log2;
-    // optional by-product of the backward (npcd_attn_bwd_colsum): per-wave column sums of the stored dq / dk / dv rows, one fp32 row of
+    // optional by-product of the backward (npcd_attn_args::colsum_part): per-wave column sums of the stored dq / dk / dv rows, one fp32 row of
     // 3 H 64 columns (the packed c_qkv order: h, {q, k, v}, d) per (batch, 128-row block, wave) [+ one per batch for the edge token]
     float* colsum;
-    // optional scratch of the forward (npcd_attn_fwd_ws): partial softmax states of the LAST query row of a sequence of 256 j + 1
+    // optional scratch of the forward (npcd_attn_args::workspace): partial softmax states of the LAST query row of a sequence of 256 j + 1
     // tokens, one record of kRowxFloats floats per (batch, head, 64-key tile); see rowx_tile
     float* rowx;
 };
@@ -2221,13 +2221,13 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
     }
 }
 template <int D>
-static int launch_f32_valu(const float* q, const float* k, const float* v, float* out, float* lse, int B, int n, int H, int64_t sb, int64_t sn,
-                           int64_t sh, int64_t osb, int64_t osn, int64_t osh, float scale, hipStream_t st) {
+static int launch_f32_valu(const npcd_attn_args& a, hipStream_t st) {
     constexpr size_t lds = (size_t)(64 * (D + 1) + 64 * D + 16 * D + 16 * 64) * sizeof(float);
     static DynLds attr;
     if (lds > 65536) NPCD_HIP_CHECK(attr.ensure(reinterpret_cast<const void*>(attn_fwd_f32_kernel<D>), lds));
-    hipLaunchKernelGGL(attn_fwd_f32_kernel<D>, dim3(B * H * ceil_div(n, 16)), dim3(256), lds, st, q, k, v, out, lse, B, n, H, sb, sn, sh, osb, osn,
-                       osh, scale);
+    hipLaunchKernelGGL(attn_fwd_f32_kernel<D>, dim3(a.B * a.H * ceil_div(a.n, 16)), dim3(256), lds, st, static_cast<const float*>(a.q),
+                       static_cast<const float*>(a.k), static_cast<const float*>(a.v), static_cast<float*>(a.out), a.lse, a.B, a.n, a.H,
+                       a.qkv_sb, a.qkv_sn, a.qkv_sh, a.out_sb, a.out_sn, a.out_sh, a.scale);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
@@ -2688,22 +2688,37 @@ static int check_layout(std::initializer_list<const void*> required, std::initia
         if (x % 8 != 0) return NPCD_ERR_ARG;
     return NPCD_OK;
 }
-// what the forward and the backward share; the forward adds o_w (and rowx), the backward attn_bwd_params
-static AttnParams attn_params(const void* q, const void* k, const void* v, const float* lse, int B, int n, int H, int64_t qkv_sb, int64_t qkv_sn,
-                              int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh, float scale) {
+// The public argument block -> the parameter structs of the kernels: the one place per struct that knows both layouts.  The optional
+// scratch pointers (colsum, rowx) are set by the launch that has checked them.
+static AttnParams attn_params(const npcd_attn_args& a) {
     AttnParams p{};
-    p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse);
-    p.B = B; p.n = n; p.H = H;
-    p.sb = qkv_sb; p.sn = qkv_sn; p.sh = qkv_sh;
-    p.osb = out_sb; p.osn = out_sn; p.osh = out_sh;
-    p.scale = scale; p.scale_log2 = scale * kLog2e;
+    p.q = a.q; p.k = a.k; p.v = a.v; p.out = a.out; p.dout = a.dout;
+    p.o_w = a.out; p.dq = a.dq; p.dk = a.dk; p.dv = a.dv;
+    p.lse = a.lse; p.delta = a.delta;
+    p.B = a.B; p.n = a.n; p.H = a.H;
+    p.sb = a.qkv_sb; p.sn = a.qkv_sn; p.sh = a.qkv_sh;
+    p.osb = a.out_sb; p.osn = a.out_sn; p.osh = a.out_sh;
+    p.gsb = a.g_sb; p.gsn = a.g_sn; p.gsh = a.g_sh;
+    p.scale = a.scale; p.scale_log2 = a.scale * kLog2e;
     return p;
 }
-static void attn_bwd_params(AttnParams& p, const void* out, const void* dout, void* dq, void* dk, void* dv, float* delta, int64_t g_sb,
-                            int64_t g_sn, int64_t g_sh) {
-    p.out = out; p.dout = dout; p.delta = delta;
-    p.dq = dq; p.dk = dk; p.dv = dv;
-    p.gsb = g_sb; p.gsn = g_sn; p.gsh = g_sh;
+// The fp32 matrix-instruction FORWARD shares the struct of the fp32 backward: it writes `out` through dq and the g strides, lse through delta.
+static AttnF32Bwd attn_f32_params(const npcd_attn_args& a, bool fwd) {
+    AttnF32Bwd p{};
+    p.q = static_cast<const float*>(a.q); p.k = static_cast<const float*>(a.k); p.v = static_cast<const float*>(a.v);
+    p.B = a.B; p.n = a.n; p.H = a.H;
+    p.sb = a.qkv_sb; p.sn = a.qkv_sn; p.sh = a.qkv_sh;
+    p.scale = a.scale;
+    if (fwd) {
+        p.dq = static_cast<float*>(a.out); p.delta = a.lse;
+        p.gsb = a.out_sb; p.gsn = a.out_sn; p.gsh = a.out_sh;
+        return p;
+    }
+    p.o = static_cast<const float*>(a.out); p.dout = static_cast<const float*>(a.dout); p.lse = a.lse;
+    p.dq = static_cast<float*>(a.dq); p.dk = static_cast<float*>(a.dk); p.dv = static_cast<float*>(a.dv); p.delta = a.delta;
+    p.osb = a.out_sb; p.osn = a.out_sn; p.osh = a.out_sh;
+    p.gsb = a.g_sb; p.gsn = a.g_sn; p.gsh = a.g_sh;
+    return p;
 }
 // f(BF16{}) or f(F16{}): the element traits of `dtype` (check_common admits no other)
 template <class F>
@@ -2728,52 +2743,40 @@ extern "C" int64_t npcd_attn_fwd_workspace_floats(int B, int n, int H) {
     return (rowx_mode(n) && !fwd_rows32(n)) ? (int64_t)B * H * ((n - 1) / 64) * kRowxFloats : 0;
 }
 
-static int attn_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, float* workspace, int B, int n, int H, int d,
-                           int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                           float scale, int dtype, void* stream) {
-    if (dtype == NPCD_F32) {   // exact fp32 path (lse [B, H, n] written when given: natural log of the row sums of exp(scaled scores))
-        if (B <= 0 || n <= 0 || H <= 0 || !q || !k || !v || !out) return NPCD_ERR_ARG;
-        if (d == 32 || d == 128) {        // (round 6) the exact vector-ALU form covers the other head dims: forward only (sampling / inference)
-            hipStream_t sv = static_cast<hipStream_t>(stream);
-            const float *fq = static_cast<const float*>(q), *fk = static_cast<const float*>(k), *fv = static_cast<const float*>(v);
-            return d == 32 ? launch_f32_valu<32>(fq, fk, fv, static_cast<float*>(out), lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale, sv)
-                           : launch_f32_valu<128>(fq, fk, fv, static_cast<float*>(out), lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale, sv);
-        }
+static int attn_fwd_launch(const npcd_attn_args& a, void* stream) {
+    const int B = a.B, n = a.n, H = a.H, d = a.d;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (a.dtype == NPCD_F32) {   // exact fp32 path (lse [B, H, n] written when given: natural log of the row sums of exp(scaled scores))
+        if (B <= 0 || n <= 0 || H <= 0 || !a.q || !a.k || !a.v || !a.out) return NPCD_ERR_ARG;
+        // (round 6) the exact vector-ALU form covers the other head dims: forward only (sampling / inference)
+        if (d == 32) return launch_f32_valu<32>(a, st);
+        if (d == 128) return launch_f32_valu<128>(a, st);
         if (d != 64) return NPCD_ERR_UNSUPPORTED;
         static const bool valu_form = getenv("NPCD_ATTN_F32_VALU") != nullptr;
-        const bool vec_ok = !(qkv_sb % 4 || qkv_sn % 4 || qkv_sh % 4 || out_sb % 4 || out_sn % 4 || out_sh % 4) && aligned16(q) &&
-                            aligned16(k) && aligned16(v) && aligned16(out);
-        if (vec_ok && !valu_form) {        // matrix-instruction form (needs 16-byte rows); the vector-ALU form below takes any layout
-            AttnF32Bwd a{};
-            a.q = static_cast<const float*>(q); a.k = static_cast<const float*>(k); a.v = static_cast<const float*>(v);
-            a.dq = static_cast<float*>(out); a.delta = lse;
-            a.B = B; a.n = n; a.H = H; a.sb = qkv_sb; a.sn = qkv_sn; a.sh = qkv_sh; a.gsb = out_sb; a.gsn = out_sn; a.gsh = out_sh;
-            a.scale = scale;
-            hipLaunchKernelGGL(attn_fwd_f32_mfma_kernel, dim3(B * H * ceil_div(n, 128)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-            NPCD_HIP_CHECK(hipGetLastError());
-            return NPCD_OK;
-        }
-        return launch_f32_valu<64>(static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v), static_cast<float*>(out),
-                                   lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale, static_cast<hipStream_t>(stream));
+        const bool vec_ok = !(a.qkv_sb % 4 || a.qkv_sn % 4 || a.qkv_sh % 4 || a.out_sb % 4 || a.out_sn % 4 || a.out_sh % 4) && aligned16(a.q) &&
+                            aligned16(a.k) && aligned16(a.v) && aligned16(a.out);
+        // the vector-ALU form takes any layout, the matrix-instruction form needs 16-byte rows
+        if (!vec_ok || valu_form) return launch_f32_valu<64>(a, st);
+        hipLaunchKernelGGL(attn_fwd_f32_mfma_kernel, dim3(B * H * ceil_div(n, 128)), dim3(256), 0, st, attn_f32_params(a, true));
+        NPCD_HIP_CHECK(hipGetLastError());
+        return NPCD_OK;
     }
     // head dims 32 and 128 (the reference's attention works for any width / heads, transformer.py:68-84): the kernels of
     // attention_gen.hip; NPCD_ATTN_GEN=1 sends d = 64 there too (tests: the two kernel families against each other)
     const bool force_gen = getenv("NPCD_ATTN_GEN") != nullptr;      // (read at every call, like NPCD_ATTN_FWD)
     const bool gen = d != 64 || force_gen;
-    int rc = check_common(B, n, H, gen && attn_gen_supported(d) ? 64 : d, dtype);
+    int rc = check_common(B, n, H, gen && attn_gen_supported(d) ? 64 : d, a.dtype);
     if (rc != NPCD_OK) return rc;
-    rc = check_layout({q, k, v, out, lse}, {q, k, v, out}, {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh});
+    rc = check_layout({a.q, a.k, a.v, a.out, a.lse}, {a.q, a.k, a.v, a.out}, {a.qkv_sb, a.qkv_sn, a.qkv_sh, a.out_sb, a.out_sn, a.out_sh});
     if (rc != NPCD_OK) return rc;
-    if (gen) return attn_gen_fwd(q, k, v, out, lse, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale, dtype, stream);
-    AttnParams p = attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
-    p.o_w = out;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (gen) return attn_gen_fwd(a, stream);
+    AttnParams p = attn_params(a);
     // Two forms of the forward (measured in one process, tools/probes/gpu_dev_fwd_ab.py): 64 query rows per wave wins
     // on long sequences (n = 2049: 597-614 against 640-653 us), 32 rows per wave on short ones, where a workgroup's start-up and
     // wind-down dominate and its finer grid fills the chip better (n = 513: 113 against 117 us).  NPCD_ATTN_FWD=32 / 64 forces one.
     const bool rows32 = fwd_rows32(n);
-    p.rowx = (workspace && !rows32 && rowx_mode(n)) ? workspace : nullptr;
-    for_dtype(dtype, [&](auto tr) {
+    p.rowx = (a.workspace && !rows32 && rowx_mode(n)) ? static_cast<float*>(a.workspace) : nullptr;
+    for_dtype(a.dtype, [&](auto tr) {
         using TR = decltype(tr);
         if (rows32) hipLaunchKernelGGL(attn_fwd_kernel<TR>, dim3(B * H * ceil_div(n, 128)), dim3(256), 0, st, p);
         else hipLaunchKernelGGL(attn_fwd64_kernel<TR>, dim3(B * H * (p.rowx ? (n - 1) / 256 : ceil_div(n, 256))), dim3(256), 0, st, p);
@@ -2783,16 +2786,7 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* ou
     return NPCD_OK;
 }
 
-extern "C" int npcd_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int B, int n, int H, int d,
-                             int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                             float scale, int dtype, void* stream) {
-    return attn_fwd_launch(q, k, v, out, lse, nullptr, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale, dtype, stream);
-}
-extern "C" int npcd_attn_fwd_ws(const void* q, const void* k, const void* v, void* out, float* lse, float* workspace, int B, int n, int H,
-                                int d, int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                                float scale, int dtype, void* stream) {
-    return attn_fwd_launch(q, k, v, out, lse, workspace, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale, dtype, stream);
-}
+extern "C" int npcd_attn_fwd(const npcd_attn_args* a, void* stream) { return a ? attn_fwd_launch(*a, stream) : NPCD_ERR_ARG; }
 
 // fp8 forward (opt-in): workspace = the e4m3 copies of k and v^T
 static int fp8_nk(int n) { return (n & 63) == 1 && n > 64 ? n - 1 : n; }
@@ -2802,23 +2796,23 @@ extern "C" int64_t npcd_attn_fwd_fp8_workspace_bytes(int B, int n, int H) {
     if (nk % 64 != 0) return 0;              // length not covered: use npcd_attn_fwd
     return (int64_t)B * H * 64 * 2 * (int64_t)nk;
 }
-extern "C" int npcd_attn_fwd_fp8(const void* q, const void* k, const void* v, void* out, float* lse, void* workspace, int B, int n, int H,
-                                 int d, int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                                 float scale, int dtype, void* stream) {
-    int rc = npcd::check_common(B, n, H, d, dtype);
+extern "C" int npcd_attn_fwd_fp8(const npcd_attn_args* a, void* stream) {
+    if (!a) return NPCD_ERR_ARG;
+    const int B = a->B, n = a->n, H = a->H;
+    int rc = check_common(B, n, H, a->d, a->dtype);
     if (rc != NPCD_OK) return rc;
-    if (dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
+    if (a->dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
     const int nk = fp8_nk(n);
     if (nk % 64 != 0) return NPCD_ERR_UNSUPPORTED;
-    rc = npcd::check_layout({q, k, v, out, lse, workspace}, {q, k, v, out, workspace}, {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh});
+    rc = check_layout({a->q, a->k, a->v, a->out, a->lse, a->workspace}, {a->q, a->k, a->v, a->out, a->workspace},
+                      {a->qkv_sb, a->qkv_sn, a->qkv_sh, a->out_sb, a->out_sn, a->out_sh});
     if (rc != NPCD_OK) return rc;
-    npcd::AttnParams p = npcd::attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
-    p.o_w = out;
-    unsigned char* k8 = static_cast<unsigned char*>(workspace);
+    const AttnParams p = attn_params(*a);
+    unsigned char* k8 = static_cast<unsigned char*>(a->workspace);
     unsigned char* v8t = k8 + (int64_t)B * H * nk * 64;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(npcd::attn_fp8_pack_kernel, dim3(B * H * (nk / 64)), dim3(256), 0, st, p, k8, v8t, nk);
-    hipLaunchKernelGGL(npcd::attn_fwd_fp8_kernel, dim3(B * H * npcd::ceil_div(n, 128)), dim3(256), 0, st, p, k8, v8t, nk);
+    hipLaunchKernelGGL(attn_fp8_pack_kernel, dim3(B * H * (nk / 64)), dim3(256), 0, st, p, k8, v8t, nk);
+    hipLaunchKernelGGL(attn_fwd_fp8_kernel, dim3(B * H * ceil_div(n, 128)), dim3(256), 0, st, p, k8, v8t, nk);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
@@ -2878,62 +2872,52 @@ extern "C" int npcd_attn_bwd_colsum_rows(int B, int n, int H) {
     return npcd::edge_mode(n) ? B * ((n >> 7) * 4 + 1) : B * npcd::ceil_div(n, 128) * 4;
 }
 
-static int attn_bwd_launch(int passes, const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
-                           void* dq, void* dk, void* dv, float* delta, int B, int n, int H, int d,
-                           int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                           int64_t g_sb, int64_t g_sn, int64_t g_sh, float scale, int dtype, void* stream, float* colsum = nullptr) {
-    if (dtype == NPCD_F32) {
-        if (B <= 0 || n <= 0 || H <= 0 || !q || !k || !v || !out || !dout || !lse || !delta || colsum) return NPCD_ERR_ARG;
+static int attn_bwd_launch(const npcd_attn_args& a, int passes, void* stream) {
+    const int B = a.B, n = a.n, H = a.H, d = a.d;
+    float* const colsum = a.colsum_part;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool no_grad = ((passes & 1) && !a.dq) || ((passes & 2) && (!a.dk || !a.dv));      // an output of a requested pass is missing
+    if (a.dtype == NPCD_F32) {
+        if (B <= 0 || n <= 0 || H <= 0 || !a.q || !a.k || !a.v || !a.out || !a.dout || !a.lse || !a.delta || colsum) return NPCD_ERR_ARG;
         if (d != 64) return NPCD_ERR_UNSUPPORTED;
-        if (((passes & 1) && !dq) || ((passes & 2) && (!dk || !dv))) return NPCD_ERR_ARG;
-        const int64_t strides[] = {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, g_sb, g_sn, g_sh};
-        for (int64_t x : strides)
+        if (no_grad) return NPCD_ERR_ARG;
+        for (int64_t x : {a.qkv_sb, a.qkv_sn, a.qkv_sh, a.out_sb, a.out_sn, a.out_sh, a.g_sb, a.g_sn, a.g_sh})
             if (x % 4 != 0) return NPCD_ERR_ARG;
-        if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) ||
-            !aligned16(dv))
-            return NPCD_ERR_ARG;
-        AttnF32Bwd a{static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v),
-                     static_cast<const float*>(out), static_cast<const float*>(dout), lse,
-                     static_cast<float*>(dq), static_cast<float*>(dk), static_cast<float*>(dv), delta, B, n, H,
-                     qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, g_sb, g_sn, g_sh, scale};
+        for (const void* x : std::initializer_list<const void*>{a.q, a.k, a.v, a.out, a.dout, a.dq, a.dk, a.dv})
+            if (!aligned16(x)) return NPCD_ERR_ARG;
+        const AttnF32Bwd p = attn_f32_params(a, false);
         const int grid = B * H * ceil_div(n, 128);
-        hipStream_t st32 = static_cast<hipStream_t>(stream);
-        if (passes & 1) hipLaunchKernelGGL(attn_bwd_f32_dq_kernel, dim3(grid), dim3(256), 0, st32, a);      // also writes delta
-        if (passes & 2) hipLaunchKernelGGL(attn_bwd_f32_dkdv_kernel, dim3(grid), dim3(256), 0, st32, a);
+        if (passes & 1) hipLaunchKernelGGL(attn_bwd_f32_dq_kernel, dim3(grid), dim3(256), 0, st, p);      // also writes delta
+        if (passes & 2) hipLaunchKernelGGL(attn_bwd_f32_dkdv_kernel, dim3(grid), dim3(256), 0, st, p);
         NPCD_HIP_CHECK(hipGetLastError());
         return NPCD_OK;
     }
     const bool force_gen = getenv("NPCD_ATTN_GEN") != nullptr;      // (read at every call, like NPCD_ATTN_FWD)
     const bool gen = d != 64 || (force_gen && !colsum);
-    int rc = check_common(B, n, H, gen && attn_gen_supported(d) ? 64 : d, dtype);
+    int rc = check_common(B, n, H, gen && attn_gen_supported(d) ? 64 : d, a.dtype);
     if (rc != NPCD_OK) return rc;
-    rc = check_layout({q, k, v, out, dout, lse, delta}, {q, k, v, out, dout, dq, dk, dv},
-                      {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, g_sb, g_sn, g_sh});
+    rc = check_layout({a.q, a.k, a.v, a.out, a.dout, a.lse, a.delta}, {a.q, a.k, a.v, a.out, a.dout, a.dq, a.dk, a.dv},
+                      {a.qkv_sb, a.qkv_sn, a.qkv_sh, a.out_sb, a.out_sn, a.out_sh, a.g_sb, a.g_sn, a.g_sh});
     if (rc != NPCD_OK) return rc;
-    if ((passes & 1) && !dq) return NPCD_ERR_ARG;
-    if ((passes & 2) && (!dk || !dv)) return NPCD_ERR_ARG;
+    if (no_grad) return NPCD_ERR_ARG;
     if (gen) {
         if (colsum) return NPCD_ERR_UNSUPPORTED;        // the column-sum by-product belongs to the d = 64 kernels (the fused backbone)
-        return attn_gen_bwd(passes, q, k, v, out, dout, lse, dq, dk, dv, delta, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh,
-                            g_sb, g_sn, g_sh, scale, dtype, stream);
+        return attn_gen_bwd(a, passes, stream);
     }
-    AttnParams p = attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
-    attn_bwd_params(p, out, dout, dq, dk, dv, delta, g_sb, g_sn, g_sh);
+    AttnParams p = attn_params(a);
     if (colsum) {       // only for the packed c_qkv gradient: [.., H, (dq | dk | dv) x 64]
         const size_t es = 2;
-        if (g_sh != 192 || (dk && reinterpret_cast<const char*>(dk) != reinterpret_cast<const char*>(dq) + 64 * es) ||
-            (dv && reinterpret_cast<const char*>(dv) != reinterpret_cast<const char*>(dq) + 128 * es) || !aligned16(colsum))
-            return NPCD_ERR_ARG;
+        const char* dq = static_cast<const char*>(a.dq);
+        if (a.g_sh != 192 || (a.dk && a.dk != dq + 64 * es) || (a.dv && a.dv != dq + 128 * es) || !aligned16(colsum)) return NPCD_ERR_ARG;
         p.colsum = colsum;
     }
     const bool edge = edge_mode(n);
     const int grid = B * H * (edge ? n >> 7 : ceil_div(n, 128));
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const int dyn = 3 * kDkdvSlot;
     static DynLds lds_bf16, lds_f16;
     NPCD_HIP_CHECK(lds_bf16.ensure(reinterpret_cast<const void*>(attn_bwd_dkdv_kernel<BF16>), dyn));
     NPCD_HIP_CHECK(lds_f16.ensure(reinterpret_cast<const void*>(attn_bwd_dkdv_kernel<F16>), dyn));
-    for_dtype(dtype, [&](auto tr) {
+    for_dtype(a.dtype, [&](auto tr) {
         using TR = decltype(tr);
         if (passes & 1) hipLaunchKernelGGL(attn_bwd_dq_kernel<TR>, dim3(grid), dim3(256), 0, st, p);
         if (passes & 2) hipLaunchKernelGGL(attn_bwd_dkdv_kernel<TR>, dim3(grid), dim3(256), dyn, st, p);
@@ -2943,58 +2927,36 @@ static int attn_bwd_launch(int passes, const void* q, const void* k, const void*
     return NPCD_OK;
 }
 
+// passes: 1 = the dq pass (also writes delta), 2 = the dk/dv pass, 3 = both.  The column sums of a.colsum_part are those of the packed
+// gradient, whose first block is dq: it is needed for the layout check whichever pass runs.
+extern "C" int npcd_attn_bwd(const npcd_attn_args* a, int passes, void* stream) {
+    if (!a || passes < 1 || passes > 3 || (a->colsum_part && !a->dq)) return NPCD_ERR_ARG;
+    return attn_bwd_launch(*a, passes, stream);
+}
+
 extern "C" int64_t npcd_attn_bwd_fused_slab_floats(int B, int n, int H) {
     if (B <= 0 || n <= 0 || H <= 0) return -1;
     return n <= 256 ? 0 : (int64_t)B * H * ((n + 63) / 64 * 64) * 64;
 }
 
-// The single-pass backward (attn_bwd_fused_kernel): same arguments as npcd_attn_bwd + dq_slab, an fp32 scratch of
-// npcd_attn_bwd_fused_slab_floats(B, n, H) elements (may be NULL when that is 0).
-extern "C" int npcd_attn_bwd_fused(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
-                                   void* dq, void* dk, void* dv, float* delta, float* dq_slab, int B, int n, int H, int d,
-                                   int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                                   int64_t g_sb, int64_t g_sn, int64_t g_sh, float scale, int dtype, void* stream) {
-    int rc = check_common(B, n, H, d, dtype);
+// The single-pass backward (attn_bwd_fused_kernel): workspace = the dQ slab, an fp32 scratch of npcd_attn_bwd_fused_slab_floats(B, n, H)
+// elements (may be NULL when that is 0).
+extern "C" int npcd_attn_bwd_fused(const npcd_attn_args* a, void* stream) {
+    if (!a) return NPCD_ERR_ARG;
+    int rc = check_common(a->B, a->n, a->H, a->d, a->dtype);
     if (rc != NPCD_OK) return rc;
-    rc = check_layout({q, k, v, out, dout, lse, delta, dq, dk, dv}, {q, k, v, out, dout, dq, dk, dv, dq_slab},
-                      {qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, g_sb, g_sn, g_sh});
+    rc = check_layout({a->q, a->k, a->v, a->out, a->dout, a->lse, a->delta, a->dq, a->dk, a->dv},
+                      {a->q, a->k, a->v, a->out, a->dout, a->dq, a->dk, a->dv, a->workspace},
+                      {a->qkv_sb, a->qkv_sn, a->qkv_sh, a->out_sb, a->out_sn, a->out_sh, a->g_sb, a->g_sn, a->g_sh});
     if (rc != NPCD_OK) return rc;
-    if (n > 256 && !dq_slab) return NPCD_ERR_ARG;
-    AttnParams p = attn_params(q, k, v, lse, B, n, H, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh, scale);
-    attn_bwd_params(p, out, dout, dq, dk, dv, delta, g_sb, g_sn, g_sh);
+    if (a->n > 256 && !a->workspace) return NPCD_ERR_ARG;
+    const AttnParams p = attn_params(*a);
+    float* dq_slab = static_cast<float*>(a->workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
     static DynLds lds_bf16, lds_f16;
     NPCD_HIP_CHECK(lds_bf16.ensure(reinterpret_cast<const void*>(attn_bwd_fused_kernel<BF16>), kFLds));
     NPCD_HIP_CHECK(lds_f16.ensure(reinterpret_cast<const void*>(attn_bwd_fused_kernel<F16>), kFLds));
-    for_dtype(dtype, [&](auto tr) { hipLaunchKernelGGL(attn_bwd_fused_kernel<decltype(tr)>, dim3(B * H), dim3(512), kFLds, st, p, dq_slab); });
+    for_dtype(a->dtype, [&](auto tr) { hipLaunchKernelGGL(attn_bwd_fused_kernel<decltype(tr)>, dim3(a->B * a->H), dim3(512), kFLds, st, p, dq_slab); });
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
-}
-
-extern "C" int npcd_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
-                             void* dq, void* dk, void* dv, float* delta, int B, int n, int H, int d,
-                             int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                             int64_t g_sb, int64_t g_sn, int64_t g_sh, float scale, int dtype, void* stream) {
-    return attn_bwd_launch(3, q, k, v, out, dout, lse, dq, dk, dv, delta, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh,
-                           g_sb, g_sn, g_sh, scale, dtype, stream);
-}
-
-// npcd_attn_bwd / npcd_attn_bwd_pass with the column sums of the packed gradient as a by-product: colsum_part [rows + scratch, 3 H 64]
-// fp32, rows = npcd_attn_bwd_colsum_rows(B, n, H) -- finished by npcd_colsum_finalize(colsum_part, rows, 3 H 64, bias_grad, ...).
-extern "C" int npcd_attn_bwd_colsum(int passes, const void* q, const void* k, const void* v, const void* out, const void* dout,
-                                    const float* lse, void* dq, void* dk, void* dv, float* delta, float* colsum_part, int B, int n, int H, int d,
-                                    int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                                    int64_t g_sb, int64_t g_sn, int64_t g_sh, float scale, int dtype, void* stream) {
-    if (passes < 1 || passes > 3 || !colsum_part || !dq) return NPCD_ERR_ARG;
-    return attn_bwd_launch(passes, q, k, v, out, dout, lse, dq, dk, dv, delta, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh,
-                           g_sb, g_sn, g_sh, scale, dtype, stream, colsum_part);
-}
-
-extern "C" int npcd_attn_bwd_pass(int pass, const void* q, const void* k, const void* v, const void* out, const void* dout,
-                                  const float* lse, void* dq, void* dk, void* dv, float* delta, int B, int n, int H, int d,
-                                  int64_t qkv_sb, int64_t qkv_sn, int64_t qkv_sh, int64_t out_sb, int64_t out_sn, int64_t out_sh,
-                                  int64_t g_sb, int64_t g_sn, int64_t g_sh, float scale, int dtype, void* stream) {
-    if (pass != 1 && pass != 2) return NPCD_ERR_ARG;
-    return attn_bwd_launch(pass, q, k, v, out, dout, lse, dq, dk, dv, delta, B, n, H, d, qkv_sb, qkv_sn, qkv_sh, out_sb, out_sn, out_sh,
-                           g_sb, g_sn, g_sh, scale, dtype, stream);
 }

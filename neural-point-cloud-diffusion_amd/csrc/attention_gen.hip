@@ -367,44 +367,39 @@ int launch_bwd(const GenParams& p, int passes, hipStream_t st) {
     return NPCD_OK;
 }
 
-GenParams make_params(const void* q, const void* k, const void* v, int B, int n, int H, int64_t sb, int64_t sn, int64_t sh, int64_t osb,
-                      int64_t osn, int64_t osh, float scale) {
+// the one place that knows both layouts: the public argument block -> the kernels' parameter struct
+GenParams make_params(const npcd_attn_args& a) {
     GenParams p{};
-    p.q = q; p.k = k; p.v = v;
-    p.B = B; p.n = n; p.H = H;
-    p.sb = sb; p.sn = sn; p.sh = sh;
-    p.osb = osb; p.osn = osn; p.osh = osh;
-    p.scale = scale; p.scale_log2 = scale * kLog2e;
+    p.q = a.q; p.k = a.k; p.v = a.v; p.out = a.out; p.dout = a.dout;
+    p.o_w = a.out; p.dq = a.dq; p.dk = a.dk; p.dv = a.dv;
+    p.lse = a.lse; p.delta = a.delta;
+    p.B = a.B; p.n = a.n; p.H = a.H;
+    p.sb = a.qkv_sb; p.sn = a.qkv_sn; p.sh = a.qkv_sh;
+    p.osb = a.out_sb; p.osn = a.out_sn; p.osh = a.out_sh;
+    p.gsb = a.g_sb; p.gsn = a.g_sn; p.gsh = a.g_sh;
+    p.scale = a.scale; p.scale_log2 = a.scale * kLog2e;
     return p;
 }
+
+// f<TR, D>(...) for the head dim a.d and the element traits of a.dtype
+#define NPCD_GEN_DTYPE(f, D, ...) (a.dtype == NPCD_BF16 ? f<BF16, D>(__VA_ARGS__) : f<F16, D>(__VA_ARGS__))
+#define NPCD_GEN_DISPATCH(f, ...) \
+    (a.d == 32 ? NPCD_GEN_DTYPE(f, 32, __VA_ARGS__) : a.d == 64 ? NPCD_GEN_DTYPE(f, 64, __VA_ARGS__) : NPCD_GEN_DTYPE(f, 128, __VA_ARGS__))
+
+bool supported(const npcd_attn_args& a) { return attn_gen_supported(a.d) && (a.dtype == NPCD_BF16 || a.dtype == NPCD_F16); }
 
 }  // namespace
 
 bool attn_gen_supported(int d) { return d == 32 || d == 64 || d == 128; }
 
-int attn_gen_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int B, int n, int H, int d, int64_t sb, int64_t sn,
-                 int64_t sh, int64_t osb, int64_t osn, int64_t osh, float scale, int dtype, void* stream) {
-    if (!attn_gen_supported(d) || (dtype != NPCD_BF16 && dtype != NPCD_F16)) return NPCD_ERR_UNSUPPORTED;
-    GenParams p = make_params(q, k, v, B, n, H, sb, sn, sh, osb, osn, osh, scale);
-    p.o_w = out; p.lse = lse;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define NPCD_GEN_FWD(DD) (dtype == NPCD_BF16 ? launch_fwd<BF16, DD>(p, st) : launch_fwd<F16, DD>(p, st))
-    return d == 32 ? NPCD_GEN_FWD(32) : d == 64 ? NPCD_GEN_FWD(64) : NPCD_GEN_FWD(128);
-#undef NPCD_GEN_FWD
+int attn_gen_fwd(const npcd_attn_args& a, void* stream) {
+    if (!supported(a)) return NPCD_ERR_UNSUPPORTED;
+    return NPCD_GEN_DISPATCH(launch_fwd, make_params(a), static_cast<hipStream_t>(stream));
 }
 
-int attn_gen_bwd(int passes, const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, void* dq, void* dk,
-                 void* dv, float* delta, int B, int n, int H, int d, int64_t sb, int64_t sn, int64_t sh, int64_t osb, int64_t osn, int64_t osh,
-                 int64_t gsb, int64_t gsn, int64_t gsh, float scale, int dtype, void* stream) {
-    if (!attn_gen_supported(d) || (dtype != NPCD_BF16 && dtype != NPCD_F16)) return NPCD_ERR_UNSUPPORTED;
-    GenParams p = make_params(q, k, v, B, n, H, sb, sn, sh, osb, osn, osh, scale);
-    p.out = out; p.dout = dout; p.lse = const_cast<float*>(lse); p.delta = delta;
-    p.dq = dq; p.dk = dk; p.dv = dv;
-    p.gsb = gsb; p.gsn = gsn; p.gsh = gsh;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define NPCD_GEN_BWD(DD) (dtype == NPCD_BF16 ? launch_bwd<BF16, DD>(p, passes, st) : launch_bwd<F16, DD>(p, passes, st))
-    return d == 32 ? NPCD_GEN_BWD(32) : d == 64 ? NPCD_GEN_BWD(64) : NPCD_GEN_BWD(128);
-#undef NPCD_GEN_BWD
+int attn_gen_bwd(const npcd_attn_args& a, int passes, void* stream) {
+    if (!supported(a)) return NPCD_ERR_UNSUPPORTED;
+    return NPCD_GEN_DISPATCH(launch_bwd, make_params(a), passes, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace npcd

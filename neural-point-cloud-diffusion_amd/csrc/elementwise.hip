@@ -844,10 +844,6 @@ extern "C" int npcd_add_ln_fwd_dt(const float* x_in, const void* delta, const fl
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
-extern "C" int npcd_add_ln_fwd(const float* x_in, const void* delta, const float* gamma, const float* beta, float* x_out, void* y,
-                               float* mean, float* rstd, int T, int W, float eps, void* stream) {
-    return npcd_add_ln_fwd_dt(x_in, delta, gamma, beta, x_out, y, mean, rstd, T, W, eps, NPCD_BF16, stream);
-}
 
 extern "C" int npcd_ln_bwd_blocks(int T) { const int r = ln_rows_per_wave(T); return (T + 4 * r - 1) / (4 * r); }
 
@@ -902,10 +898,6 @@ extern "C" int npcd_ln_bwd_split3_bf16(const float* dy, const float* x, const fl
     return NPCD_OK;
 }
 
-extern "C" int npcd_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* dres,
-                           float* dx, void* dxb, float* part_gamma, float* part_beta, float* part_col, int T, int W, void* stream) {
-    return npcd_ln_bwd_dt(dy, x, mean, rstd, gamma, dres, dx, dxb, part_gamma, part_beta, part_col, T, W, NPCD_BF16, stream);
-}
 
 // One-launch form (round 6): a workgroup of 1,024 threads = 64 columns x 16 row lanes; lane r adds rows r, r + 16, ... of its column
 // (two accumulators), the 16 lane sums are added through LDS in a fixed tree.  One launch instead of two, no stage buffer; the
@@ -1001,7 +993,6 @@ extern "C" int npcd_gelu_fwd_dt(const void* h, void* g, int64_t numel, int dtype
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
-extern "C" int npcd_gelu_fwd(const void* h, void* g, int64_t numel, void* stream) { return npcd_gelu_fwd_dt(h, g, numel, NPCD_BF16, stream); }
 
 extern "C" int npcd_colsum_blocks(int T) { const int r = col_rows(T); return (T + r - 1) / r; }
 
@@ -1023,9 +1014,6 @@ extern "C" int npcd_gelu_bwd_dt(const void* dg, const void* h, void* dh, float* 
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
-extern "C" int npcd_gelu_bwd(const void* dg, const void* h, void* dh, float* part, int T, int N, void* stream) {
-    return npcd_gelu_bwd_dt(dg, h, dh, part, T, N, NPCD_BF16, stream);
-}
 
 extern "C" int npcd_colsum_dt(const void* a, float* part, int T, int N, int dtype, void* stream) {
     if (!a || !part || T <= 0 || N <= 0) return NPCD_ERR_ARG;
@@ -1040,7 +1028,6 @@ extern "C" int npcd_colsum_dt(const void* a, float* part, int T, int N, int dtyp
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
-extern "C" int npcd_colsum_bf16(const void* a, float* part, int T, int N, void* stream) { return npcd_colsum_dt(a, part, T, N, NPCD_BF16, stream); }
 
 extern "C" int npcd_small_wgrad_blocks(int T) { return T <= 0 ? -1 : (T + 255) / 256 < 1024 ? (T + 255) / 256 : 1024; }
 
@@ -1086,10 +1073,6 @@ extern "C" int npcd_adamw_ema_dt(float* p, float* g, float* m, float* v, float* 
                            static_cast<V<__bf16>::x4*>(shadow), n4, a, zero_grad);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
-}
-extern "C" int npcd_adamw_ema(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t numel, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, int step, float ema_decay, int zero_grad, void* stream) {
-    return npcd_adamw_ema_dt(p, g, m, v, ema, shadow_bf16, NPCD_BF16, numel, lr, beta1, beta2, eps, weight_decay, step, ema_decay, zero_grad, stream);
 }
 
 extern "C" int npcd_adamw_ema_gated(float* p, float* g, float* m, float* v, float* ema, void* shadow, int shadow_dtype, int64_t numel, float lr,
@@ -1321,4 +1304,3 @@ extern "C" int npcd_cast_f32_dt(const float* src, void* dst, int64_t numel, int 
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
-extern "C" int npcd_cast_f32_bf16(const float* src, void* dst, int64_t numel, void* stream) { return npcd_cast_f32_dt(src, dst, numel, NPCD_BF16, stream); }

@@ -34,24 +34,21 @@ SIGNATURES = {
     "npcd_abi_version": (c_int, []),
     "npcd_error_string": (c_char_p, [c_int]),
     "npcd_last_hip_error": (c_char_p, []),
-    "npcd_attn_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int] + [c_int64] * 6 + [c_float, c_int, _P]),
+    "npcd_attn_fwd": (c_int, [_P, _P]),               # (npcd_attn_args*, stream): attention.AttnArgs by reference
     "npcd_attn_fwd_workspace_floats": (c_int64, [c_int, c_int, c_int]),
-    "npcd_attn_fwd_ws": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int] + [c_int64] * 6 + [c_float, c_int, _P]),
     "npcd_ray_march_bwd": (c_int, [_P] * 8 + [c_int, c_int, c_int] + [_P] * 6 + [_P]),
     "npcd_leaky_bwd_blocks": (c_int, [c_int64]),
     "npcd_leaky_bwd_colsum": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_float, c_int, _P]),
     "npcd_pair_input_fwd": (c_int, [_P] * 5 + [c_int, c_int, c_int64, _P, _P, _P]),
     "npcd_pair_input_bwd": (c_int, [_P, _P, c_int, c_int, c_int64, _P, _P]),
     "npcd_pair_aggregate": (c_int, [c_int, _P, _P, _P, _P, c_int, c_int64, _P, _P]),
-    "npcd_attn_bwd": (c_int, [_P] * 10 + [c_int] * 4 + [c_int64] * 9 + [c_float, c_int, _P]),
+    "npcd_attn_bwd": (c_int, [_P, c_int, _P]),
     "npcd_attn_bwd_workspace_floats": (c_int64, [c_int, c_int, c_int]),
     "npcd_attn_bwd_colsum_rows": (c_int, [c_int, c_int, c_int]),
-    "npcd_attn_bwd_colsum": (c_int, [c_int] + [_P] * 11 + [c_int] * 4 + [c_int64] * 9 + [c_float, c_int, _P]),
     "npcd_attn_fwd_fp8_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
-    "npcd_attn_fwd_fp8": (c_int, [_P] * 6 + [c_int] * 4 + [c_int64] * 6 + [c_float, c_int, _P]),
+    "npcd_attn_fwd_fp8": (c_int, [_P, _P]),
     "npcd_attn_bwd_fused_slab_floats": (c_int64, [c_int, c_int, c_int]),
-    "npcd_attn_bwd_fused": (c_int, [_P] * 11 + [c_int] * 4 + [c_int64] * 9 + [c_float, c_int, _P]),
-    "npcd_attn_bwd_pass": (c_int, [c_int] + [_P] * 10 + [c_int] * 4 + [c_int64] * 9 + [c_float, c_int, _P]),
+    "npcd_attn_bwd_fused": (c_int, [_P, _P]),
     "npcd_grid_workspace_bytes": (c_int64, [POINTER(GridParams), c_int, c_int]),
     "npcd_grid_build": (c_int, [POINTER(GridParams), _P, _P, c_int, c_int, _P, _P]),
     "npcd_grid_query": (c_int, [POINTER(GridParams), _P, _P] + [c_int] * 6 + [c_float, c_int] + [_P] * 9 + [_P]),
@@ -82,20 +79,13 @@ SIGNATURES = {
     "npcd_ray_march_ws_floats": (c_int64, [c_int]),
     "npcd_ray_gen_ws_floats": (c_int64, [c_int, c_int, c_int]),
     "npcd_ray_march": (c_int, [_P] * 8 + [c_int, c_int, c_int] + [_P] * 4 + [_P]),
-    "npcd_add_ln_fwd": (c_int, [_P] * 8 + [c_int, c_int, c_float, _P]),
     "npcd_ln_bwd_blocks": (c_int, [c_int]),
-    "npcd_ln_bwd": (c_int, [_P] * 11 + [c_int, c_int, _P]),
     "npcd_colsum_scratch_rows": (c_int, []),
     "npcd_colsum_finalize": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
     "npcd_colsum_finalize_batch": (c_int, [_P, c_int, _P]),
     "npcd_ddpm_reverse_step": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P, _P, _P, _P, _P, c_float, c_float, c_int, _P]),
     "npcd_sampler_step": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "npcd_gelu_fwd": (c_int, [_P, _P, c_int64, _P]),
     "npcd_colsum_blocks": (c_int, [c_int]),
-    "npcd_gelu_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
-    "npcd_colsum_bf16": (c_int, [_P, _P, c_int, c_int, _P]),
-    "npcd_adamw_ema": (c_int, [_P] * 6 + [c_int64] + [c_float] * 5 + [c_int, c_float, c_int, _P]),
-    "npcd_cast_f32_bf16": (c_int, [_P, _P, c_int64, _P]),
     "npcd_add_ln_fwd_dt": (c_int, [_P] * 8 + [c_int, c_int, c_float, c_int, _P]),
     "npcd_ln_bwd_dt": (c_int, [_P] * 11 + [c_int, c_int, c_int, _P]),
     "npcd_gelu_fwd_dt": (c_int, [_P, _P, c_int64, c_int, _P]),

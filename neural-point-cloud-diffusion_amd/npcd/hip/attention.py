@@ -4,11 +4,30 @@
 c_qkv output in place (transformer.py:71-72) and its backward writes one packed gradient buffer.
 `flash_attn_func` keeps the third-party signature the reference imports (transformer.py:9-12,75).
 """
+import ctypes
 import math
+from ctypes import c_float, c_int32, c_int64, c_void_p
 
 import torch
 
-from . import arena, check, dtype_code, lib, ptr, require_gpu, stream_ptr
+from . import arena, check, dtype_code, lib, require_gpu, stream_ptr
+
+
+class AttnArgs(ctypes.Structure):
+    """struct npcd_attn_args (include/npcd_hip.h): the one argument block of the attention entry points."""
+    _fields_ = ([(name, c_void_p) for name in ("q", "k", "v", "out", "lse", "dout", "dq", "dk", "dv", "delta", "colsum_part", "workspace")]
+                + [(name, c_int64) for name in ("qkv_sb", "qkv_sn", "qkv_sh", "out_sb", "out_sn", "out_sh", "g_sb", "g_sn", "g_sh")]
+                + [(name, c_int32) for name in ("B", "n", "H", "d", "dtype")] + [("scale", c_float)])
+
+
+def _args(q, k, v, out, lse, scale, dout=None, dq=None, dk=None, dv=None, delta=None, colsum_part=None, workspace=None):
+    """The argument block of one call, by reference.  q / k / v share one stride set, out / dout another, dq / dk / dv a third (the
+    callers assert it); absent tensors are NULL.  It holds addresses, not tensors: the caller keeps them alive until the launch."""
+    B, n, H, d = q.shape
+    (qb, qn, qh, _), (ob, on, oh, _) = q.stride(), out.stride()
+    gb, gn, gh, _ = dq.stride() if dq is not None else (0, 0, 0, 1)
+    return ctypes.byref(AttnArgs(*(None if t is None else t.data_ptr() for t in (q, k, v, out, lse, dout, dq, dk, dv, delta, colsum_part, workspace)),
+                                 qb, qn, qh, ob, on, oh, gb, gn, gh, B, n, H, d, dtype_code(q), scale))
 
 
 def _fwd(q, k, v, scale):
@@ -22,15 +41,13 @@ def _fwd(q, k, v, scale):
         nbytes = lib().npcd_attn_fwd_fp8_workspace_bytes(B, n, H)
         if nbytes > 0:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-            check(_timed("fwd", lambda: lib().npcd_attn_fwd_fp8(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(ws), B, n, H, d,
-                                                                q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1),
-                                                                out.stride(2), scale, dtype_code(q), stream_ptr())), "npcd_attn_fwd_fp8")
+            a = _args(q, k, v, out, lse, scale, workspace=ws)
+            check(_timed("fwd", lambda: lib().npcd_attn_fwd_fp8(a, stream_ptr())), "npcd_attn_fwd_fp8")
             return out, lse
     nws = lib().npcd_attn_fwd_workspace_floats(B, n, H) if FWD_WS else 0
     ws = arena.empty(nws, torch.float32, q.device) if nws > 0 else None
-    check(_timed("fwd", lambda: lib().npcd_attn_fwd_ws(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(ws), B, n, H, d,
-                                                       q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1),
-                                                       out.stride(2), scale, dtype_code(q), stream_ptr())), "npcd_attn_fwd_ws")
+    a = _args(q, k, v, out, lse, scale, workspace=ws)
+    check(_timed("fwd", lambda: lib().npcd_attn_fwd(a, stream_ptr())), "npcd_attn_fwd")
     return out, lse
 
 
@@ -79,27 +96,16 @@ def _bwd(q, k, v, out, dout, lse, dq, dk, dv, scale, colsum_part=None):
     if BWD_MODE == "fused":
         nslab = lib().npcd_attn_bwd_fused_slab_floats(B, n, H)
         slab = torch.empty(nslab, dtype=torch.float32, device=q.device) if nslab > 0 else None
-        check(_timed("bwd", lambda: lib().npcd_attn_bwd_fused(
-            ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(dq), ptr(dk), ptr(dv), ptr(delta), ptr(slab), B, n, H, d,
-            q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2), dq.stride(0), dq.stride(1), dq.stride(2),
-            scale, dtype_code(q), stream_ptr())), "npcd_attn_bwd_fused")
+        a = _args(q, k, v, out, lse, scale, dout, dq, dk, dv, delta, workspace=slab)
+        check(_timed("bwd", lambda: lib().npcd_attn_bwd_fused(a, stream_ptr())), "npcd_attn_bwd_fused")
         return
-    args = (ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(dq), ptr(dk), ptr(dv),
-            ptr(delta), B, n, H, d, q.stride(0), q.stride(1), q.stride(2),
-            out.stride(0), out.stride(1), out.stride(2), dq.stride(0), dq.stride(1), dq.stride(2),
-            scale, dtype_code(q), stream_ptr())
-    if colsum_part is not None:       # column sums of the packed gradient as a by-product (csrc/attention.hip, AttnParams::colsum)
-        cargs = args[:10] + (ptr(colsum_part),) + args[10:]
-        if KERNEL_EVENTS is None:
-            check(lib().npcd_attn_bwd_colsum(3, *cargs), "npcd_attn_bwd_colsum")
-        else:
-            check(_timed("dq", lambda: lib().npcd_attn_bwd_colsum(1, *cargs)), "npcd_attn_bwd_colsum(dq)")
-            check(_timed("dkdv", lambda: lib().npcd_attn_bwd_colsum(2, *cargs)), "npcd_attn_bwd_colsum(dkdv)")
-    elif KERNEL_EVENTS is None:
-        check(lib().npcd_attn_bwd(*args), "npcd_attn_bwd")
+    # colsum_part: column sums of the packed gradient as a by-product (csrc/attention.hip, AttnParams::colsum)
+    a = _args(q, k, v, out, lse, scale, dout, dq, dk, dv, delta, colsum_part)
+    if KERNEL_EVENTS is None:
+        check(lib().npcd_attn_bwd(a, 3, stream_ptr()), "npcd_attn_bwd")
     else:
-        check(_timed("dq", lambda: lib().npcd_attn_bwd_pass(1, *args)), "npcd_attn_bwd_pass(dq)")
-        check(_timed("dkdv", lambda: lib().npcd_attn_bwd_pass(2, *args)), "npcd_attn_bwd_pass(dkdv)")
+        check(_timed("dq", lambda: lib().npcd_attn_bwd(a, 1, stream_ptr())), "npcd_attn_bwd(dq)")
+        check(_timed("dkdv", lambda: lib().npcd_attn_bwd(a, 2, stream_ptr())), "npcd_attn_bwd(dkdv)")
 
 
 def _check_input(x):
@@ -114,8 +120,7 @@ def _fwd_f32(q, k, v, scale, want_lse=False):
         raise RuntimeError(f"HIP attention is built for head dims 32, 64 and 128 (got head dim {d})")
     out = torch.empty((B, n, H, d), dtype=torch.float32, device=q.device)
     lse = torch.empty((B, H, n), dtype=torch.float32, device=q.device) if want_lse else None
-    check(lib().npcd_attn_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), B, n, H, d, q.stride(0), q.stride(1), q.stride(2),
-                              out.stride(0), out.stride(1), out.stride(2), scale, dtype_code(q), stream_ptr()), "npcd_attn_fwd(f32)")
+    check(lib().npcd_attn_fwd(_args(q, k, v, out, lse, scale), stream_ptr()), "npcd_attn_fwd(f32)")
     return (out, lse) if want_lse else out
 
 
@@ -130,9 +135,7 @@ def _bwd_f32(q, k, v, out, dout, lse, dq, dk, dv, scale):
     B, n, H, d = q.shape
     assert q.stride() == k.stride() == v.stride() and dq.stride() == dk.stride() == dv.stride() and dout.stride() == out.stride()
     delta = torch.empty(lib().npcd_attn_bwd_workspace_floats(B, n, H), dtype=torch.float32, device=q.device)
-    check(lib().npcd_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(dq), ptr(dk), ptr(dv), ptr(delta),
-                              B, n, H, d, q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2),
-                              dq.stride(0), dq.stride(1), dq.stride(2), scale, dtype_code(q), stream_ptr()), "npcd_attn_bwd(f32)")
+    check(lib().npcd_attn_bwd(_args(q, k, v, out, lse, scale, dout, dq, dk, dv, delta), 3, stream_ptr()), "npcd_attn_bwd(f32)")
 
 
 class _AttnF32(torch.autograd.Function):

@@ -197,7 +197,7 @@ def test_header_exports_and_signatures_agree_for_the_new_names():
     assert len(hip.SIGNATURES["npcd_moments_update"][1]) == 10 and len(hip.SIGNATURES["npcd_moments_finish"][1]) == 8
     assert len(hip.SIGNATURES["npcd_kid_subsets"][1]) == 15
     assert re.search(r"#define NPCD_F64 3\b", header) and hip.NPCD_F64 == 3
-    assert L.npcd_abi_version() == 9
+    assert L.npcd_abi_version() == 10
 
 
 # ---- the kernels' resources ----------------------------------------------------------------------------------------------------------------------

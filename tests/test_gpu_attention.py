@@ -202,8 +202,9 @@ def test_attention_edge_token_extremes(n):
 
 @pytest.mark.parametrize("n", [129, 200, 513])
 def test_backward_passes_launched_separately_match_the_single_call(n, monkeypatch):
-    """npcd_attn_bwd_pass(1) then (2) -- what bench.py times -- against npcd_attn_bwd: the same kernels, bitwise equal gradients
-    (for 128 j + 1 tokens pass 2 also launches the kernel that finishes the last token's three rows from both passes' partials)."""
+    """npcd_attn_bwd with passes = 1, then with passes = 2 -- what bench.py times -- against one call with passes = 3: the same kernels,
+    bitwise equal gradients (for 128 j + 1 tokens pass 2 also launches the kernel that finishes the last token's three rows from both
+    passes' partials)."""
     from npcd.hip import attention as A
     gen = torch.Generator().manual_seed(n)
     qkv = torch.randn(2, n, 3 * 2 * 64, generator=gen).bfloat16()
@@ -217,7 +218,7 @@ def test_backward_passes_launched_separately_match_the_single_call(n, monkeypatc
 
 @pytest.mark.parametrize("n", [40, 65, 129, 193, 200, 513])
 def test_backward_column_sums_by_product(n):
-    """npcd_attn_bwd_colsum: the column sums of the packed dqkv (the c_qkv bias gradient) from the backward's own row stores --
+    """npcd_attn_bwd with colsum_part: the column sums of the packed dqkv (the c_qkv bias gradient) from the backward's own row stores --
     against the sum of the stored bf16 gradient (fp32 accumulation; order differs: 1e-5 of the column's absolute sum) and with
     gradients bitwise equal to the plain call; ragged blocks (waves without rows) and the edge token's rows included."""
     from npcd.hip import attention as A
@@ -240,6 +241,37 @@ def test_backward_column_sums_by_product(n):
     want, scale_ = flat.sum(0), flat.abs().sum(0)
     assert torch.isfinite(got).all()
     assert float(((got - want).abs() / scale_.clamp_min(1e-6)).max()) < 1e-5
+
+
+@pytest.mark.parametrize("n", [129, 200])
+def test_backward_column_sums_with_the_passes_launched_separately(n, monkeypatch):
+    """The merged backward with the column-sum by-product, passes = 1 then passes = 2 (KERNEL_EVENTS set, as bench.py runs it) against
+    the single call with passes = 3, in the edge-token regime (129) and the plain one (200): bitwise equal gradients and bitwise equal
+    finished column sums; the partial buffer starts as NaN in both runs, so every partial row is written by the pass that owns it."""
+    from npcd.hip import attention as A
+    from npcd.hip import elementwise as ew
+    B, H, d = 3, 2, 64
+    gen = torch.Generator().manual_seed(n)
+    qkv = torch.randn(B, n, H, 3 * d, generator=gen).bfloat16().cuda()
+    dout = torch.randn(B, n, H, d, generator=gen).bfloat16().cuda()
+    q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+    out, lse = A._fwd(q, k, v, 0.125)
+
+    def backward():
+        g = torch.zeros_like(qkv)
+        part, rows = A.colsum_part_for(g[..., :d])
+        part.fill_(float("nan"))
+        A._bwd(q, k, v, out, dout, lse, g[..., :d], g[..., d:2 * d], g[..., 2 * d:], 0.125, colsum_part=part)
+        sums = torch.empty(3 * H * d, device="cuda")
+        ew._finish(None, part, rows, 3 * H * d, sums)
+        return g, sums
+
+    g3, s3 = backward()
+    monkeypatch.setattr(A, "KERNEL_EVENTS", {t: [] for t in A.KERNEL_TAGS})
+    g12, s12 = backward()
+    assert len(A.KERNEL_EVENTS["dq"]) == 1 and len(A.KERNEL_EVENTS["dkdv"]) == 1
+    assert torch.isfinite(s3).all() and torch.isfinite(g3.float()).all()
+    assert torch.equal(g3, g12) and torch.equal(s3, s12)
 
 
 @pytest.mark.parametrize("n,B", [(128, 2), (513, 2), (2049, 1)])

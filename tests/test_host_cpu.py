@@ -1,6 +1,7 @@
 """CPU-only checks of the host side: C-ABI library loads and exports every declared symbol,
 module trees / state_dict keys mirror the reference, host math equals the oracle, and the product
 path refuses to run without a GPU (no silent fallback)."""
+import ctypes
 import os
 import re
 
@@ -22,7 +23,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, name), f"libnpcd_hip.so does not export {name}"
     assert declared == set(hip.SIGNATURES), (declared ^ set(hip.SIGNATURES))
     assert L.npcd_missing == (), f"stale library, missing {L.npcd_missing}"
-    assert L.npcd_abi_version() == 9
+    assert L.npcd_abi_version() == 10
     assert L.npcd_ray_march_ws_floats(16384) >= 2 and L.npcd_ray_march_ws_floats(0) == -1
     assert L.npcd_ray_gen_ws_floats(1, 128, 0) == 4 + 2 * 64 and L.npcd_ray_gen_ws_floats(2, 128, 100) == 4 + 2 and L.npcd_ray_gen_ws_floats(0, 128, 0) == -1
     assert L.npcd_error_string(-2).decode() == "unsupported shape or dtype"
@@ -58,6 +59,65 @@ def test_attention_forward_workspace_size(monkeypatch):
     assert f(B, 513, H) == B * H * 8 * 68
     monkeypatch.setenv("NPCD_ATTN_FWD", "32")
     assert f(B, 2049, H) == 0
+
+
+def test_attention_argument_block_layout():
+    """AttnArgs mirrors struct npcd_attn_args: its size and the offset of its last member are the literals of the header's static_assert."""
+    from npcd.hip.attention import AttnArgs
+    header = open(os.path.join(ROOT, "include", "npcd_hip.h")).read()
+    size, last, offset = re.search(r"static_assert\(sizeof\(npcd_attn_args\) == (\d+) && offsetof\(npcd_attn_args, (\w+)\) == (\d+)", header).groups()
+    assert AttnArgs._fields_[-1][0] == last
+    assert (ctypes.sizeof(AttnArgs), getattr(AttnArgs, last).offset) == (int(size), int(offset)) == (192, 188)
+
+
+def _attn_args(dtype=0, B=2, n=64, H=2, d=64, qkv_sn=None, null=(), **over):
+    """An argument block whose pointers are made-up 16-byte aligned addresses: the checks under test return before anything is
+    launched or dereferenced.  Packed layout: q | k | v and dq | dk | dv interleaved per head."""
+    from npcd.hip.attention import AttnArgs
+    es = 4 if dtype == 2 else 2
+    ptrs = dict(q=0x10000, k=0x10000 + d * es, v=0x10000 + 2 * d * es, out=0x20000, lse=0x30000, dout=0x40000,
+                dq=0x50000, dk=0x50000 + d * es, dv=0x50000 + 2 * d * es, delta=0x60000, colsum_part=None, workspace=None)
+    ptrs.update(over)
+    ptrs.update({name: None for name in null})
+    sn = H * 3 * d
+    return AttnArgs(qkv_sb=n * sn, qkv_sn=sn if qkv_sn is None else qkv_sn, qkv_sh=3 * d, out_sb=n * H * d, out_sn=H * d, out_sh=d,
+                    g_sb=n * sn, g_sn=sn, g_sh=3 * d, B=B, n=n, H=H, d=d, dtype=dtype, scale=0.125, **ptrs)
+
+
+ERR_ARG, ERR_UNSUPPORTED = -1, -2
+BF16, F16, F32 = 0, 1, 2
+
+
+def test_attention_entry_points_check_their_arguments():
+    """Every argument check of the four attention entry points answers before the first HIP call, with the code the header names."""
+    from npcd import hip
+    L, ref = hip.lib(), ctypes.byref
+    assert L.npcd_attn_fwd(None, None) == ERR_ARG
+    assert L.npcd_attn_fwd(ref(_attn_args(B=0)), None) == ERR_ARG
+    assert L.npcd_attn_fwd(ref(_attn_args(d=48)), None) == ERR_UNSUPPORTED
+    assert L.npcd_attn_fwd(ref(_attn_args(qkv_sn=4)), None) == ERR_ARG
+
+    assert L.npcd_attn_bwd(None, 3, None) == ERR_ARG
+    for passes in (0, 4):
+        assert L.npcd_attn_bwd(ref(_attn_args()), passes, None) == ERR_ARG
+    assert L.npcd_attn_bwd(ref(_attn_args(colsum_part=0x70000, null=("dq",))), 2, None) == ERR_ARG
+    assert L.npcd_attn_bwd(ref(_attn_args(dtype=F32, colsum_part=0x70000)), 3, None) == ERR_ARG
+    assert L.npcd_attn_bwd(ref(_attn_args(d=32, colsum_part=0x70000)), 3, None) == ERR_UNSUPPORTED
+    # the layout conditions of the column sums: 192 elements per head, dk and dv 64 and 128 elements behind dq, 16-byte alignment
+    assert L.npcd_attn_bwd(ref(_attn_args(colsum_part=0x70000, dk=0x58000)), 3, None) == ERR_ARG
+    assert L.npcd_attn_bwd(ref(_attn_args(colsum_part=0x70000, dv=0x58000)), 3, None) == ERR_ARG
+    assert L.npcd_attn_bwd(ref(_attn_args(colsum_part=0x70004)), 3, None) == ERR_ARG
+    assert L.npcd_attn_bwd(ref(_attn_args(null=("dk",))), 2, None) == ERR_ARG            # an output of the requested pass is missing
+    assert L.npcd_attn_bwd(ref(_attn_args(null=("delta",))), 3, None) == ERR_ARG
+
+    assert L.npcd_attn_fwd_fp8(None, None) == ERR_ARG
+    assert L.npcd_attn_fwd_fp8(ref(_attn_args(dtype=F16, workspace=0x80000)), None) == ERR_UNSUPPORTED
+    assert L.npcd_attn_fwd_fp8(ref(_attn_args(n=100, workspace=0x80000)), None) == ERR_UNSUPPORTED
+    assert L.npcd_attn_fwd_fp8(ref(_attn_args()), None) == ERR_ARG                        # no workspace
+
+    assert L.npcd_attn_bwd_fused(None, None) == ERR_ARG
+    assert L.npcd_attn_bwd_fused(ref(_attn_args(n=257)), None) == ERR_ARG                 # n > 256 needs the dQ slab
+    assert L.npcd_attn_bwd_fused(ref(_attn_args(dtype=F32)), None) == ERR_UNSUPPORTED
 
 
 def test_no_cpu_fallback():
