@@ -780,6 +780,35 @@ int64_t npcd_kid_workspace_bytes(int S, int m);
 int npcd_kid_subsets(const void* fake, const void* real, int dtype, int Nf, int Nr, int D, int64_t ldf, int64_t ldr, const int32_t* idx_f,
                      const int32_t* idx_r, int S, int m, double* workspace, double* out, void* stream);
 
+/* ---- feature k-NN: the radii and ball counts behind precision / recall and density / coverage -------------------------------------------
+ * (csrc/feature_manifold.hip).  x [n, D] and y [m, D] are features on the device, dtype NPCD_F32 or NPCD_F64 (one for
+ * both), a row stride in elements (>= D) and unit column stride, only read; y may be x.  All arithmetic is float64 on the float64 matrix
+ * instruction:
+ *   d2_ij = max((nx_i + ny_j) - 2 g_ij, +0),   g_ij = x_i . y_j,   nx_i = x_i . x_i,   ny_j = y_j . y_j,
+ * evaluated as written.  Columns j >= m do not exist; with exclude_self = 1 the pair j == i does not exist either (by index, not by
+ * value).  The distances are streamed tile by tile and never stored.
+ *
+ * npcd_feature_knn: out [n, k] float64 = the k smallest d2_ij of every row i, ascending, equal values kept (a multiset), fully
+ *   written.  1 <= k <= npcd_feature_knn_max_k() (8).
+ * npcd_feature_ball_counts: rho_y float64 [m];  cnt[i] = #{j : d2_ij < rho_y[j]} (int32 [n], strict),  near[i] = min_j d2_ij
+ *   (float64 [n]), fully written.
+ * splits: workgroups per block of 64 rows of x, each taking a contiguous range of the 64-row tiles of y; 0 lets the library choose
+ *   from n and m, a value above the number of tiles (or above 256) is lowered to it.  The results are the same bits for every value
+ *   and on every run: no atomics, no fence; the partial results of the splits are merged by a second small launch in a fixed order.
+ * workspace: npcd_feature_rows_workspace_bytes(n, m, k, splits) bytes (k = 0: for the ball counts), 8-byte aligned, contents
+ *   irrelevant before and after: 8 (n + m) for the norms, plus 8 S n k (k-NN) or 16 S n (ball counts) for the partial results when
+ *   the S splits in effect are more than one.
+ *
+ * NPCD_ERR_UNSUPPORTED for D < 1 or D > 4,096, a dtype other than the two, k out of range, m - exclude_self < k, n < 1, m < 1, n or
+ * m > 2^24, splits < 0 and exclude_self other than 0 / 1 (the workspace query returns it too), before any pointer is looked at;
+ * NPCD_ERR_ARG for a NULL pointer or a row stride below D.  Nothing is launched in either case. */
+int npcd_feature_knn_max_k(void);
+int64_t npcd_feature_rows_workspace_bytes(int n, int m, int k, int splits);
+int npcd_feature_knn(const void* x, const void* y, int dtype, int n, int m, int D, int64_t ldx, int64_t ldy, int exclude_self, int k,
+                     int splits, double* workspace, double* out, void* stream);
+int npcd_feature_ball_counts(const void* x, const void* y, int dtype, int n, int m, int D, int64_t ldx, int64_t ldy, const double* rho_y,
+                             int splits, double* workspace, int32_t* cnt, double* near, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,9 @@ SOURCES = {
     # the feature statistics evaluate their float64 epilogues as written (cov from the raw moments, the cubic kernel): the exact-integer
     # tests and cov == cov.T rest on it; the products themselves are the float64 matrix instruction's
     "feature_stats.hip": ["-ffp-contract=off"],
+    # the feature k-NN forms d2 = max((nx + ny) - 2 g, +0) and the squares of the norms as written: the exact-integer tests and "the same
+    # bits for every split" rest on it
+    "feature_manifold.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

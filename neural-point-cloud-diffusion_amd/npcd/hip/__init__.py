@@ -150,6 +150,10 @@ SIGNATURES = {
     "npcd_kid_tile": (c_int, [POINTER(c_int)]),
     "npcd_kid_workspace_bytes": (c_int64, [c_int, c_int]),
     "npcd_kid_subsets": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, c_int, _P, _P, _P]),
+    "npcd_feature_knn_max_k": (c_int, []),
+    "npcd_feature_rows_workspace_bytes": (c_int64, [c_int] * 4),
+    "npcd_feature_knn": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, _P, _P, _P]),
+    "npcd_feature_ball_counts": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, c_int, _P, _P, _P, _P]),
 }
 
 _lib = None
