@@ -6,6 +6,9 @@ Tolerances (bf16 inputs, fp32 accumulation, P rounded to bf16 before P.V as in f
   backward : rel-L2 <= 2e-2
   denoiser : eps rel-L2 <= 2e-2 vs the reference's fp32 golden output (SURVEY.md §7 step 4 measured
              7e-3 for the reference's own bf16-autocast path)
+
+These are whole-tensor bars.  The 16-bit kernels are also held to per-element bounds at every tile-count regime in
+tests/test_gpu_attention_bounds.py (docs/experiments.md R26.1 has the derivation and the measured errors).
 """
 import math
 
