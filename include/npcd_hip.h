@@ -491,6 +491,26 @@ typedef struct NpcdSamplerTensor {
 int npcd_sampler_step(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const int64_t* t, const float* table, int T,
                       int B, int deterministic, void* stream);
 
+/* The same step with per-point keeping (completion, local edits).  Tensors are fp32 [B, channels, n_points] with the point index
+ * fastest (what the denoiser takes; per_sample = channels * n_points); keep_coords / keep_feats are bytes [B, n_points], non-zero =
+ * the point is kept, shared by all channels of the tensor.
+ *   mask NULL : that tensor follows its `mode` exactly as in npcd_sampler_step (the same bits).
+ *   mask given: x_t, eps, noise and known must all be given; `mode` is ignored; n_points must divide per_sample.  Per element of
+ *        point p:  out = keep[b, p] ? h1[t] known + h2[t] noise : (the reverse step of npcd_sampler_step),
+ *        the kept branch with the bits of NPCD_SAMPLER_HOLD and the free branch with the bits of NPCD_SAMPLER_REVERSE on the same
+ *        operands.  The clip and x0 belong to free points; x0_out (may be NULL) receives `known` at kept points.  The branches are
+ *        SELECTED, not blended: `known` at free points and x_t / eps at kept points may hold anything, NaN included, and do not
+ *        reach an output.  With `deterministic` non-zero the s[t] noise term of free points is skipped, as a reverse tensor without
+ *        noise skips it; the noise is still required, for the kept points.
+ * Both tensors go in ONE launch on the grid rule of npcd_sampler_step (at most 1024 workgroups per sample and tensor); no atomics: the
+ * same bits on every run.  A masked tensor moves 16 bytes per lane, and reads the four mask bytes of its four points at once, when
+ * n_points is a multiple of 4, the mask pointer is 4-byte aligned and its pointers are 16-byte aligned (8 bytes for bf16 eps);
+ * otherwise one element per lane.  NPCD_ERR_ARG for a missing operand, n_points <= 0 or a per_sample of a masked tensor that n_points
+ * does not divide; NPCD_ERR_UNSUPPORTED as for npcd_sampler_step; both before any launch. */
+int npcd_sampler_step_keep(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const uint8_t* keep_coords,
+                           const uint8_t* keep_feats, int64_t n_points, const int64_t* t, const float* table, int T, int B,
+                           int deterministic, void* stream);
+
 /* Forward process and training loss of the DDPM, fused (reference gaussian_diffusion.py:68-76 q_sample, :199-230 p_losses):
  *   npcd_q_sample    : x_t = tab_sqrt_acp[t_b] * x_0 + tab_sqrt_1macp[t_b] * noise, fp32 [B, per_sample], t int64 [B]; the products
  *                      and the sum are rounded separately like the reference's eager ops (bit-identical to them)

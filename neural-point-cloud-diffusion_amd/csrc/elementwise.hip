@@ -11,7 +11,8 @@
 //   AdamW + EMA + bf16 weight shadow + gradient zeroing           -> adamw_ema (1 pass over 310 M params)
 //   GradScaler + clip_grad_norm_ bookkeeping on the device        -> grad_stats, scaler_finalize, adamw_ema_gated
 // and of the sampler (gaussian_diffusion.py:100-146): the DDPM reverse step per tensor -> ddpm_reverse; a step of the scheduled sampler
-// (strided DDIM levels, eta, one tensor held), both tensors in one launch          -> sampler_step
+// (strided DDIM levels, eta, one tensor held), both tensors in one launch          -> sampler_step; the same step with a per-point
+// mask that keeps some points of a tensor (completion, local edits)               -> sampler_step_keep
 // All are pure streaming kernels: 16-byte accesses per lane, fp32 math, no LDS except the cross-wave
 // reduction of column partials.  Roofline: HBM.
 #include <math.h>
@@ -783,11 +784,8 @@ __device__ __forceinline__ void sampler_hold(const NpcdSamplerTensor& a, const S
     }
 }
 
-__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerArgs args, const int64_t* __restrict__ t, const float* __restrict__ table, int T) {
-    const int z = blockIdx.z, b = blockIdx.y;
-    const NpcdSamplerTensor& a = args.tz[z];
-    const int vec = args.vec[z];
-    // (blocks of the wider tensor's grid that lie past this tensor's range fall through their loop)
+// the seven coefficients of sample b: its table row, or NaN for a timestep outside [0, T)
+__device__ __forceinline__ SamplerCoef sampler_coef(const int64_t* __restrict__ t, const float* __restrict__ table, int T, int b) {
     const int64_t ts = t[b];
     const float nan = __builtin_nanf("");
     SamplerCoef k{nan, nan, nan, nan, nan, nan, nan};
@@ -795,7 +793,11 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerArgs args, con
         const f32x4 lo = reinterpret_cast<const f32x4*>(table)[2 * ts], hi = reinterpret_cast<const f32x4*>(table)[2 * ts + 1];
         k = SamplerCoef{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2]};
     }
-    const int64_t base = (int64_t)b * a.per_sample;
+    return k;
+}
+
+// one tensor by its mode
+__device__ __forceinline__ void sampler_by_mode(const NpcdSamplerTensor& a, int vec, const SamplerCoef& k, int64_t base) {
     if (a.mode == NPCD_SAMPLER_HOLD) {
         if (vec) sampler_hold<true>(a, k, base);
         else sampler_hold<false>(a, k, base);
@@ -805,6 +807,94 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerArgs args, con
     } else {
         if (vec) sampler_reverse<__bf16, true>(a, k, base);
         else sampler_reverse<__bf16, false>(a, k, base);
+    }
+}
+
+__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerArgs args, const int64_t* __restrict__ t, const float* __restrict__ table, int T) {
+    const int z = blockIdx.z, b = blockIdx.y;
+    const NpcdSamplerTensor& a = args.tz[z];
+    // (blocks of the wider tensor's grid that lie past this tensor's range fall through their loop)
+    sampler_by_mode(a, args.vec[z], sampler_coef(t, table, T, b), (int64_t)b * a.per_sample);
+}
+
+// Per-point keeping (npcd_sampler_step_keep): tensors are [B, channels, n_points], `keep` is this sample's mask row, one byte per
+// point.  Every element computes both parents with their own expressions and SELECTS: kept points take the hold expression, free
+// points the reverse step (clip and x0 are theirs alone; x0_out of a kept point is `known`).  A select, never a blend: what is
+// loaded for the branch not taken (NaN included) does not reach an output.  `det`: the s z term of free points is skipped, as a
+// reverse tensor without noise skips it.  The 16-byte path reads the four mask bytes of its four points as one dword (n_points % 4
+// == 0 and a 4-byte aligned mask: an item never straddles a channel row); the point index of an item is taken in 32 bits when it fits.
+__device__ __forceinline__ int64_t sampler_col(int64_t i, int64_t n) {
+    return ((uint64_t)(i | n) >> 32) == 0 ? (int64_t)((uint32_t)i % (uint32_t)n) : i % n;
+}
+
+template <class EPS, bool VEC>
+__device__ __forceinline__ void sampler_keep(const NpcdSamplerTensor& a, const uint8_t* __restrict__ keep, int64_t n_points, int det,
+                                             const SamplerCoef& k, int64_t base) {
+    const float* __restrict__ x_t = a.x_t + base;
+    const EPS* __restrict__ eps = static_cast<const EPS*>(a.eps) + base;
+    const float* __restrict__ noise = a.noise + base;
+    const float* __restrict__ known = a.known + base;
+    float* __restrict__ out = a.out + base;
+    float* __restrict__ x0_out = a.x0_out ? a.x0_out + base : nullptr;
+    if constexpr (VEC) {
+        const int64_t n4 = a.per_sample / 4, row4 = n_points / 4;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+            const uint32_t m = reinterpret_cast<const uint32_t*>(keep)[sampler_col(i, row4)];
+            const f32x4 x = reinterpret_cast<const f32x4*>(x_t)[i];
+            const f32x4 e = to_f32(reinterpret_cast<const typename V<EPS>::x4*>(eps)[i]);
+            const f32x4 z = reinterpret_cast<const f32x4*>(noise)[i], kn = reinterpret_cast<const f32x4*>(known)[i];
+            f32x4 x0, o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float f0 = sampler_x0(k, x[q], e[q], a.has_clip, a.clip_lo, a.clip_hi);
+                float fo = __builtin_fmaf(k.c1, f0, k.c2 * x[q]);
+                if (!det) fo = __builtin_fmaf(k.s, z[q], fo);
+                const bool kept = ((m >> (8 * q)) & 0xffu) != 0;
+                x0[q] = kept ? kn[q] : f0;
+                o[q] = kept ? __builtin_fmaf(k.h1, kn[q], k.h2 * z[q]) : fo;
+            }
+            if (x0_out) reinterpret_cast<f32x4*>(x0_out)[i] = x0;
+            reinterpret_cast<f32x4*>(out)[i] = o;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256) {
+            const bool kept = keep[sampler_col(i, n_points)] != 0;
+            const float x = x_t[i], z = noise[i], kn = known[i];
+            const float f0 = sampler_x0(k, x, (float)eps[i], a.has_clip, a.clip_lo, a.clip_hi);
+            float fo = __builtin_fmaf(k.c1, f0, k.c2 * x);
+            if (!det) fo = __builtin_fmaf(k.s, z, fo);
+            if (x0_out) x0_out[i] = kept ? kn : f0;
+            out[i] = kept ? __builtin_fmaf(k.h1, kn, k.h2 * z) : fo;
+        }
+    }
+}
+
+struct SamplerKeepArgs {
+    NpcdSamplerTensor tz[2];
+    const uint8_t* keep[2];          // [B, n_points] or null: that tensor goes by its mode
+    int64_t n_points;
+    int vec[2];
+    int det;
+};
+
+__global__ __launch_bounds__(256) void sampler_step_keep_kernel(SamplerKeepArgs args, const int64_t* __restrict__ t, const float* __restrict__ table,
+                                                                int T) {
+    const int z = blockIdx.z, b = blockIdx.y;
+    const NpcdSamplerTensor& a = args.tz[z];
+    const int vec = args.vec[z];
+    const SamplerCoef k = sampler_coef(t, table, T, b);
+    const int64_t base = (int64_t)b * a.per_sample;
+    if (!args.keep[z]) {
+        sampler_by_mode(a, vec, k, base);
+        return;
+    }
+    const uint8_t* keep = args.keep[z] + (int64_t)b * args.n_points;
+    if (a.eps_dtype == NPCD_F32) {
+        if (vec) sampler_keep<float, true>(a, keep, args.n_points, args.det, k, base);
+        else sampler_keep<float, false>(a, keep, args.n_points, args.det, k, base);
+    } else {
+        if (vec) sampler_keep<__bf16, true>(a, keep, args.n_points, args.det, k, base);
+        else sampler_keep<__bf16, false>(a, keep, args.n_points, args.det, k, base);
     }
 }
 
@@ -1146,6 +1236,31 @@ extern "C" int npcd_ddpm_reverse_step(const float* x_t, const void* eps, int eps
     return NPCD_OK;
 }
 
+// One tensor of npcd_sampler_step by its mode: the operands it needs, whether it takes the 16-byte path
+static int sampler_check_mode(const NpcdSamplerTensor& a, int deterministic, bool* vec_out) {
+    if (!a.out || a.per_sample <= 0) return NPCD_ERR_ARG;
+    bool vec = a.per_sample % 4 == 0 && al16(a.out);
+    if (a.mode == NPCD_SAMPLER_HOLD) {
+        if (!a.known || !a.noise) return NPCD_ERR_ARG;
+        vec = vec && al16(a.known) && al16(a.noise);
+    } else if (a.mode == NPCD_SAMPLER_REVERSE) {
+        if (!a.x_t || !a.eps || (!a.noise && !deterministic)) return NPCD_ERR_ARG;
+        if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
+        vec = vec && al16(a.x_t) && (!a.noise || al16(a.noise)) && (!a.x0_out || al16(a.x0_out)) &&
+              (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
+    } else {
+        return NPCD_ERR_ARG;
+    }
+    *vec_out = vec;
+    return NPCD_OK;
+}
+
+// the grid of ddpm_reverse_kernel: one sweep of 256 lanes per workgroup, at most 1024 workgroups per sample, the rest strided
+static int sampler_grid(const NpcdSamplerTensor& a, bool vec) {
+    const int64_t items = vec ? a.per_sample / 4 : a.per_sample;
+    return (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
+}
+
 extern "C" int npcd_sampler_step(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const int64_t* t, const float* table, int T,
                                  int B, int deterministic, void* stream) {
     if (!coords || !feats || !t || !table || T <= 0 || B <= 0) return NPCD_ERR_ARG;
@@ -1154,27 +1269,49 @@ extern "C" int npcd_sampler_step(const NpcdSamplerTensor* coords, const NpcdSamp
     int gx = 1;
     for (int z = 0; z < 2; ++z) {
         const NpcdSamplerTensor& a = z ? *feats : *coords;
-        if (!a.out || a.per_sample <= 0) return NPCD_ERR_ARG;
-        bool vec = a.per_sample % 4 == 0 && al16(a.out);
-        if (a.mode == NPCD_SAMPLER_HOLD) {
-            if (!a.known || !a.noise) return NPCD_ERR_ARG;
-            vec = vec && al16(a.known) && al16(a.noise);
-        } else if (a.mode == NPCD_SAMPLER_REVERSE) {
-            if (!a.x_t || !a.eps || (!a.noise && !deterministic)) return NPCD_ERR_ARG;
-            if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
-            vec = vec && al16(a.x_t) && (!a.noise || al16(a.noise)) && (!a.x0_out || al16(a.x0_out)) &&
-                  (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
-        } else {
-            return NPCD_ERR_ARG;
-        }
+        bool vec = false;
+        const int rc = sampler_check_mode(a, deterministic, &vec);
+        if (rc != NPCD_OK) return rc;
         args.tz[z] = a;
         args.vec[z] = vec ? 1 : 0;
-        // the grid of ddpm_reverse_kernel: one sweep of 256 lanes per workgroup, at most 1024 workgroups per sample, the rest strided
-        const int64_t items = vec ? a.per_sample / 4 : a.per_sample;
-        const int g = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
+        const int g = sampler_grid(a, vec);
         gx = g > gx ? g : gx;
     }
     hipLaunchKernelGGL(sampler_step_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
+}
+
+extern "C" int npcd_sampler_step_keep(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const uint8_t* keep_coords,
+                                      const uint8_t* keep_feats, int64_t n_points, const int64_t* t, const float* table, int T, int B,
+                                      int deterministic, void* stream) {
+    if (!coords || !feats || !t || !table || T <= 0 || B <= 0 || n_points <= 0) return NPCD_ERR_ARG;
+    if (B > 65535 || !al16(table)) return NPCD_ERR_UNSUPPORTED;
+    SamplerKeepArgs args;
+    args.n_points = n_points;
+    args.det = deterministic ? 1 : 0;
+    int gx = 1;
+    for (int z = 0; z < 2; ++z) {
+        const NpcdSamplerTensor& a = z ? *feats : *coords;
+        const uint8_t* keep = z ? keep_feats : keep_coords;
+        bool vec = false;
+        if (!keep) {
+            const int rc = sampler_check_mode(a, deterministic, &vec);
+            if (rc != NPCD_OK) return rc;
+        } else {
+            if (!a.out || !a.x_t || !a.eps || !a.noise || !a.known || a.per_sample <= 0 || a.per_sample % n_points != 0) return NPCD_ERR_ARG;
+            if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
+            vec = n_points % 4 == 0 && (reinterpret_cast<uintptr_t>(keep) & 3) == 0 && al16(a.out) && al16(a.x_t) && al16(a.noise) &&
+                  al16(a.known) && (!a.x0_out || al16(a.x0_out)) &&
+                  (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
+        }
+        args.tz[z] = a;
+        args.keep[z] = keep;
+        args.vec[z] = vec ? 1 : 0;
+        const int g = sampler_grid(a, vec);
+        gx = g > gx ? g : gx;
+    }
+    hipLaunchKernelGGL(sampler_step_keep_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }

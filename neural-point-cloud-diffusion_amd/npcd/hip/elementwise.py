@@ -411,10 +411,12 @@ SAMPLER_REVERSE, SAMPLER_HOLD = 0, 1
 
 
 def _sampler_tensor(spec, B):
-    """One tensor of sampler_step -> (the C record, out, x0 or None, the tensors the record points to)."""
-    hold = spec.get("mode", "reverse") == "hold"
-    if spec.get("mode", "reverse") not in ("reverse", "hold"):
-        raise ValueError("sampler_step: mode is 'reverse' or 'hold'")
+    """One tensor of sampler_step -> (the C record, out, x0 or None, the mask as bytes [B, N] or None, the tensors the record
+    points to)."""
+    mode = spec.get("mode", "reverse")
+    if mode not in ("reverse", "hold", "keep"):
+        raise ValueError("sampler_step: mode is 'reverse', 'hold' or 'keep'")
+    hold = mode == "hold"
     keep = [None if spec.get(k) is None else spec[k].contiguous() for k in ("x_t", "eps", "noise", "known")]
     x_t, eps, noise, known = keep
     like = known if hold else x_t
@@ -428,6 +430,16 @@ def _sampler_tensor(spec, B):
     if eps is not None and eps.shape != like.shape:
         raise RuntimeError("sampler_step: eps has the shape of x_t")
     require_gpu(*[v for v in keep if v is not None])
+    mask = None
+    if mode == "keep":
+        mask = spec.get("keep")
+        if mask is None or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 2 or mask.shape[0] != B or like.dim() < 2 \
+                or mask.shape[1] != like.shape[-1]:
+            raise RuntimeError("sampler_step: keep is a bool or uint8 [B, N] tensor, the tensors are [B, ..., N]")
+        require_gpu(mask)
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask      # a bool is one byte, 0 or 1: no copy
+        keep.append(mask)
     out = spec.get("out")
     out = arena.empty(like.shape, _f32, like.device) if out is None else out
     x0 = spec.get("x0_out")
@@ -435,31 +447,41 @@ def _sampler_tensor(spec, B):
         x0 = arena.empty(like.shape, _f32, like.device)
     clip = None if hold else spec.get("clip")
     rec = SamplerTensor()
-    rec.x_t, rec.eps, rec.noise, rec.known = (0 if v is None else v.data_ptr() for v in keep)
+    rec.x_t, rec.eps, rec.noise, rec.known = (0 if v is None else v.data_ptr() for v in keep[:4])
     rec.out, rec.x0_out = out.data_ptr(), (0 if x0 is None else x0.data_ptr())
     rec.per_sample = like.numel() // B
     rec.clip_lo, rec.clip_hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
     rec.has_clip, rec.mode = int(clip is not None), SAMPLER_HOLD if hold else SAMPLER_REVERSE
     rec.eps_dtype = dtype_code(eps) if eps is not None else 2
-    return rec, out, x0, keep
+    return rec, out, x0, mask, keep
 
 
 def sampler_step(coords, feats, t, table, deterministic):
-    """One step of the scheduled sampler for BOTH tensors in one launch (npcd_sampler_step).  `coords` / `feats` are dicts:
+    """One step of the scheduled sampler for BOTH tensors in one launch.  `coords` / `feats` are dicts:
          mode "reverse" (default): x_t fp32 [B, ...], eps fp32 or bf16, noise fp32 or None, clip (lo, hi) floats or None, want_x0
          mode "hold"             : known fp32 [B, ...], noise fp32
+         mode "keep"             : x_t, eps, noise, known as above, all given, [B, channels, N]; keep bool or uint8 [B, N] (non-zero:
+                                   the point takes the hold expression, the others the reverse step; x0 is `known` there); clip, want_x0
        and optionally out / x0_out, contiguous fp32 tensors to write into (otherwise from the arena).  t int64 [B]; table fp32 [T, 8]
        and deterministic (eta == 0: every s of the table is 0, the only case in which a reverse tensor may come without noise) are
-       SamplingSchedule.table / .deterministic.  -> ((out, x0 or None) of coords, (out, x0 or None) of feats)."""
+       SamplingSchedule.table / .deterministic.  npcd_sampler_step_keep when either tensor has a mask, npcd_sampler_step otherwise.
+       -> ((out, x0 or None) of coords, (out, x0 or None) of feats)."""
     require_gpu(t, table)
     if t.dtype != torch.int64 or table.dtype != _f32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
         raise RuntimeError("sampler_step: t is int64 [B], table a contiguous fp32 [T, 8]")
     t = t.contiguous()
     B = t.shape[0]
-    rc, oc, x0c, keep_c = _sampler_tensor(coords, B)
-    rf, of, x0f, keep_f = _sampler_tensor(feats, B)
-    check(lib().npcd_sampler_step(ctypes.byref(rc), ctypes.byref(rf), ptr(t), ptr(table), table.shape[0], B, int(bool(deterministic)),
-                                  stream_ptr()), "npcd_sampler_step")
+    rc, oc, x0c, mc, keep_c = _sampler_tensor(coords, B)
+    rf, of, x0f, mf, keep_f = _sampler_tensor(feats, B)
+    if mc is None and mf is None:
+        check(lib().npcd_sampler_step(ctypes.byref(rc), ctypes.byref(rf), ptr(t), ptr(table), table.shape[0], B, int(bool(deterministic)),
+                                      stream_ptr()), "npcd_sampler_step")
+    else:
+        if mc is not None and mf is not None and mc.shape != mf.shape:
+            raise RuntimeError("sampler_step: the two masks are [B, N] with one N")
+        n_points = (mc if mc is not None else mf).shape[1]
+        check(lib().npcd_sampler_step_keep(ctypes.byref(rc), ctypes.byref(rf), ptr(mc), ptr(mf), n_points, ptr(t), ptr(table),
+                                           table.shape[0], B, int(bool(deterministic)), stream_ptr()), "npcd_sampler_step_keep")
     del keep_c, keep_f
     return (oc, x0c), (of, x0f)
 

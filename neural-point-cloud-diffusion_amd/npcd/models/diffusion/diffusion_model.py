@@ -80,7 +80,8 @@ class DiffusionModel(nn.Module):
         return self.diffusion_process.p_losses(self.denoiser, coords, feats, t, coords_noise, feats_noise, want_pointwise=want_pointwise)
 
     @torch.no_grad()
-    def generate(self, num, batch_size=8, progress=True, dtype=None, use_graph=False, sampling_steps=None, eta=None, coords=None, feats=None):
+    def generate(self, num, batch_size=8, progress=True, dtype=None, use_graph=False, sampling_steps=None, eta=None, coords=None, feats=None,
+                 keep_coords=None, keep_feats=None, keep=None, resample=None):
         """Reference :108-133.  Two options the reference does not have: `dtype` (e.g. torch.bfloat16) runs the denoiser under
         autocast on the MFMA attention kernels -- 6x faster per reverse step than the reference's fp32 sampling, eps within the
         training-time bf16 tolerance; `use_graph` replays each reverse step from a captured HIP graph.
@@ -89,13 +90,34 @@ class DiffusionModel(nn.Module):
         leaves today's loop and bits): `sampling_steps` levels of a strided schedule instead of all of them, `eta` in [0, 1] (0: the
         deterministic DDIM step, one launch and no noise; default 1), and ONE of `coords` [num, 3, N] / `feats` [num, F, N] in data
         space (what generate returns, stacked): that tensor is held -- at every level the denoiser sees it forward-noised -- and the
-        other one is sampled; it comes back as the caller's values, unclipped, bit for bit."""
+        other one is sampled; it comes back as the caller's values, unclipped, bit for bit.
+
+        Per-point conditioning (p_sample_loop(keep=, resample=); completion, local edits): `keep_coords` / `keep_feats`, bool [num, N],
+        mark the points of `coords` / `feats` that are kept; `keep` sets both masks.  A mask needs its tensor.  With at least one mask
+        both tensors may be given, and a tensor given without a mask is kept at every point.  The result is where(mask, given,
+        sampled): the caller's values at kept points, unclipped, bit for bit (the given values at free points are not read).
+        `resample` = r >= 1 performs every transition r times with a re-noise in between, which is what makes the free points follow
+        the kept ones (docs/experiments.md); it also works without masks."""
         assert not self.training, "Model must be in eval mode for generation"
-        if coords is not None and feats is not None:
+        if keep is not None:
+            if keep_coords is not None or keep_feats is not None:
+                raise ValueError("generate(keep=) sets both masks: give it alone, or keep_coords= / keep_feats=")
+            keep_coords = keep_feats = keep
+        masked = keep_coords is not None or keep_feats is not None
+        if coords is not None and feats is not None and not masked:
             raise ValueError("generate(coords=, feats=): at most one of the two tensors can be held")
         for name, given, dim in (("coords", coords, self.coords_dim), ("feats", feats, self.feats_dim)):
             if given is not None and tuple(given.shape) != (num, dim, self.num_points):
                 raise ValueError(f"generate({name}=...): expected shape {(num, dim, self.num_points)}, got {tuple(given.shape)}")
+        for name, given, mask in (("coords", coords, keep_coords), ("feats", feats, keep_feats)):
+            if mask is None:
+                continue
+            if given is None:
+                raise ValueError(f"generate(keep_{name}=...) needs {name}=: the values of the kept points")
+            if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (num, self.num_points):
+                raise ValueError(f"generate(keep_{name}=...): expected a bool tensor of shape {(num, self.num_points)}")
+        if resample is not None and (int(resample) != resample or resample < 1):
+            raise ValueError(f"generate(resample=...): an integer >= 1 (got {resample!r})")
         device = next(self.parameters()).device
         sizes = [batch_size] * (num // batch_size) + ([num % batch_size] if num % batch_size else [])
         # dtype = "fp32_class": the reference's fp32 sampling with the backbone's Linear layers as split-operand bf16 GEMMs (two bf16 halves
@@ -109,37 +131,50 @@ class DiffusionModel(nn.Module):
         if backbone is not None:
             backbone.fp32_class = fp32_class
         try:
-            return self._generate(sizes, device, ctx, progress, use_graph, sampling_steps, eta, coords, feats)
+            return self._generate(sizes, device, ctx, progress, use_graph, sampling_steps, eta, coords, feats, keep_coords, keep_feats, resample)
         finally:
             if backbone is not None:
                 backbone.fp32_class = prev_mode
 
-    def _generate(self, sizes, device, ctx, progress, use_graph, sampling_steps=None, eta=None, coords=None, feats=None):
+    def _generate(self, sizes, device, ctx, progress, use_graph, sampling_steps=None, eta=None, coords=None, feats=None, keep_coords=None,
+                  keep_feats=None, resample=None):
         coords_out, feats_out = [], []
-        given = coords if coords is not None else feats
-        norm = self.coords_normalization if coords is not None else self.feats_normalization
+        masked = keep_coords is not None or keep_feats is not None
+        sides = (("coords", coords, keep_coords, self.coords_normalization), ("feats", feats, keep_feats, self.feats_normalization))
+        scheduled = sampling_steps is not None or eta is not None or coords is not None or feats is not None or resample is not None
         done = 0
         for bs in sizes:
             c = torch.randn(bs, self.coords_dim, self.num_points, device=device)
             f = torch.randn(bs, self.feats_dim, self.num_points, device=device)
-            new = {}
-            if sampling_steps is not None or eta is not None or given is not None:
-                new = dict(steps=sampling_steps, eta=1.0 if eta is None else eta)
-            if given is not None:
-                part = given[done:done + bs].to(device=device, dtype=torch.float32)
+            new = dict(steps=sampling_steps, eta=1.0 if eta is None else eta) if scheduled else {}
+            if resample is not None:
+                new["resample"] = resample
+            given = {}
+            for name, full, mask, norm in sides:
+                if full is None:
+                    continue
+                part = full[done:done + bs].to(device=device, dtype=torch.float32)
                 # data -> model space, written out: the modules are in eval mode, where their forward is the inverse map
                 known = (part - norm.shift[None, :, None]) / norm.scale[None, :, None]
-                new["hold"] = ("coords" if coords is not None else "feats", known)
+                m = None
+                if not masked:
+                    new["hold"] = (name, known)
+                else:                                  # a tensor given without a mask beside a masked one: every point is kept
+                    m = (torch.ones(bs, self.num_points, dtype=torch.bool, device=device) if mask is None
+                         else mask[done:done + bs].to(device))
+                    new.setdefault("keep", {})[name] = (known, m)
+                given[name] = (full[done:done + bs], m)
             with ctx:
                 c, f = self.diffusion_process.p_sample_loop(
                     self.denoiser, c, f,
                     coords_clip_range=(self.coords_normalization.min, self.coords_normalization.max),
                     feats_clip_range=(self.feats_normalization.min, self.feats_normalization.max), progress=progress,
                     use_graph=use_graph, **new)
-            c, f = self.coords_normalization(c), self.feats_normalization(f)
-            if given is not None:                      # the caller's own values: the round trip through model space is not exact
-                c, f = (given[done:done + bs].to(c), f) if coords is not None else (c, given[done:done + bs].to(f))
-            coords_out += list(c.unbind())
-            feats_out += list(f.unbind())
+            out = {"coords": self.coords_normalization(c), "feats": self.feats_normalization(f)}
+            for name, (part, m) in given.items():      # the caller's own values: the round trip through model space is not exact
+                part = part.to(out[name])
+                out[name] = part if m is None else torch.where(m[:, None, :], part, out[name])
+            coords_out += list(out["coords"].unbind())
+            feats_out += list(out["feats"].unbind())
             done += bs
         return coords_out, feats_out

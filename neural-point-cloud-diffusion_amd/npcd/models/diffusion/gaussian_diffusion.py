@@ -33,7 +33,13 @@ class SamplingSchedule:
         held   = h1 known + h2 z     :   h1 = sqrt(p),  h2 = sqrt(1 - p)       (the forward process at the level the step arrives at)
     eta = 1 with K = T is the DDPM posterior of the reference.  `coef64[name]` are the float64 arrays [K]; `table` is the device
     form, fp32 [T, 8], row tau_i = (r, m, c1, c2, s, h1, h2, 0) with each coefficient rounded once and r, m (x0 = r x_t - m eps)
-    taken from the module's fp32 tables, so that x0 has the bits of the DDPM kernel's; rows of levels off the schedule are NaN."""
+    taken from the module's fp32 tables, so that x0 has the bits of the DDPM kernel's; rows of levels off the schedule are NaN.
+
+    Resampling (p_sample_loop(resample=)) goes back from tau_{i-1} to tau_i with the forward process between the two levels,
+        x = g1 x + g2 z:   g1 = sqrt(a / p),  g2 = sqrt(1 - a / p)
+    `renoise64` holds the float64 g1, g2 [K]; `renoise_table` is a second fp32 [T, 8] table with them, rounded once, in the h1 / h2
+    columns of row tau_i (the other coefficient columns and the rows off the schedule are NaN): a hold-mode launch of the step kernel
+    on it, with `known` = the current state, is the re-noise."""
 
     def __init__(self, process, T, K, eta, device):
         self.T, self.steps, self.eta, self.deterministic = T, K, eta, eta == 0.0
@@ -54,6 +60,12 @@ class SamplingSchedule:
             table[idx, j] = torch.from_numpy(self.coef64[name]).float()
         table[idx, 7] = 0.0
         self.table = table.to(device).contiguous()
+        self.renoise64 = {"g1": np.sqrt(a / p), "g2": np.sqrt(1.0 - a / p)}
+        renoise = torch.full((T, 8), float("nan"), dtype=torch.float32)
+        renoise[idx, 5] = torch.from_numpy(self.renoise64["g1"]).float()
+        renoise[idx, 6] = torch.from_numpy(self.renoise64["g2"]).float()
+        renoise[idx, 7] = 0.0
+        self.renoise_table = renoise.to(device).contiguous()
 
 
 class GaussianDiffusion(nn.Module):
@@ -205,22 +217,58 @@ class GaussianDiffusion(nn.Module):
             raise ValueError("hold is None, ('coords', known) or ('feats', known)")
         return which, known
 
-    def _scheduled_step(self, denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused):
-        """One step of the scheduled loop.  RNG order: coords noise, then feats noise; a reverse-mode tensor draws only if eta > 0,
-        the held tensor at every step.  fused: ONE launch for both tensors (npcd_sampler_step), clip_* are (lo, hi) floats or None;
-        otherwise the same step in torch, clip_* are the ranges as given to p_sample_loop."""
-        eps_c, eps_f = denoise_fn(c, f, t)
+    @staticmethod
+    def _keep_spec(keep, hold, c, f):
+        """keep= of p_sample_loop -> {"coords" | "feats": (known in the state's dtype, mask bool [B, N])} on the state's device"""
+        if keep is None:
+            return {}
+        if hold is not None:
+            raise ValueError("hold and keep cannot be given together (an all-True mask keeps a whole tensor)")
+        if not isinstance(keep, dict) or any(name not in ("coords", "feats") for name in keep):
+            raise ValueError("keep is None or {'coords': (known, mask), 'feats': (known, mask)} with either key optional")
+        spec = {}
+        for name, x in (("coords", c), ("feats", f)):
+            if keep.get(name) is None:
+                continue
+            known, mask = keep[name]
+            if not torch.is_tensor(known) or not torch.is_tensor(mask) or mask.dtype != torch.bool:
+                raise ValueError(f"keep[{name!r}] is (known tensor, bool mask)")
+            if known.shape != x.shape or x.dim() != 3 or tuple(mask.shape) != (x.shape[0], x.shape[2]):
+                raise ValueError(f"keep[{name!r}]: known has the shape of the state {tuple(x.shape)} = [B, channels, N], mask is [B, N] "
+                                 f"(got {tuple(known.shape)} and {tuple(mask.shape)})")
+            spec[name] = (known.to(device=x.device, dtype=x.dtype).contiguous(), mask.to(device=x.device).contiguous())
+        return spec
+
+    @staticmethod
+    def _scheduled_draws(sched, which, keep):
+        """(coords draws, feats draws) in a performance of a step: a reverse-mode tensor only if eta > 0, a held tensor and a tensor
+        with a mask always"""
         draw = not sched.deterministic
-        zc = torch.randn_like(c) if (draw or which == "coords") else None
-        zf = torch.randn_like(f) if (draw or which == "feats") else None
+        return draw or which == "coords" or "coords" in keep, draw or which == "feats" or "feats" in keep
+
+    def _scheduled_noise(self, c, f, sched, which, keep):
+        """The draws of one performance of a step, in the fixed RNG order: coords noise, then feats noise."""
+        draw_c, draw_f = self._scheduled_draws(sched, which, keep)
+        zc = torch.randn_like(c) if draw_c else None
+        zf = torch.randn_like(f) if draw_f else None
+        return zc, zf
+
+    def _scheduled_update(self, c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep):
+        """The update of one step on given eps and noise.  fused: ONE launch for both tensors (npcd_sampler_step, or
+        npcd_sampler_step_keep when a tensor has a mask), clip_* are (lo, hi) floats or None; otherwise the same step in torch,
+        clip_* are the ranges as given to p_sample_loop.  A tensor with a mask: where(mask, the hold expression on its known values,
+        the reverse step) -- selected, so that nothing of the branch not taken reaches the result."""
         if fused:
             from ...hip import elementwise as ew
             spec = []
             for name, x, eps, z, clip in (("coords", c, eps_c, zc, clip_c), ("feats", f, eps_f, zf, clip_f)):
                 if which == name:
                     spec.append(dict(mode="hold", known=known, noise=z))
+                    continue
+                eps = eps if eps.dtype in (torch.float32, torch.bfloat16) else eps.float()
+                if name in keep:
+                    spec.append(dict(mode="keep", x_t=x, eps=eps, noise=z, known=keep[name][0], keep=keep[name][1], clip=clip))
                 else:
-                    eps = eps if eps.dtype in (torch.float32, torch.bfloat16) else eps.float()
                     spec.append(dict(mode="reverse", x_t=x, eps=eps, noise=z, clip=clip))
             (c_next, _), (f_next, _) = ew.sampler_step(spec[0], spec[1], t, sched.table, sched.deterministic)
             return c_next, f_next
@@ -235,15 +283,47 @@ class GaussianDiffusion(nn.Module):
             if clip is not None:
                 x0 = torch.clamp(x0, clip[0], clip[1])
             nxt = k[2] * x0 + k[3] * x
-            out.append(nxt if z is None else nxt + k[4] * z)
+            if name in keep:
+                kn, mask = keep[name]
+                out.append(torch.where(mask[:, None, :], k[5] * kn + k[6] * z, nxt if sched.deterministic else nxt + k[4] * z))
+            else:
+                out.append(nxt if z is None else nxt + k[4] * z)
+        return out[0], out[1]
+
+    def _scheduled_step(self, denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused, keep=None):
+        """One step of the scheduled loop: the denoiser, the draws (_scheduled_noise fixes the RNG order), the update."""
+        keep = keep or {}
+        eps_c, eps_f = denoise_fn(c, f, t)
+        zc, zf = self._scheduled_noise(c, f, sched, which, keep)
+        return self._scheduled_update(c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep)
+
+    @staticmethod
+    def _renoise(c, f, zc, zf, t, sched, fused):
+        """Back from the level a step arrived at to the level t it left: x = g1 x + g2 z on both tensors in whole.  fused: ONE
+        hold-mode launch of the step kernel on the schedule's second table, the current state as `known`."""
+        if fused:
+            from ...hip import elementwise as ew
+            (c_next, _), (f_next, _) = ew.sampler_step(dict(mode="hold", known=c, noise=zc), dict(mode="hold", known=f, noise=zf), t,
+                                                       sched.renoise_table, False)
+            return c_next, f_next
+        row = sched.renoise_table.to(t.device)[t]
+        out = []
+        for x, z in ((c, zc), (f, zf)):
+            g1, g2 = (row[:, j].reshape((-1,) + (1,) * (x.dim() - 1)) for j in (5, 6))
+            out.append(g1 * x + g2 * z)
         return out[0], out[1]
 
     def _p_sample_loop_scheduled(self, denoise_fn, coords_start, feats_start, coords_clip_range, feats_clip_range, progress, use_graph,
-                                 steps, eta, hold):
-        """The loop behind p_sample_loop(steps=, eta=, hold=): the schedule's levels in descending order, one _scheduled_step each."""
+                                 steps, eta, hold, keep=None, resample=None):
+        """The loop behind p_sample_loop(steps=, eta=, hold=, keep=, resample=): the schedule's levels in descending order, each
+        transition performed `resample` times (_scheduled_step) with a re-noise (_renoise) between two performances."""
         c, f = coords_start, feats_start
+        r = 1 if resample is None else int(resample)
+        if r != (1 if resample is None else resample) or r < 1:
+            raise ValueError(f"resample must be an integer >= 1 (got {resample!r})")
         sched = self.sampling_schedule(steps, 1.0 if eta is None else eta, device=c.device)
         which, known = self._hold_spec(hold)
+        keep = self._keep_spec(keep, hold, c, f)
         levels = [int(i) for i in sched.timesteps[::-1]]
         if progress:
             from tqdm.auto import tqdm
@@ -253,6 +333,10 @@ class GaussianDiffusion(nn.Module):
             known = known.to(device=c.device, dtype=torch.float32).contiguous()
             start = self.q_sample(known, t, coords_start if which == "coords" else feats_start)
             c, f = (start, f) if which == "coords" else (c, start)
+        if "coords" in keep:                  # likewise at the kept points; the free points start as the start tensor
+            c = torch.where(keep["coords"][1][:, None, :], self.q_sample(keep["coords"][0], t, c), c)
+        if "feats" in keep:
+            f = torch.where(keep["feats"][1][:, None, :], self.q_sample(keep["feats"][0], t, f), f)
         has_c, clip_c = self._scalar_clip(coords_clip_range)
         has_f, clip_f = self._scalar_clip(feats_clip_range)
         fused = c.is_cuda and c.dtype == torch.float32 and f.dtype == torch.float32 and not (has_c and clip_c is None) and not (has_f and clip_f is None)
@@ -261,8 +345,13 @@ class GaussianDiffusion(nn.Module):
         if not (fused and use_graph):
             for i in levels:
                 t.fill_(i)
-                c, f = self._scheduled_step(denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused)
+                for j in range(r):
+                    c, f = self._scheduled_step(denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused, keep)
+                    if j + 1 < r:
+                        c, f = self._renoise(c, f, torch.randn_like(c), torch.randn_like(f), t, sched, fused)
             return c, f
+        if keep or r > 1:
+            return self._scheduled_graph_loop(denoise_fn, c, f, t, levels, r, sched, which, known, clip_c, clip_f, keep)
         # graph replay, as in p_sample_loop: static state buffers, warm-up on a side stream, one captured step, t refilled between replays
         sc, sf = c.clone(), f.clone()
         side = torch.cuda.Stream()
@@ -281,8 +370,55 @@ class GaussianDiffusion(nn.Module):
             sf.copy_(of)
         return sc.clone(), sf.clone()
 
+    def _scheduled_graph_loop(self, denoise_fn, c, f, t, levels, r, sched, which, known, clip_c, clip_f, keep):
+        """Graph replay of the loop with masks and / or resampling: one captured step (denoiser + update) and, for r > 1, one captured
+        re-noise, on static state and noise buffers.  The noise is drawn between the replays, by the calls and in the order of the
+        eager loop, so that eager and replayed sampling consume the generator alike and give the same bits."""
+        sc, sf = c.clone(), f.clone()
+        draw_c, draw_f = self._scheduled_draws(sched, which, keep)
+        zc = torch.zeros_like(sc) if draw_c else None                       # the noise of a step, refilled before every replay
+        zf = torch.zeros_like(sf) if draw_f else None
+        nc, nf = torch.zeros_like(sc), torch.zeros_like(sf)                 # the noise of a re-noise: always both
+
+        def step():
+            eps_c, eps_f = denoise_fn(sc, sf, t)
+            return self._scheduled_update(sc, sf, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, True, keep)
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                step()
+                if r > 1:
+                    self._renoise(sc, sf, nc, nf, t, sched, True)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            oc, of = step()
+        back = None
+        if r > 1:
+            back = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(back):
+                bc, bf = self._renoise(sc, sf, nc, nf, t, sched, True)
+        for i in levels:
+            t.fill_(i)
+            for j in range(r):
+                for z in (zc, zf):
+                    if z is not None:
+                        z.normal_()
+                graph.replay()
+                sc.copy_(oc)
+                sf.copy_(of)
+                if j + 1 < r:
+                    nc.normal_()
+                    nf.normal_()
+                    back.replay()
+                    sc.copy_(bc)
+                    sf.copy_(bf)
+        return sc.clone(), sf.clone()
+
     def p_sample_loop(self, denoise_fn, coords_start, feats_start, coords_clip_range=None, feats_clip_range=None,
-                      progress=False, use_graph=False, steps=None, eta=None, hold=None):
+                      progress=False, use_graph=False, steps=None, eta=None, hold=None, keep=None, resample=None):
         """1000 reverse steps (reference :148-177 without the trajectory lists).  On the GPU with scalar clip ranges every step
         runs the fused posterior update; `use_graph` additionally captures one whole step (denoiser forward + update, fixed
         batch) in a HIP graph and replays it -- the per-step launch work (~600 launches at 24 layers) leaves the host.
@@ -290,10 +426,19 @@ class GaussianDiffusion(nn.Module):
         Any of `steps` (levels of a strided schedule, 1..T), `eta` (0 = deterministic DDIM .. 1 = DDPM variance; default 1) and
         `hold` (("coords" | "feats", known in model space): that tensor is, at every level, the known one forward-noised, and ends
         as `known`) selects the scheduled loop instead (sampling_schedule / _scheduled_step, whose docstring fixes the RNG order);
-        the held tensor's start tensor serves as its start noise.  Without them: today's loop, today's bits."""
-        if steps is not None or eta is not None or hold is not None:
+        the held tensor's start tensor serves as its start noise.  Without them: today's loop, today's bits.
+
+        `keep` and `resample` select the scheduled loop too.  keep = {"coords": (known, mask), "feats": (known, mask)}, either key
+        optional, known in model space with the state's shape [B, channels, N], mask bool [B, N]: the per-point form of `hold` (not
+        both).  A tensor with a mask starts as where(mask, q_sample(known, first level, start), start); at every step its kept points
+        are the known values forward-noised to the level the step arrives at (exactly `known` after the last), its free points the
+        reverse step.  resample = r >= 1 (None: 1) performs every transition r times, with both tensors re-noised in whole back to the
+        level the transition left between two performances (RePaint, Lugmayr et al. 2022: with one pass the free points largely ignore
+        the kept ones, docs/experiments.md).  RNG order: per performance coords noise, then feats noise (a tensor with a mask always
+        draws); per re-noise coords noise, then feats noise, always both."""
+        if steps is not None or eta is not None or hold is not None or keep is not None or resample is not None:
             return self._p_sample_loop_scheduled(denoise_fn, coords_start, feats_start, coords_clip_range, feats_clip_range, progress,
-                                                 use_graph, steps, eta, hold)
+                                                 use_graph, steps, eta, hold, keep, resample)
         steps = range(self.num_timesteps - 1, -1, -1)
         if progress:
             from tqdm.auto import tqdm
