@@ -511,6 +511,28 @@ int npcd_sampler_step_keep(const NpcdSamplerTensor* coords, const NpcdSamplerTen
                            const uint8_t* keep_feats, int64_t n_points, const int64_t* t, const float* table, int T, int B,
                            int deterministic, void* stream);
 
+/* The deterministic step in second order: DPM-Solver++(2M) in data prediction (Lu et al. 2022) on the levels of the schedule.
+ * `table` is SamplingSchedule.multistep_table: the eta = 0 table of npcd_sampler_step with the multistep weight w in column 7,
+ * (r, m, c1, c2, 0, h1, h2, w).  Per element of a reverse-mode tensor, or of a free point of a masked one:
+ *   x0 = r[t] x_t - m[t] eps (clamped if has_clip: the bits of npcd_sampler_step's x0),
+ *   D  = w[t] == 0 ? x0 : fma(w[t], x0 - hist, x0),   out = fma(c1[t], D, c2[t] x_t),   hist = x0.
+ * hist_coords / hist_feats are fp32 [B, per_sample], the previous step's x0 of that tensor; every element is read (only where
+ * w[t] != 0) and then overwritten in place by the lane that owns it.  A sample whose row has w = 0 (the first step of a run, which
+ * has no history, and the step to the data) reads nothing from `hist` -- it may be uninitialised or NaN -- and its out has the bits
+ * of NPCD_SAMPLER_REVERSE with `deterministic` on the same operands.  The clip applies to x0 before the extrapolation; the stored
+ * history and x0_out are the clipped x0.  There is no noise term: the noise of a reverse-mode tensor is not read.
+ *   mode NPCD_SAMPLER_HOLD (no mask): exactly as in npcd_sampler_step; its hist pointer is not used and may be NULL.
+ *   mask given (keep_coords / keep_feats, bytes [B, n_points]): as in npcd_sampler_step_keep -- x_t, eps, noise and known must all be
+ *        given, `mode` is ignored, n_points must divide per_sample; kept points take h1[t] known + h2[t] noise, selected and not
+ *        blended; hist and x0_out receive `known` there; nothing at a free point reads `known`.  n_points is read only with a mask.
+ * Both tensors go in ONE launch on the grid rule of npcd_sampler_step; 16 bytes per lane under the alignment conditions of
+ * npcd_sampler_step / npcd_sampler_step_keep with hist 16-byte aligned too, otherwise one element per lane; no atomics: the same bits
+ * on every run from the same history.  NPCD_ERR_ARG / NPCD_ERR_UNSUPPORTED as for those two, and NPCD_ERR_ARG for a missing hist of a
+ * tensor that is not in hold mode; all before any launch. */
+int npcd_sampler_step_multistep(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, float* hist_coords, float* hist_feats,
+                                const uint8_t* keep_coords, const uint8_t* keep_feats, int64_t n_points, const int64_t* t,
+                                const float* table, int T, int B, void* stream);
+
 /* Forward process and training loss of the DDPM, fused (reference gaussian_diffusion.py:68-76 q_sample, :199-230 p_losses):
  *   npcd_q_sample    : x_t = tab_sqrt_acp[t_b] * x_0 + tab_sqrt_1macp[t_b] * noise, fp32 [B, per_sample], t int64 [B]; the products
  *                      and the sum are rounded separately like the reference's eager ops (bit-identical to them)

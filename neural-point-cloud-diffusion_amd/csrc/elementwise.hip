@@ -12,7 +12,8 @@
 //   GradScaler + clip_grad_norm_ bookkeeping on the device        -> grad_stats, scaler_finalize, adamw_ema_gated
 // and of the sampler (gaussian_diffusion.py:100-146): the DDPM reverse step per tensor -> ddpm_reverse; a step of the scheduled sampler
 // (strided DDIM levels, eta, one tensor held), both tensors in one launch          -> sampler_step; the same step with a per-point
-// mask that keeps some points of a tensor (completion, local edits)               -> sampler_step_keep
+// mask that keeps some points of a tensor (completion, local edits)               -> sampler_step_keep; the deterministic step in
+// second order, with the previous step's data prediction as history (DPM-Solver++ 2M) -> sampler_step_multistep
 // All are pure streaming kernels: 16-byte accesses per lane, fp32 math, no LDS except the cross-wave
 // reduction of column partials.  Roofline: HBM.
 #include <math.h>
@@ -898,6 +899,111 @@ __global__ __launch_bounds__(256) void sampler_step_keep_kernel(SamplerKeepArgs 
     }
 }
 
+// Second-order multistep step (npcd_sampler_step_multistep; DPM-Solver++ 2M in data prediction, Lu et al. 2022, on a deterministic
+// schedule): the reverse step with the data prediction extrapolated from the previous step's, which `hist` carries from launch to launch
+//   x0 = sampler_x0 (clipped),  D = (w == 0) ? x0 : fma(w, x0 - hist, x0),  out = fma(c1, D, c2 x),  hist = x0
+// w is column 7 of the sample's table row (0 in the tables of npcd_sampler_step).  A row with w = 0 -- the first step, which has no
+// history, and the step to the data -- loads nothing from `hist`, and its out is sampler_reverse's without noise: the same bits.  The
+// branch is uniform over the workgroup (one sample, one w).  Every lane reads and then overwrites its own elements of `hist`, which
+// no other lane touches.  roundings past x0: the subtraction, the fma of D, c2 x, the fma of out.
+// KEEP: the select of sampler_keep -- kept points take the hold expression on `known`, and hist and x0_out receive `known` there.
+__device__ __forceinline__ float sampler_multistep_d(float w, float x0, float h) { return __builtin_fmaf(w, x0 - h, x0); }
+
+template <class EPS, bool VEC, bool KEEP>
+__device__ __forceinline__ void sampler_multistep(const NpcdSamplerTensor& a, float* __restrict__ hist, const uint8_t* __restrict__ keep,
+                                                  int64_t n_points, const SamplerCoef& k, float w, int64_t base) {
+    const float* __restrict__ x_t = a.x_t + base;
+    const EPS* __restrict__ eps = static_cast<const EPS*>(a.eps) + base;
+    const float* __restrict__ noise = KEEP ? a.noise + base : nullptr;
+    const float* __restrict__ known = KEEP ? a.known + base : nullptr;
+    float* __restrict__ out = a.out + base;
+    float* __restrict__ x0_out = a.x0_out ? a.x0_out + base : nullptr;
+    hist += base;
+    const bool first_order = w == 0.f;
+    if constexpr (VEC) {
+        const int64_t n4 = a.per_sample / 4, row4 = KEEP ? n_points / 4 : 1;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+            const f32x4 x = reinterpret_cast<const f32x4*>(x_t)[i];
+            const f32x4 e = to_f32(reinterpret_cast<const typename V<EPS>::x4*>(eps)[i]);
+            f32x4 h = f32x4{0.f, 0.f, 0.f, 0.f}, z = h, kn = h;
+            if (!first_order) h = reinterpret_cast<const f32x4*>(hist)[i];
+            uint32_t m = 0;
+            if constexpr (KEEP) {
+                m = reinterpret_cast<const uint32_t*>(keep)[sampler_col(i, row4)];
+                z = reinterpret_cast<const f32x4*>(noise)[i];
+                kn = reinterpret_cast<const f32x4*>(known)[i];
+            }
+            f32x4 x0, o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float f0 = sampler_x0(k, x[q], e[q], a.has_clip, a.clip_lo, a.clip_hi);
+                const float d = first_order ? f0 : sampler_multistep_d(w, f0, h[q]);
+                const float fo = __builtin_fmaf(k.c1, d, k.c2 * x[q]);
+                const bool kept = KEEP && ((m >> (8 * q)) & 0xffu) != 0;
+                x0[q] = kept ? kn[q] : f0;
+                o[q] = kept ? __builtin_fmaf(k.h1, kn[q], k.h2 * z[q]) : fo;
+            }
+            if (x0_out) reinterpret_cast<f32x4*>(x0_out)[i] = x0;
+            reinterpret_cast<f32x4*>(hist)[i] = x0;
+            reinterpret_cast<f32x4*>(out)[i] = o;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256) {
+            const float x = x_t[i];
+            const float f0 = sampler_x0(k, x, (float)eps[i], a.has_clip, a.clip_lo, a.clip_hi);
+            const float d = first_order ? f0 : sampler_multistep_d(w, f0, hist[i]);
+            float o = __builtin_fmaf(k.c1, d, k.c2 * x), x0 = f0;
+            if constexpr (KEEP) {
+                if (keep[sampler_col(i, n_points)] != 0) {
+                    x0 = known[i];
+                    o = __builtin_fmaf(k.h1, x0, k.h2 * noise[i]);
+                }
+            }
+            if (x0_out) x0_out[i] = x0;
+            hist[i] = x0;
+            out[i] = o;
+        }
+    }
+}
+
+struct SamplerMultistepArgs {
+    NpcdSamplerTensor tz[2];
+    float* hist[2];                  // [B, per_sample]; null only for a hold-mode tensor
+    const uint8_t* keep[2];          // [B, n_points] or null: that tensor goes by its mode
+    int64_t n_points;
+    int vec[2];
+};
+
+template <class EPS>
+__device__ __forceinline__ void sampler_multistep_by_path(const NpcdSamplerTensor& a, float* hist, const uint8_t* keep, int64_t n_points, int vec,
+                                                          const SamplerCoef& k, float w, int64_t base) {
+    if (keep) {
+        if (vec) sampler_multistep<EPS, true, true>(a, hist, keep, n_points, k, w, base);
+        else sampler_multistep<EPS, false, true>(a, hist, keep, n_points, k, w, base);
+    } else {
+        if (vec) sampler_multistep<EPS, true, false>(a, hist, keep, n_points, k, w, base);
+        else sampler_multistep<EPS, false, false>(a, hist, keep, n_points, k, w, base);
+    }
+}
+
+__global__ __launch_bounds__(256) void sampler_step_multistep_kernel(SamplerMultistepArgs args, const int64_t* __restrict__ t,
+                                                                     const float* __restrict__ table, int T) {
+    const int z = blockIdx.z, b = blockIdx.y;
+    const NpcdSamplerTensor& a = args.tz[z];
+    const SamplerCoef k = sampler_coef(t, table, T, b);
+    const int64_t base = (int64_t)b * a.per_sample;
+    if (!args.keep[z] && a.mode == NPCD_SAMPLER_HOLD) {
+        if (args.vec[z]) sampler_hold<true>(a, k, base);
+        else sampler_hold<false>(a, k, base);
+        return;
+    }
+    const int64_t ts = t[b];
+    const float w = (ts >= 0 && ts < T) ? table[8 * ts + 7] : __builtin_nanf("");
+    const uint8_t* keep = args.keep[z] ? args.keep[z] + (int64_t)b * args.n_points : nullptr;
+    if (a.eps_dtype == NPCD_F32) sampler_multistep_by_path<float>(a, args.hist[z], keep, args.n_points, args.vec[z], k, w, base);
+    else sampler_multistep_by_path<__bf16>(a, args.hist[z], keep, args.n_points, args.vec[z], k, w, base);
+}
+
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace npcd
@@ -1312,6 +1418,46 @@ extern "C" int npcd_sampler_step_keep(const NpcdSamplerTensor* coords, const Npc
         gx = g > gx ? g : gx;
     }
     hipLaunchKernelGGL(sampler_step_keep_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
+    NPCD_HIP_CHECK(hipGetLastError());
+    return NPCD_OK;
+}
+
+extern "C" int npcd_sampler_step_multistep(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, float* hist_coords,
+                                           float* hist_feats, const uint8_t* keep_coords, const uint8_t* keep_feats, int64_t n_points,
+                                           const int64_t* t, const float* table, int T, int B, void* stream) {
+    if (!coords || !feats || !t || !table || T <= 0 || B <= 0) return NPCD_ERR_ARG;
+    if ((keep_coords || keep_feats) && n_points <= 0) return NPCD_ERR_ARG;
+    if (B > 65535 || !al16(table)) return NPCD_ERR_UNSUPPORTED;
+    SamplerMultistepArgs args;
+    args.n_points = n_points;
+    int gx = 1;
+    for (int z = 0; z < 2; ++z) {
+        const NpcdSamplerTensor& a = z ? *feats : *coords;
+        const uint8_t* keep = z ? keep_feats : keep_coords;
+        float* hist = z ? hist_feats : hist_coords;
+        bool vec = false;
+        if (!keep) {
+            const int rc = sampler_check_mode(a, 1, &vec);          // the schedule is deterministic: a reverse tensor needs no noise
+            if (rc != NPCD_OK) return rc;
+        } else {
+            if (!a.out || !a.x_t || !a.eps || !a.noise || !a.known || a.per_sample <= 0 || a.per_sample % n_points != 0) return NPCD_ERR_ARG;
+            if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
+            vec = n_points % 4 == 0 && (reinterpret_cast<uintptr_t>(keep) & 3) == 0 && al16(a.out) && al16(a.x_t) && al16(a.noise) &&
+                  al16(a.known) && (!a.x0_out || al16(a.x0_out)) &&
+                  (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
+        }
+        if (keep || a.mode != NPCD_SAMPLER_HOLD) {
+            if (!hist) return NPCD_ERR_ARG;
+            vec = vec && al16(hist);
+        }
+        args.tz[z] = a;
+        args.hist[z] = hist;
+        args.keep[z] = keep;
+        args.vec[z] = vec ? 1 : 0;
+        const int g = sampler_grid(a, vec);
+        gx = g > gx ? g : gx;
+    }
+    hipLaunchKernelGGL(sampler_step_multistep_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }

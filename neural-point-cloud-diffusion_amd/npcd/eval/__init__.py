@@ -125,14 +125,15 @@ def load_test_poses(name: str = "srncars"):
 @torch.no_grad()
 def sample_and_render(model, poses: torch.Tensor, intrinsics: torch.Tensor, num_samples: int = 4, generate_batch_size: int = 4,
                       render_batch_size: int = 8, resolution: int = 128, dtype=None, use_graph: bool = False, feed=None,
-                      max_shading_points=None, render_mlp_dtype=None, sampling_steps=None, eta=None) -> Dict:
+                      max_shading_points=None, render_mlp_dtype=None, sampling_steps=None, eta=None, spacing=None, solver=None) -> Dict:
     """The measurement loop of the reference's DiffusionEvaluation._evaluate (:146-183): `generate_batch_size` clouds at a time from
     model.diffusion.generate (:152), every cloud rendered from all poses, `render_batch_size` poses per PointNeRF.render call
     (:163-169), images clipped to [0, 1] and rounded to 8 bits (:172-173).  `feed(images [n_poses, 3, H, W] in [0, 1])`, when given,
     receives every cloud's images (the reference hands them to FID/KID as images * 2 - 1, :179; the Inception network is outside this
     package, SURVEY section 8).  `dtype`: run the sampler's denoiser under autocast, or "fp32_class" (DiffusionModel.generate);
     `render_mlp_dtype=torch.float32`: shade in the reference's numerics class (PointNeRF.render); `sampling_steps` / `eta`: the
-    scheduled sampler of DiffusionModel.generate (few-step DDIM), passed through.  Returns timings:
+    scheduled sampler of DiffusionModel.generate (few-step DDIM), passed through, as are `spacing` / `solver` (levels uniform in the log
+    signal-to-noise ratio, the second-order multistep step).  Returns timings:
     seconds in generate / render, clouds per second, rendered views and rays per second (device-synchronised walls)."""
     model.eval()
     dev = next(model.pointnerf.parameters()).device
@@ -141,12 +142,13 @@ def sample_and_render(model, poses: torch.Tensor, intrinsics: torch.Tensor, num_
     t_gen = t_ren = 0.0
     n_views = 0
     shapes = None
+    new = {k: v for k, v in (("spacing", spacing), ("solver", solver)) if v is not None}
     for s0 in range(0, num_samples, generate_batch_size):
         n = min(generate_batch_size, num_samples - s0)
         torch.cuda.synchronize()
         t0 = time.time()
         coords_b, feats_b = model.diffusion.generate(num=n, batch_size=n, progress=False, dtype=dtype, use_graph=use_graph,
-                                                         sampling_steps=sampling_steps, eta=eta)
+                                                         sampling_steps=sampling_steps, eta=eta, **new)
         torch.cuda.synchronize()
         t_gen += time.time() - t0
         for coords, feats in zip(coords_b, feats_b):

@@ -86,6 +86,7 @@ SIGNATURES = {
     "npcd_ddpm_reverse_step": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P, _P, _P, _P, _P, c_float, c_float, c_int, _P]),
     "npcd_sampler_step": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "npcd_sampler_step_keep": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, _P]),
+    "npcd_sampler_step_multistep": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int, _P]),
     "npcd_colsum_blocks": (c_int, [c_int]),
     "npcd_add_ln_fwd_dt": (c_int, [_P] * 8 + [c_int, c_int, c_float, c_int, _P]),
     "npcd_ln_bwd_dt": (c_int, [_P] * 11 + [c_int, c_int, c_int, _P]),

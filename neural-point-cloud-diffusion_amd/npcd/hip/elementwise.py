@@ -486,6 +486,37 @@ def sampler_step(coords, feats, t, table, deterministic):
     return (oc, x0c), (of, x0f)
 
 
+def sampler_step_multistep(coords, feats, t, table):
+    """One second-order multistep step (DPM-Solver++ 2M) of the scheduled sampler for BOTH tensors in one launch
+    (npcd_sampler_step_multistep).  `coords` / `feats` are the dicts of sampler_step plus, for every tensor that is not in hold mode,
+         hist: contiguous fp32 tensor with the shape of x_t, the previous step's x0 -- read where the row's w is not 0, then overwritten
+               in place with this step's x0 (`known` at kept points)
+       noise is read only by a hold-mode tensor and by a tensor with a mask.  t int64 [B]; table fp32 [T, 8] is
+       SamplingSchedule.multistep_table (w in column 7).  -> ((out, x0 or None) of coords, (out, x0 or None) of feats)."""
+    require_gpu(t, table)
+    if t.dtype != torch.int64 or table.dtype != _f32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise RuntimeError("sampler_step_multistep: t is int64 [B], table a contiguous fp32 [T, 8]")
+    t = t.contiguous()
+    B = t.shape[0]
+    rc, oc, x0c, mc, keep_c = _sampler_tensor(coords, B)
+    rf, of, x0f, mf, keep_f = _sampler_tensor(feats, B)
+    hist = []
+    for spec, rec in ((coords, rc), (feats, rf)):
+        h = spec.get("hist")
+        if h is not None:
+            require_gpu(h)
+            if h.dtype != _f32 or not h.is_contiguous() or h.numel() != B * rec.per_sample:
+                raise RuntimeError("sampler_step_multistep: hist is a contiguous fp32 tensor with the shape of x_t (it is written in place)")
+        hist.append(h)
+    if mc is not None and mf is not None and mc.shape != mf.shape:
+        raise RuntimeError("sampler_step_multistep: the two masks are [B, N] with one N")
+    n_points = 0 if mc is None and mf is None else (mc if mc is not None else mf).shape[1]
+    check(lib().npcd_sampler_step_multistep(ctypes.byref(rc), ctypes.byref(rf), ptr(hist[0]), ptr(hist[1]), ptr(mc), ptr(mf), n_points,
+                                            ptr(t), ptr(table), table.shape[0], B, stream_ptr()), "npcd_sampler_step_multistep")
+    del keep_c, keep_f
+    return (oc, x0c), (of, x0f)
+
+
 def q_sample(x0, noise, t, tab_sqrt_acp, tab_sqrt_1macp):
     """x_t = sqrt(acp[t]) x_0 + sqrt(1 - acp[t]) noise in one launch (coefficients looked up on the device).  fp32 [B, ...]."""
     require_gpu(x0, noise, t)

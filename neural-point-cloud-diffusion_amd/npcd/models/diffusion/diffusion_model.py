@@ -81,7 +81,7 @@ class DiffusionModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, num, batch_size=8, progress=True, dtype=None, use_graph=False, sampling_steps=None, eta=None, coords=None, feats=None,
-                 keep_coords=None, keep_feats=None, keep=None, resample=None):
+                 keep_coords=None, keep_feats=None, keep=None, resample=None, spacing=None, solver=None):
         """Reference :108-133.  Two options the reference does not have: `dtype` (e.g. torch.bfloat16) runs the denoiser under
         autocast on the MFMA attention kernels -- 6x faster per reverse step than the reference's fp32 sampling, eps within the
         training-time bf16 tolerance; `use_graph` replays each reverse step from a captured HIP graph.
@@ -97,7 +97,12 @@ class DiffusionModel(nn.Module):
         both tensors may be given, and a tensor given without a mask is kept at every point.  The result is where(mask, given,
         sampled): the caller's values at kept points, unclipped, bit for bit (the given values at free points are not read).
         `resample` = r >= 1 performs every transition r times with a re-noise in between, which is what makes the free points follow
-        the kept ones (docs/experiments.md); it also works without masks."""
+        the kept ones (docs/experiments.md); it also works without masks.
+
+        `spacing` / `solver` (p_sample_loop(spacing=, solver=), scheduled sampling too): spacing = "logsnr" places the `sampling_steps`
+        levels uniformly in the log signal-to-noise ratio; solver = "dpmpp2m" is the second-order multistep step (DPM-Solver++ 2M),
+        deterministic (eta None or 0) and on "logsnr" levels unless `spacing` says otherwise -- the same error as the DDIM step for
+        a fraction of the denoiser forwards (docs/experiments.md).  It composes with held and kept tensors, not with resample > 1."""
         assert not self.training, "Model must be in eval mode for generation"
         if keep is not None:
             if keep_coords is not None or keep_feats is not None:
@@ -131,24 +136,30 @@ class DiffusionModel(nn.Module):
         if backbone is not None:
             backbone.fp32_class = fp32_class
         try:
-            return self._generate(sizes, device, ctx, progress, use_graph, sampling_steps, eta, coords, feats, keep_coords, keep_feats, resample)
+            return self._generate(sizes, device, ctx, progress, use_graph, sampling_steps, eta, coords, feats, keep_coords, keep_feats, resample,
+                                  spacing, solver)
         finally:
             if backbone is not None:
                 backbone.fp32_class = prev_mode
 
     def _generate(self, sizes, device, ctx, progress, use_graph, sampling_steps=None, eta=None, coords=None, feats=None, keep_coords=None,
-                  keep_feats=None, resample=None):
+                  keep_feats=None, resample=None, spacing=None, solver=None):
         coords_out, feats_out = [], []
         masked = keep_coords is not None or keep_feats is not None
         sides = (("coords", coords, keep_coords, self.coords_normalization), ("feats", feats, keep_feats, self.feats_normalization))
-        scheduled = sampling_steps is not None or eta is not None or coords is not None or feats is not None or resample is not None
+        scheduled = (sampling_steps is not None or eta is not None or coords is not None or feats is not None or resample is not None
+                     or spacing is not None or solver is not None)
         done = 0
         for bs in sizes:
             c = torch.randn(bs, self.coords_dim, self.num_points, device=device)
             f = torch.randn(bs, self.feats_dim, self.num_points, device=device)
-            new = dict(steps=sampling_steps, eta=1.0 if eta is None else eta) if scheduled else {}
+            new = dict(steps=sampling_steps, eta=1.0 if (eta is None and solver is None) else eta) if scheduled else {}
             if resample is not None:
                 new["resample"] = resample
+            if spacing is not None:
+                new["spacing"] = spacing
+            if solver is not None:                     # deterministic: eta stays None (or the caller's 0)
+                new["solver"] = solver
             given = {}
             for name, full, mask, norm in sides:
                 if full is None:

@@ -39,13 +39,45 @@ class SamplingSchedule:
         x = g1 x + g2 z:   g1 = sqrt(a / p),  g2 = sqrt(1 - a / p)
     `renoise64` holds the float64 g1, g2 [K]; `renoise_table` is a second fp32 [T, 8] table with them, rounded once, in the h1 / h2
     columns of row tau_i (the other coefficient columns and the rows off the schedule are NaN): a hold-mode launch of the step kernel
-    on it, with `known` = the current state, is the re-noise."""
+    on it, with `known` = the current state, is the re-noise.
 
-    def __init__(self, process, T, K, eta, device):
+    spacing = "logsnr" places the levels uniformly in lambda = log(acp / (1 - acp)) / 2 instead of uniformly in t (_logsnr_levels);
+    every coefficient above follows from the levels as before.  solver = "dpmpp2m" (eta = 0 only) adds the weights of the second-order
+    multistep step (DPM-Solver++ 2M in data prediction, Lu et al. 2022).  The transitions are performed in the order i = K-1 ... 0;
+    with h_i = lambda(tau_{i-1}) - lambda(tau_i), the step that leaves tau_i replaces x0 in x_prev = c1 x0 + c2 x_t by
+        D = x0 + w_i (x0 - x0 of the step before),   w_i = h_i / (2 h_{i+1}) for 1 <= i <= K-2,   w_{K-1} = w_0 = 0
+    (the first step has no history; the step to the data spans an infinite lambda interval and stays first order).  `coef64["w"]` holds
+    the float64 weights; `multistep_table` is `table` with w, rounded once, in column 7 of the rows on the schedule.  Both exist only
+    with the solver.  On levels uniform in t the last weights exceed 2 and the step is worse than DDIM (docs/experiments.md): the
+    solver's default spacing is "logsnr"."""
+
+    @staticmethod
+    def _logsnr_levels(lam, K):
+        """K distinct levels of a chain with decreasing lambda [T], as near as distinct levels can be to K targets uniform in lambda
+        from lambda(0) to lambda(T - 1): the nearest level of every target, pushed apart upwards from level 0, the last one set to
+        T - 1, pushed apart downwards from there.  [T - 1] for K = 1, arange(T) for K = T."""
+        T = lam.shape[0]
+        if K == 1:
+            return np.array([T - 1], dtype=np.int64)
+        targets = np.linspace(lam[0], lam[T - 1], K)
+        ts = np.abs(lam[None, :] - targets[:, None]).argmin(axis=1).astype(np.int64)
+        for i in range(1, K):
+            ts[i] = max(ts[i], ts[i - 1] + 1)
+        ts[K - 1] = T - 1
+        for i in range(K - 2, -1, -1):
+            ts[i] = min(ts[i], ts[i + 1] - 1)
+        return ts
+
+    def __init__(self, process, T, K, eta, device, spacing="uniform", solver=None):
         self.T, self.steps, self.eta, self.deterministic = T, K, eta, eta == 0.0
-        ts = np.array([T - 1], dtype=np.int64) if K == 1 else np.round(np.linspace(0.0, T - 1.0, K)).astype(np.int64)
-        self.timesteps = ts
+        self.spacing, self.solver = spacing, solver
         acp = np.cumprod(1.0 - np.asarray(process.np_betas, dtype=np.float64)[:T])
+        lam = 0.5 * np.log(acp / (1.0 - acp))
+        if spacing == "logsnr":
+            ts = self._logsnr_levels(lam, K)
+        else:
+            ts = np.array([T - 1], dtype=np.int64) if K == 1 else np.round(np.linspace(0.0, T - 1.0, K)).astype(np.int64)
+        self.timesteps = ts
         a = acp[ts]
         p = np.concatenate(([1.0], a[:-1]))
         sigma = eta * np.sqrt((1.0 - p) / (1.0 - a)) * np.sqrt(1.0 - a / p)
@@ -66,6 +98,15 @@ class SamplingSchedule:
         renoise[idx, 6] = torch.from_numpy(self.renoise64["g2"]).float()
         renoise[idx, 7] = 0.0
         self.renoise_table = renoise.to(device).contiguous()
+        if solver == "dpmpp2m":
+            w = np.zeros(K, dtype=np.float64)
+            if K > 2:
+                h = lam[ts[:-1]] - lam[ts[1:]]                                # h[i - 1] = h_i, i = 1 .. K-1
+                w[1:K - 1] = h[:-1] / (2.0 * h[1:])
+            self.coef64["w"] = w
+            multistep = table.clone()
+            multistep[idx, 7] = torch.from_numpy(w).float()
+            self.multistep_table = multistep.to(device).contiguous()
 
 
 class GaussianDiffusion(nn.Module):
@@ -189,23 +230,36 @@ class GaussianDiffusion(nn.Module):
         return c_next, f_next
 
     # ---- scheduled sampler: strided DDIM schedule with eta in [0, 1], replacement conditioning ---------------------------------
-    def sampling_schedule(self, steps=None, eta=1.0, device=None):
+    def sampling_schedule(self, steps=None, eta=None, device=None, spacing=None, solver=None):
         """The SamplingSchedule of `steps` levels (None: all T = self.num_timesteps, read now) and `eta`, its table on `device`
-        (default: where the module's tables are); cached per (T, steps, eta, device)."""
+        (default: where the module's tables are); cached per (T, steps, eta, device, spacing, solver).  `spacing`: "uniform" (levels
+        uniform in t) or "logsnr" (uniform in the log signal-to-noise ratio); `solver`: None (the DDIM step) or "dpmpp2m" (the
+        second-order multistep step; deterministic, so eta is None or 0).  eta None: 1 without a solver; spacing None: "uniform" without
+        a solver, "logsnr" with one."""
         T = int(self.num_timesteps)
         K = T if steps is None else int(steps)
         if steps is not None and K != steps:
             raise ValueError(f"sampling steps must be an integer (got {steps!r})")
         if not 1 <= K <= T:
             raise ValueError(f"sampling steps must lie in 1..{T} (got {K})")
+        if solver not in (None, "dpmpp2m"):
+            raise ValueError(f"solver is None or 'dpmpp2m' (got {solver!r})")
+        if spacing is None:
+            spacing = "uniform" if solver is None else "logsnr"
+        if spacing not in ("uniform", "logsnr"):
+            raise ValueError(f"spacing is 'uniform' or 'logsnr' (got {spacing!r})")
+        if eta is None:
+            eta = 1.0 if solver is None else 0.0
         eta = float(eta)
         if not 0.0 <= eta <= 1.0:
             raise ValueError(f"eta must lie in [0, 1] (got {eta})")
+        if solver is not None and eta != 0.0:
+            raise ValueError(f"solver={solver!r} is deterministic: eta must be None or 0 (got {eta})")
         device = torch.device(self.sqrt_recip_alphas_cumprod.device if device is None else device)
-        key = (T, K, eta, str(device))
+        key = (T, K, eta, str(device), spacing, solver)
         cache = self.__dict__.setdefault("_schedules", {})
         if key not in cache:
-            cache[key] = SamplingSchedule(self, T, K, eta, device)
+            cache[key] = SamplingSchedule(self, T, K, eta, device, spacing, solver)
         return cache[key]
 
     @staticmethod
@@ -253,11 +307,52 @@ class GaussianDiffusion(nn.Module):
         zf = torch.randn_like(f) if draw_f else None
         return zc, zf
 
-    def _scheduled_update(self, c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep):
+    def _multistep_update(self, c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist):
+        """_scheduled_update for solver="dpmpp2m": the reverse step with x0 replaced by D = x0 + w (x0 - hist) where the level's w is
+        not 0 (selected: a history that is not read may hold anything), hist = (coords history, feats history), each the previous
+        step's clipped x0 of its tensor (None for a held tensor), overwritten in place with this step's (the known values at kept
+        points).  fused: ONE npcd_sampler_step_multistep launch for both tensors."""
+        if fused:
+            from ...hip import elementwise as ew
+            spec = []
+            for name, x, eps, z, clip, h in (("coords", c, eps_c, zc, clip_c, hist[0]), ("feats", f, eps_f, zf, clip_f, hist[1])):
+                if which == name:
+                    spec.append(dict(mode="hold", known=known, noise=z))
+                    continue
+                eps = eps if eps.dtype in (torch.float32, torch.bfloat16) else eps.float()
+                if name in keep:
+                    spec.append(dict(mode="keep", x_t=x, eps=eps, noise=z, known=keep[name][0], keep=keep[name][1], clip=clip, hist=h))
+                else:
+                    spec.append(dict(mode="reverse", x_t=x, eps=eps, clip=clip, hist=h))
+            (c_next, _), (f_next, _) = ew.sampler_step_multistep(spec[0], spec[1], t, sched.multistep_table)
+            return c_next, f_next
+        row = sched.multistep_table.to(t.device)[t]                         # [B, 8]: r, m, c1, c2, 0, h1, h2, w
+        out = []
+        for name, x, eps, z, clip, h in (("coords", c, eps_c, zc, clip_c, hist[0]), ("feats", f, eps_f, zf, clip_f, hist[1])):
+            k = [row[:, j].reshape((-1,) + (1,) * (x.dim() - 1)) for j in range(8)]
+            if which == name:
+                out.append(k[5] * known + k[6] * z)
+                continue
+            x0 = k[0] * x - k[1] * (eps if eps.dtype == torch.float64 else eps.float())
+            if clip is not None:
+                x0 = torch.clamp(x0, clip[0], clip[1])
+            nxt = k[2] * torch.where(k[7] == 0, x0, x0 + k[7] * (x0 - h)) + k[3] * x
+            if name in keep:
+                kn, mask = keep[name]
+                nxt = torch.where(mask[:, None, :], k[5] * kn + k[6] * z, nxt)
+                x0 = torch.where(mask[:, None, :], kn, x0)
+            h.copy_(x0)
+            out.append(nxt)
+        return out[0], out[1]
+
+    def _scheduled_update(self, c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist=None):
         """The update of one step on given eps and noise.  fused: ONE launch for both tensors (npcd_sampler_step, or
         npcd_sampler_step_keep when a tensor has a mask), clip_* are (lo, hi) floats or None; otherwise the same step in torch,
         clip_* are the ranges as given to p_sample_loop.  A tensor with a mask: where(mask, the hold expression on its known values,
-        the reverse step) -- selected, so that nothing of the branch not taken reaches the result."""
+        the reverse step) -- selected, so that nothing of the branch not taken reaches the result.  hist given: the second-order
+        multistep step (_multistep_update)."""
+        if hist is not None:
+            return self._multistep_update(c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist)
         if fused:
             from ...hip import elementwise as ew
             spec = []
@@ -290,12 +385,12 @@ class GaussianDiffusion(nn.Module):
                 out.append(nxt if z is None else nxt + k[4] * z)
         return out[0], out[1]
 
-    def _scheduled_step(self, denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused, keep=None):
+    def _scheduled_step(self, denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused, keep=None, hist=None):
         """One step of the scheduled loop: the denoiser, the draws (_scheduled_noise fixes the RNG order), the update."""
         keep = keep or {}
         eps_c, eps_f = denoise_fn(c, f, t)
         zc, zf = self._scheduled_noise(c, f, sched, which, keep)
-        return self._scheduled_update(c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep)
+        return self._scheduled_update(c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist)
 
     @staticmethod
     def _renoise(c, f, zc, zf, t, sched, fused):
@@ -314,14 +409,17 @@ class GaussianDiffusion(nn.Module):
         return out[0], out[1]
 
     def _p_sample_loop_scheduled(self, denoise_fn, coords_start, feats_start, coords_clip_range, feats_clip_range, progress, use_graph,
-                                 steps, eta, hold, keep=None, resample=None):
-        """The loop behind p_sample_loop(steps=, eta=, hold=, keep=, resample=): the schedule's levels in descending order, each
-        transition performed `resample` times (_scheduled_step) with a re-noise (_renoise) between two performances."""
+                                 steps, eta, hold, keep=None, resample=None, spacing=None, solver=None):
+        """The loop behind p_sample_loop(steps=, eta=, hold=, keep=, resample=, spacing=, solver=): the schedule's levels in
+        descending order, each transition performed `resample` times (_scheduled_step) with a re-noise (_renoise) between two
+        performances.  solver="dpmpp2m": the second-order multistep step, its two history buffers allocated here, once."""
         c, f = coords_start, feats_start
         r = 1 if resample is None else int(resample)
         if r != (1 if resample is None else resample) or r < 1:
             raise ValueError(f"resample must be an integer >= 1 (got {resample!r})")
-        sched = self.sampling_schedule(steps, 1.0 if eta is None else eta, device=c.device)
+        if solver is not None and r > 1:
+            raise ValueError("resample > 1 cannot be combined with a multistep solver: a re-noise invalidates the history")
+        sched = self.sampling_schedule(steps, eta, device=c.device, spacing=spacing, solver=solver)
         which, known = self._hold_spec(hold)
         keep = self._keep_spec(keep, hold, c, f)
         levels = [int(i) for i in sched.timesteps[::-1]]
@@ -342,16 +440,19 @@ class GaussianDiffusion(nn.Module):
         fused = c.is_cuda and c.dtype == torch.float32 and f.dtype == torch.float32 and not (has_c and clip_c is None) and not (has_f and clip_f is None)
         if not fused:
             clip_c, clip_f = coords_clip_range, feats_clip_range
+        hist = None
+        if solver is not None:                # the previous step's x0 per tensor; the first step (w = 0) does not read it
+            hist = tuple(None if which == name else torch.zeros(x.shape, dtype=x.dtype, device=x.device) for name, x in (("coords", c), ("feats", f)))
         if not (fused and use_graph):
             for i in levels:
                 t.fill_(i)
                 for j in range(r):
-                    c, f = self._scheduled_step(denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused, keep)
+                    c, f = self._scheduled_step(denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused, keep, hist)
                     if j + 1 < r:
                         c, f = self._renoise(c, f, torch.randn_like(c), torch.randn_like(f), t, sched, fused)
             return c, f
-        if keep or r > 1:
-            return self._scheduled_graph_loop(denoise_fn, c, f, t, levels, r, sched, which, known, clip_c, clip_f, keep)
+        if keep or r > 1 or hist is not None:
+            return self._scheduled_graph_loop(denoise_fn, c, f, t, levels, r, sched, which, known, clip_c, clip_f, keep, hist)
         # graph replay, as in p_sample_loop: static state buffers, warm-up on a side stream, one captured step, t refilled between replays
         sc, sf = c.clone(), f.clone()
         side = torch.cuda.Stream()
@@ -370,10 +471,12 @@ class GaussianDiffusion(nn.Module):
             sf.copy_(of)
         return sc.clone(), sf.clone()
 
-    def _scheduled_graph_loop(self, denoise_fn, c, f, t, levels, r, sched, which, known, clip_c, clip_f, keep):
-        """Graph replay of the loop with masks and / or resampling: one captured step (denoiser + update) and, for r > 1, one captured
-        re-noise, on static state and noise buffers.  The noise is drawn between the replays, by the calls and in the order of the
-        eager loop, so that eager and replayed sampling consume the generator alike and give the same bits."""
+    def _scheduled_graph_loop(self, denoise_fn, c, f, t, levels, r, sched, which, known, clip_c, clip_f, keep, hist=None):
+        """Graph replay of the loop with masks, resampling and / or the multistep solver: one captured step (denoiser + update) and,
+        for r > 1, one captured re-noise, on static state and noise buffers.  The noise is drawn between the replays, by the calls and
+        in the order of the eager loop, so that eager and replayed sampling consume the generator alike and give the same bits.
+        `hist` (the multistep solver's history) is static too: the captured step updates it in place.  The warm-up steps write it,
+        which is harmless: the first replay is the first level's, whose w is 0 and which does not read it."""
         sc, sf = c.clone(), f.clone()
         draw_c, draw_f = self._scheduled_draws(sched, which, keep)
         zc = torch.zeros_like(sc) if draw_c else None                       # the noise of a step, refilled before every replay
@@ -382,7 +485,7 @@ class GaussianDiffusion(nn.Module):
 
         def step():
             eps_c, eps_f = denoise_fn(sc, sf, t)
-            return self._scheduled_update(sc, sf, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, True, keep)
+            return self._scheduled_update(sc, sf, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, True, keep, hist)
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -418,7 +521,8 @@ class GaussianDiffusion(nn.Module):
         return sc.clone(), sf.clone()
 
     def p_sample_loop(self, denoise_fn, coords_start, feats_start, coords_clip_range=None, feats_clip_range=None,
-                      progress=False, use_graph=False, steps=None, eta=None, hold=None, keep=None, resample=None):
+                      progress=False, use_graph=False, steps=None, eta=None, hold=None, keep=None, resample=None, spacing=None,
+                      solver=None):
         """1000 reverse steps (reference :148-177 without the trajectory lists).  On the GPU with scalar clip ranges every step
         runs the fused posterior update; `use_graph` additionally captures one whole step (denoiser forward + update, fixed
         batch) in a HIP graph and replays it -- the per-step launch work (~600 launches at 24 layers) leaves the host.
@@ -435,10 +539,17 @@ class GaussianDiffusion(nn.Module):
         reverse step.  resample = r >= 1 (None: 1) performs every transition r times, with both tensors re-noised in whole back to the
         level the transition left between two performances (RePaint, Lugmayr et al. 2022: with one pass the free points largely ignore
         the kept ones, docs/experiments.md).  RNG order: per performance coords noise, then feats noise (a tensor with a mask always
-        draws); per re-noise coords noise, then feats noise, always both."""
-        if steps is not None or eta is not None or hold is not None or keep is not None or resample is not None:
+        draws); per re-noise coords noise, then feats noise, always both.
+
+        `spacing` and `solver` select the scheduled loop too (sampling_schedule).  spacing = "logsnr" places the `steps` levels
+        uniformly in the log signal-to-noise ratio instead of uniformly in t; it works with every mode above.  solver = "dpmpp2m" is
+        the second-order multistep step (DPM-Solver++ 2M, data prediction): deterministic (eta None or 0), on "logsnr" levels unless
+        `spacing` says otherwise, one extra buffer per tensor for the previous step's x0, still one launch per step and
+        graph-capturable.  hold and keep compose with it; resample > 1 does not (a re-noise invalidates the history)."""
+        if (steps is not None or eta is not None or hold is not None or keep is not None or resample is not None or spacing is not None
+                or solver is not None):
             return self._p_sample_loop_scheduled(denoise_fn, coords_start, feats_start, coords_clip_range, feats_clip_range, progress,
-                                                 use_graph, steps, eta, hold, keep, resample)
+                                                 use_graph, steps, eta, hold, keep, resample, spacing, solver)
         steps = range(self.num_timesteps - 1, -1, -1)
         if progress:
             from tqdm.auto import tqdm
