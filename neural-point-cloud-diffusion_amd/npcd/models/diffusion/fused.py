@@ -12,7 +12,9 @@ instead of ~40 autograd nodes per block:
 Numerics follow the reference's bf16-autocast step: bf16 GEMM inputs with fp32 accumulation, fp32
 residual stream, fp32 LayerNorm statistics, exact-erf GELU.
 """
+import contextlib
 import math
+import os
 
 import torch
 
@@ -25,6 +27,86 @@ _bf16, _f32 = torch.bfloat16, torch.float32
 _BLOCK_PARAMS = ("ln_1.weight", "ln_1.bias", "attn.c_qkv.weight", "attn.c_qkv.bias", "attn.c_proj.weight", "attn.c_proj.bias",
                  "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")
 _LINEARS = ("attn_c_qkv", "attn_c_proj", "mlp_c_fc", "mlp_c_proj")          # the four Linear layers of a block, in parameter order
+_NULL = contextlib.nullcontext()
+
+
+# ---- the switches: every environment variable this module reads, read once, here (README "Environment switches") --------------------
+# They exist for A/B measurements; what each one selects, and what was measured, stands next to the code that uses it.
+def _env_on(name):
+    """An on/off switch that is off by default: unset, "" and "0" are off, anything else is on."""
+    return os.environ.get(name, "") not in ("", "0")
+
+
+def _env_not_off(name):
+    """An on/off switch that is on by default: "0" is off, anything else (unset and "" too) is on."""
+    return os.environ.get(name, "") != "0"
+
+
+def _env_int(name, default):
+    """An integer from the environment (unset: the default); anything that is no integer raises a ValueError that names the variable."""
+    try:
+        return int(os.environ.get(name, default))
+    except ValueError:
+        raise ValueError(f"{name}={os.environ[name]!r}: expected an integer") from None
+
+
+def _parse_wgrad_stream(value):
+    """NPCD_WGRAD_STREAM -> (enabled, max token rows): unset = on below 20,000 rows, "0" = off, "1" = on at every size, any other
+    integer = on up to that many rows.  Parsed ONCE, here (ADVICE r5: it had been read twice with two meanings).  Anything else
+    raises a ValueError that names the variable."""
+    if value is None or value == "":
+        return True, 20000
+    if value == "0":
+        return False, 0
+    if value == "1":
+        return True, 1 << 62
+    try:
+        return True, int(value)
+    except ValueError:
+        raise ValueError(f"NPCD_WGRAD_STREAM={value!r}: expected unset, 0 (off), 1 (on at every size) or a token-row limit") from None
+
+
+def _parse_wgrad_multiblock(value):
+    """NPCD_WGRAD_MULTIBLOCK -> "on" (unset, "", "1"), "off" ("0") or "force"; anything else raises a ValueError that names the
+    variable.  Parsed once, here."""
+    modes = {None: "on", "": "on", "1": "on", "0": "off", "force": "force"}
+    if value not in modes:
+        raise ValueError(f"NPCD_WGRAD_MULTIBLOCK={value!r}: expected unset, 0 (off), 1 (on) or force (skip the fill rule)")
+    return modes[value]
+
+
+# the token-dimension split of the forward / data-gradient GEMMs (_split_gemm)
+_SPLIT = 0 if _env_on("NPCD_NO_GEMM_SPLIT") else 256
+_SPLIT_MIN = _env_int("NPCD_GEMM_SPLIT_MIN", 16000)
+_SPLIT_BIG_FIRST = not _env_on("NPCD_GEMM_SPLIT_SMALL_FIRST")
+_SPLIT_WIDE_N = _env_int("NPCD_GEMM_SPLIT_WIDE_N", 4096)
+# attn.c_proj at a rank's token count on the own 128 x 128-tile kernel (_linear)
+_LIN128 = not _env_on("NPCD_NO_LIN128")
+_LIN128_MAX_T = _env_int("NPCD_LIN128_MAX_T", 4200)
+# the data gradients: the transposed weight shadow (FusedBackboneEngine), the own mlp.c_proj product with the GELU backward (_own_dgelu)
+_DGRAD_NN = _env_on("NPCD_DGRAD_NN")
+_DGRAD_T_MIN_T = _env_int("NPCD_DGRAD_T_MIN_T", 16000)
+_OWN_DGELU = _env_on("NPCD_OWN_DGELU")
+_ATTN_COLSUM = not _env_on("NPCD_NO_ATTN_COLSUM")     # c_qkv bias gradient from the attention backward itself
+# one weight-gradient product (_wgrad)
+_OWN_WGRAD = _env_on("NPCD_OWN_WGRAD")
+_SUM_KERNEL = not _env_on("NPCD_NO_SUM_KERNEL")       # the weight-gradient partials summed by csrc/elementwise.hip
+# where and when the weight gradients of the 16-bit backward are issued (_WgradSchedule)
+_WGRAD_STREAM, _WGRAD_STREAM_MAX_T = _parse_wgrad_stream(os.environ.get("NPCD_WGRAD_STREAM"))
+_WGRAD_STREAM_PRIO = _env_int("NPCD_WGRAD_STREAM_PRIO", 0)
+_WGRAD_GROUP = _env_not_off("NPCD_WGRAD_GROUP")
+_WGRAD_GROUP_MAX_T = _env_int("NPCD_WGRAD_GROUP_MAX_T", 17000)
+_JOIN_PER_BLOCK = _env_on("NPCD_WGRAD_JOIN_PER_BLOCK")
+_WGRAD_MULTIBLOCK = _parse_wgrad_multiblock(os.environ.get("NPCD_WGRAD_MULTIBLOCK"))
+_WGRAD_MULTIBLOCK_MIN_T = _env_int("NPCD_WGRAD_MULTIBLOCK_MIN_T", 20000)
+# the step arena of the 16-bit node (FusedBackboneEngine)
+_STEP_ARENA = _env_not_off("NPCD_STEP_ARENA")
+_STEP_ARENA_MAX_T = _env_int("NPCD_STEP_ARENA_MAX_T", 20000)
+# the form of the fp32-class weight gradients (_BackboneX2Fn)
+_X2_WGRAD = os.environ.get("NPCD_X2_WGRAD", "library")
+if _X2_WGRAD not in ("library", "own"):
+    raise ValueError(f"NPCD_X2_WGRAD={_X2_WGRAD!r}: expected library or own")
+# ---- end of the switches ------------------------------------------------------------------------------------------------------------
 
 
 # ---- token-dimension split of the forward / data-gradient GEMMs ---------------------------------------------------------------
@@ -35,46 +117,12 @@ _LINEARS = ("attn_c_qkv", "attn_c_proj", "mlp_c_fc", "mlp_c_proj")          # th
 # its workgroups queue behind the large GEMM's and the join waits for them: no gain at either stream priority.  Tried: a
 # hand-written kernel for the 64 left-over rows of the forward -- one pass over the weights straight into MFMA fragments,
 # split-K over 8 waves: 11.5 us per call in situ against the tuned library's 12.8 us, 0.2-0.5 % of a step; both are bound by
-# pulling 2-8 MB of cold weights through a launch that is over before it has filled the chip.  Not kept.)
-import os
-
-
-def _env_on(name):
-    """An on/off switch from the environment: unset, "" and "0" are off, anything else is on."""
-    return os.environ.get(name, "") not in ("", "0")
-
-
-_SPLIT = 0 if os.environ.get("NPCD_NO_GEMM_SPLIT") else 256       # (the env switches exist for A/B measurements)
-_SPLIT_MIN = int(os.environ.get("NPCD_GEMM_SPLIT_MIN", "16000"))
-# the left-over rows go BEHIND the large call: they then find the weights in L2 / MALL (82.08 against 82.32 ms per step, two
-# alternating rounds, tools/run_split_order_ab.sh; NPCD_GEMM_SPLIT_SMALL_FIRST=1 restores the old order)
-_SPLIT_BIG_FIRST = not os.environ.get("NPCD_GEMM_SPLIT_SMALL_FIRST")
-_ATTN_COLSUM = not os.environ.get("NPCD_NO_ATTN_COLSUM")      # c_qkv bias gradient from the attention backward itself (A/B switch)
-_SUM_KERNEL = not os.environ.get("NPCD_NO_SUM_KERNEL")          # the weight-gradient partials summed by csrc/elementwise.hip (A/B switch)
-# opt-in: the weight gradients on the own split-T kernel (csrc/gemm.hip: at parity with the library's row-split form -- both are
-# bound by the L2 -> LDS stream of a 256 x 256 tile -- bitwise reproducible, no library call)
-_OWN_WGRAD = _env_on("NPCD_OWN_WGRAD")
-# opt-in: the data gradient of mlp.c_proj as the own NT product with the GELU backward and the c_fc bias-gradient column sums in its
-# epilogue (csrc/gemm_nt.hip, docs/experiments.md R4.1) on the full 256-row tiles of the token range; the remainder rows keep the
-# library product + the separate kernel.  Reads the engine's transposed shadow of the weight (below).
-_OWN_DGELU = _env_on("NPCD_OWN_DGELU")
-# The data gradients dy @ W read a TRANSPOSED 16-bit shadow of the four Linear weights of every block (FusedBackboneEngine), i.e. they
-# are the forward's BLAS-TN form dy @ (W^T)^T instead of BLAS-NN against the weight as stored: the library's TN kernel is the faster
-# one at these shapes (docs/experiments.md R10.1).  The shadow is re-transposed per block in the forward, one launch per block, only
-# after the 16-bit shadow was written (once per optimizer step).  NPCD_DGRAD_NN=1: the product against the weight as stored, no
-# transposed shadow kept up to date (A/B).  NPCD_DGRAD_T_MIN_T: the token rows from which the transposed form is used -- the
-# saving grows with the token rows, the transposes (13 us per block) do not: at 4,104 rows the two cancel (13 us saved per block).
-_DGRAD_NN = _env_on("NPCD_DGRAD_NN")
-_DGRAD_T_MIN_T = int(os.environ.get("NPCD_DGRAD_T_MIN_T", "16000"))
-
-
-# Below _SPLIT_MIN only the products whose OUTPUT is at least this wide are split (round 5, R5.18): at T = 4,104 / 8,208 the left-over
-# row of 256-row tiles turns the 4,096-wide products (c_fc forward, mlp.c_proj data gradient) from 256 / 512 tiles = one / two full
-# rounds into 272 / 528.  Same box, alternating processes: a rank's step at per-GPU batch 8 18.51-18.57 -> 18.18-18.36 ms, at 16
+# pulling 2-8 MB of cold weights through a launch that is over before it has filled the chip.  Not kept.)  NPCD_NO_GEMM_SPLIT=1: no
+# split; NPCD_GEMM_SPLIT_MIN: the token rows from which every product is split.
+# Below _SPLIT_MIN only the products whose OUTPUT is at least _SPLIT_WIDE_N wide are split (round 5, R5.18): at T = 4,104 / 8,208 the
+# left-over row of 256-row tiles turns the 4,096-wide products (c_fc forward, mlp.c_proj data gradient) from 256 / 512 tiles = one / two
+# full rounds into 272 / 528.  Same box, alternating processes: a rank's step at per-GPU batch 8 18.51-18.57 -> 18.18-18.36 ms, at 16
 # 28.71-28.75 -> 27.96-27.99 ms; with 3,072 (c_qkv too) 18.34.  NPCD_GEMM_SPLIT_WIDE_N=0 switches it off.
-_SPLIT_WIDE_N = int(os.environ.get("NPCD_GEMM_SPLIT_WIDE_N", "4096"))
-
-
 def _split_gemm(fn, T, N=0):
     """fn(rows) enqueues the product for a row range into a shared output."""
     # below ~16 k tokens the large call is short enough that the extra launch costs what the quarter tile did (measured at
@@ -84,22 +132,17 @@ def _split_gemm(fn, T, N=0):
     if Tm == 0 or Tm == T:
         fn(slice(0, T))
         return
-    if _SPLIT_BIG_FIRST:
-        fn(slice(0, Tm))
-        fn(slice(Tm, T))
-        return
-    fn(slice(Tm, T))
-    fn(slice(0, Tm))
+    # the left-over rows go BEHIND the large call: they then find the weights in L2 / MALL (82.08 against 82.32 ms per step, two
+    # alternating rounds, tools/run_split_order_ab.sh; NPCD_GEMM_SPLIT_SMALL_FIRST=1 restores the old order)
+    big, rest = slice(0, Tm), slice(Tm, T)
+    for rows in ((big, rest) if _SPLIT_BIG_FIRST else (rest, big)):
+        fn(rows)
 
 
 # The token counts of one rank of a 4- / 8-GPU job (8,208 / 4,104 rows): the square product of the block (attn.c_proj, N = K = 1,024:
 # 64-68 tiles of 256 x 256 for 256 CUs in the library's form) goes to the own 128 x 128-tile kernel, which measured 1.3 x the tuned
 # library there (17.6-18.1 against 23-29 us at T = 4,104; docs/experiments.md R4.7) and loses on every other shape of the block --
-# selected by shape, NPCD_NO_LIN128=1 switches it off (A/B).
-_LIN128 = not os.environ.get("NPCD_NO_LIN128")
-_LIN128_MAX_T = int(os.environ.get("NPCD_LIN128_MAX_T", "4200"))
-
-
+# selected by shape (up to _LIN128_MAX_T rows, NPCD_LIN128_MAX_T), NPCD_NO_LIN128=1 switches it off (A/B).
 def _linear(bias, x, w16):
     """x [T, K] bf16, w16 [N, K] bf16, bias [N] bf16 -> x @ w16^T + bias, [T, N] bf16."""
     T = x.shape[0]
@@ -113,6 +156,12 @@ def _linear(bias, x, w16):
     return out
 
 
+# The data gradients dy @ W read a TRANSPOSED 16-bit shadow of the four Linear weights of every block (FusedBackboneEngine), i.e. they
+# are the forward's BLAS-TN form dy @ (W^T)^T instead of BLAS-NN against the weight as stored: the library's TN kernel is the faster
+# one at these shapes (docs/experiments.md R10.1).  The shadow is re-transposed per block in the forward, one launch per block, only
+# after the 16-bit shadow was written (once per optimizer step).  NPCD_DGRAD_NN=1: the product against the weight as stored, no
+# transposed shadow kept up to date (A/B).  NPCD_DGRAD_T_MIN_T: the token rows from which the transposed form is used -- the
+# saving grows with the token rows, the transposes (13 us per block) do not: at 4,104 rows the two cancel (13 us saved per block).
 def _dgrad(dy, w16, wT=None):
     """dy [T, N] bf16, w16 [N, K] bf16 -> dy @ w16, [T, K] bf16.  wT [K, N]: w16 transposed (the engine's transposed shadow) -- the
     product then runs as dy @ wT^T, the forward's form; the large rows and the left-over rows of the split read the same buffer."""
@@ -137,6 +186,8 @@ def _wgrad(dy, x, out):
     Round 18: at T = 32,832 the four products of a block take 874 us this way inside the step (slab sums included); from
     _WGRAD_MULTIBLOCK_MIN_T token rows on the backward sends whole groups of blocks to one ew.wgrad_group launch instead (773 us per
     block, docs/experiments.md R18.1) and this function serves the L mod G blocks at the bottom and the fallback."""
+    # opt-in (NPCD_OWN_WGRAD=1): the own split-T kernel (csrc/gemm.hip: at parity with the library's row-split form -- both are bound
+    # by the L2 -> LDS stream of a 256 x 256 tile -- bitwise reproducible, no library call)
     if _OWN_WGRAD and ew.wgrad(dy, x, out):
         return
     T = dy.shape[0]
@@ -165,53 +216,26 @@ def _wgrad(dy, x, out):
 # and the gradients are the same bits (tests/test_gpu_fused.py).  Where it engages -- the grouped launch exists on the side stream
 # only -- side stream off runs the per-product library calls instead: two fp32 accumulation orders over the same 16-bit operands,
 # NOT the same bits (tests/test_gpu_rank_step.py bounds the difference).
-def _parse_wgrad_stream(value):
-    """NPCD_WGRAD_STREAM -> (enabled, max token rows): unset = on below 20,000 rows, "0" = off, "1" = on at every size, any other
-    integer = on up to that many rows.  Parsed ONCE, here (ADVICE r5: it had been read twice with two meanings).  Anything else
-    raises a ValueError that names the variable."""
-    if value is None or value == "":
-        return True, 20000
-    if value == "0":
-        return False, 0
-    if value == "1":
-        return True, 1 << 62
-    try:
-        return True, int(value)
-    except ValueError:
-        raise ValueError(f"NPCD_WGRAD_STREAM={value!r}: expected unset, 0 (off), 1 (on at every size) or a token-row limit") from None
-
-
-_WGRAD_STREAM, _WGRAD_STREAM_MAX_T = _parse_wgrad_stream(os.environ.get("NPCD_WGRAD_STREAM"))
+# Round 6: below _WGRAD_GROUP_MAX_T token rows the four weight gradients of a block are ONE launch of the own kernel (csrc/gemm.hip,
+# npcd_wgrad_group: a workgroup per 256 x 256 tile over the whole token range; 192 tiles at width 1,024), beside the critical path on the
+# side stream.  NPCD_WGRAD_GROUP=0 switches it off (the library's products), NPCD_WGRAD_GROUP_MAX_T sets the size limit.
+# Round 6: the main stream no longer waits for the side stream once per block (a cross-queue dependency costs ~10 us of an idle chip per
+# block even when it is already satisfied: tools/step_timeline.py on the rank step).  A block's gradients are handed to the reducer FROM the
+# side stream instead -- behind the block's weight gradients in that stream's order, and behind the block's critical path through the fork's
+# wait -- so a collective launched there depends on exactly what it reads; the main stream joins the side stream once, at the end of the
+# backward.  NPCD_WGRAD_JOIN_PER_BLOCK=1 restores the per-block join (A/B).
 _side = {}
 
 
 def _side_stream(device):
     s = _side.get(device)
     if s is None:
-        s = _side[device] = torch.cuda.Stream(device=device, priority=int(os.environ.get("NPCD_WGRAD_STREAM_PRIO", "0")))
+        s = _side[device] = torch.cuda.Stream(device=device, priority=_WGRAD_STREAM_PRIO)
     return s
 
 
 def _wgrad_side_ok(T):
     return _WGRAD_STREAM and T <= _WGRAD_STREAM_MAX_T
-
-
-# Round 6: below _WGRAD_GROUP_MAX_T token rows the four weight gradients of a block are ONE launch of the own kernel (csrc/gemm.hip,
-# npcd_wgrad_group: a workgroup per 256 x 256 tile over the whole token range; 192 tiles at width 1,024), beside the critical path on the
-# side stream.  NPCD_WGRAD_GROUP=0 switches it off (the library's products), NPCD_WGRAD_GROUP_MAX_T sets the size limit.
-_WGRAD_GROUP = os.environ.get("NPCD_WGRAD_GROUP", "1") != "0"
-_WGRAD_GROUP_MAX_T = int(os.environ.get("NPCD_WGRAD_GROUP_MAX_T", "17000"))
-# Round 6: the main stream no longer waits for the side stream once per block (a cross-queue dependency costs ~10 us of an idle chip per
-# block even when it is already satisfied: tools/step_timeline.py on the rank step).  A block's gradients are handed to the reducer FROM the
-# side stream instead -- behind the block's weight gradients in that stream's order, and behind the block's critical path through the fork's
-# wait -- so a collective launched there depends on exactly what it reads; the main stream joins the side stream once, at the end of the
-# backward.  NPCD_WGRAD_JOIN_PER_BLOCK=1 restores the per-block join (A/B).
-_JOIN_PER_BLOCK = _env_on("NPCD_WGRAD_JOIN_PER_BLOCK")
-# Round 6: below _STEP_ARENA_MAX_T token rows the ~740 buffers a step of the fused node allocates are kept and handed out again in the
-# same order by the next step (npcd/hip/arena.py): 1.6 ms of host time per step at per-GPU batch 8.  The memory of a step then stays
-# allocated between steps (at 4,104 rows ~8 GB; the caching allocator would keep most of it anyway).  NPCD_STEP_ARENA=0: off.
-_STEP_ARENA = os.environ.get("NPCD_STEP_ARENA", "1") != "0"
-_STEP_ARENA_MAX_T = int(os.environ.get("NPCD_STEP_ARENA_MAX_T", "20000"))
 
 
 # Round 18: from _WGRAD_MULTIBLOCK_MIN_T token rows on -- where the side stream above is off and a product alone is 16-64 tiles for 256
@@ -223,17 +247,6 @@ _STEP_ARENA_MAX_T = int(os.environ.get("NPCD_STEP_ARENA_MAX_T", "20000"))
 # the L mod G blocks at the bottom keep the per-product calls.  The operands of up to G - 1 earlier blocks stay alive until their
 # launch (~1.07 GB per block at T = 32,832, width 1,024).  NPCD_WGRAD_MULTIBLOCK=0: off, =force: G = 4 whatever the fill rule says
 # (tests at small widths); NPCD_WGRAD_MULTIBLOCK_MIN_T: the threshold.  docs/experiments.md R18.1.
-def _parse_wgrad_multiblock(value):
-    """NPCD_WGRAD_MULTIBLOCK -> "on" (unset, "", "1"), "off" ("0") or "force"; anything else raises a ValueError that names the
-    variable.  Parsed once, here."""
-    modes = {None: "on", "": "on", "1": "on", "0": "off", "force": "force"}
-    if value not in modes:
-        raise ValueError(f"NPCD_WGRAD_MULTIBLOCK={value!r}: expected unset, 0 (off), 1 (on) or force (skip the fill rule)")
-    return modes[value]
-
-
-_WGRAD_MULTIBLOCK = _parse_wgrad_multiblock(os.environ.get("NPCD_WGRAD_MULTIBLOCK"))
-_WGRAD_MULTIBLOCK_MIN_T = int(os.environ.get("NPCD_WGRAD_MULTIBLOCK_MIN_T", "20000"))
 _multiblock_blocks = {}
 
 
@@ -252,38 +265,85 @@ def _wgrad_multiblock_blocks(T, W, dtype, device):
     return _multiblock_blocks[key]
 
 
-def _wgrad_fork(pending, device, before=None):
-    """The weight-gradient products of ONE block -- (dy, x, out) triples -- on the side stream, behind everything the current stream has
-    been given so far: one fork per block (per product it cost the host ~40 us of stream bookkeeping, 3.8 ms of a rank's step at
-    per-GPU batch 8, which is host-bound: tools/probes/gpu_dev_b8_hostprofile.py).  `before()`: called on the side stream ahead of the
-    products (the hand-over of the block above to the reducer).  The grouped launch (ew.wgrad_group) runs only here: with the side
-    stream off the same products are the per-product library calls of _wgrad, a different fp32 summation order."""
-    side = _side_stream(device)
-    with torch.cuda.stream(side):
-        if before is not None:
-            before()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for dy, x, out in pending:
-            dy.record_stream(side)
-            x.record_stream(side)
-        if not (_WGRAD_GROUP and pending and pending[0][0].shape[0] <= _WGRAD_GROUP_MAX_T and ew.wgrad_group(pending)):
-            for dy, x, out in pending:
-                _wgrad(dy, x, out)
-    pending.clear()
+def _mark_ready(eng, entry):
+    """A block's gradients are final: its parameters, in _BLOCK_PARAMS order, go to the engine's reducer, if one is reducing."""
+    if eng.reducer is not None and eng.reducer.active:
+        for p in entry["params"]:
+            eng.reducer.mark_ready(p)
 
 
-def _wgrad_join(device):
-    torch.cuda.current_stream().wait_stream(_side_stream(device))
+# The three ways the weight gradients of a backward are issued:
+#   side stream: a block's four products are queued and start on the side stream in block_done -- one fork per block (per product it
+#     cost the host ~40 us of stream bookkeeping, 3.8 ms of a rank's step at per-GPU batch 8, which is host-bound:
+#     tools/probes/gpu_dev_b8_hostprofile.py), as one grouped launch where that is on and takes them.  The block ABOVE is handed to the
+#     reducer on the side stream ahead of them: behind its own weight gradients and, through the wait of the fork that started them,
+#     behind its critical path; the main stream waits once, in finish().  (_JOIN_PER_BLOCK, the round-5 order: the main stream joins
+#     per block -- the block above had this block's critical path to finish its weight gradients beside -- and hands it on itself.)
+#     The grouped launch of ONE block runs only here: with the side stream off the same products are the per-product library calls
+#     of _wgrad, a different fp32 summation order.
+#   multi-block (group = G > 0): the products of blocks [L mod G, L) are queued and launched in runs of G blocks, counting down from
+#     the last, on the main stream -- 4 x G products, one launch; the L mod G blocks at the bottom are direct.
+#   direct: _wgrad at once.
+class _WgradSchedule:
+    """Where and when the weight gradients of ONE 16-bit backward are issued: add(dy, x, out) per product of the current block,
+    block_done(bi) when the block's critical path has been enqueued, finish() after block 0.  In every mode a block goes to the
+    reducer only behind the launch that wrote its weight gradients, and in descending block order."""
+
+    def __init__(self, eng, T, W, dtype, device, side=None, group=None):
+        # (`side`, `group`: given by tests without a GPU)
+        self.eng, self.blocks, self.T = eng, eng.blocks, T
+        self.side = _wgrad_side_ok(T) if side is None else side
+        self.stream = _side_stream(device) if self.side else None
+        self.group = group if group is not None else 0 if self.side else _wgrad_multiblock_blocks(T, W, dtype, device)
+        self.tail = len(self.blocks) % self.group if self.group else len(self.blocks)
+        self.bi = len(self.blocks) - 1             # the block whose products add() is being given
+        # the (dy, x, out) triples not yet launched -- what keeps their operands alive, cleared at the launch; main stream: the
+        # blocks not yet handed to the reducer
+        self.queue, self.waiting = [], []
+
+    def add(self, dy, x, out):
+        if self.side or self.bi >= self.tail:
+            self.queue.append((dy, x, out))
+        else:
+            _wgrad(dy, x, out)
+
+    def _launch(self, grouped):
+        if not (grouped and ew.wgrad_group(self.queue)):
+            for t in self.queue:
+                _wgrad(*t)
+        self.queue.clear()
+
+    def block_done(self, bi):
+        L, side, self.bi = len(self.blocks), self.stream, bi - 1
+        if not self.side:
+            self.waiting.append(bi)
+            if bi < self.tail or (L - bi) % self.group == 0:       # a direct block, or the last of a run of `group` blocks
+                if self.queue:
+                    self._launch(True)
+                for b in self.waiting:             # (mlp.c_proj.bias of the lowest one was finished by the block above it / the tail)
+                    _mark_ready(self.eng, self.blocks[b])
+                self.waiting.clear()
+            return
+        if bi + 1 < L:                             # the block above: behind its weight gradients
+            if _JOIN_PER_BLOCK:
+                torch.cuda.current_stream().wait_stream(side)
+            with (_NULL if _JOIN_PER_BLOCK else torch.cuda.stream(side)):
+                _mark_ready(self.eng, self.blocks[bi + 1])
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for dy, x, out in self.queue:
+                dy.record_stream(side)
+                x.record_stream(side)
+            self._launch(_WGRAD_GROUP and self.T <= _WGRAD_GROUP_MAX_T)
+
+    def finish(self):
+        if self.side:
+            torch.cuda.current_stream().wait_stream(self.stream)
+            _mark_ready(self.eng, self.blocks[0])
 
 
 def _no_engine():
     return None
-
-
-import contextlib
-
-_NULL = contextlib.nullcontext()
 
 
 class _BlockViews:
@@ -355,8 +415,10 @@ class FusedBackboneEngine(_BlockViews):
         self._shadowT, self._wT = None, None
         self._wT_stamp = [None] * len(self.blocks)
         self.transposed_refreshes = 0                        # launches of the grouped transpose, one per block and refresh
-        # the buffers of a step, reused by the next one (npcd.hip.arena) -- for the token counts of a rank of the strong-scaling job,
-        # where the host side of a step is as long as its GPU side; NPCD_STEP_ARENA=0 switches it off
+        # Round 6: below _STEP_ARENA_MAX_T token rows -- the token counts of a rank of the strong-scaling job, where the host side of a
+        # step is as long as its GPU side -- the ~740 buffers a step of the fused node allocates are kept and handed out again in the
+        # same order by the next step (npcd/hip/arena.py): 1.6 ms of host time per step at per-GPU batch 8.  The memory of a step then
+        # stays allocated between steps (at 4,104 rows ~8 GB; the caching allocator would keep most of it anyway).  NPCD_STEP_ARENA=0: off.
         self.arena = harena.StepArena() if _STEP_ARENA else None
 
     def shadow_written(self):
@@ -411,9 +473,9 @@ class FusedBackboneEngine(_BlockViews):
         return _BackboneFn.apply(x, self)
 
 
-class InferenceWeights:
-    """bf16 copies of the block weights for the forward-only path of a backbone that is not attached to a trainer
-    (sampling from a loaded checkpoint).  Rebuilt when a parameter was written to or replaced since the copy was taken."""
+class _BlockWeights:
+    """Per-block copies of the weights for the forward-only path of a backbone that is not attached to a trainer (sampling from a loaded
+    checkpoint): rebuilt when a parameter was written to or replaced since the copy was taken.  A subclass converts one parameter."""
 
     def __init__(self, backbone):
         self.heads = backbone.resblocks[0].attn.heads
@@ -427,43 +489,33 @@ class InferenceWeights:
             for ps in self.params:
                 e = {}
                 for n, p in zip(_BLOCK_PARAMS, ps):
-                    key = n.replace(".", "_")
-                    e[key] = p.data
-                    if not n.startswith("ln_"):
-                        e[key + "_16"] = p.data.to(_bf16)
+                    self.convert(e, n, n.replace(".", "_"), p.data)
                 self.blocks.append(e)
             self.stamp = stamp
         return self.blocks
 
 
-class InferenceWeightsX2:
-    """The block weights of a backbone in the split-operand form of the fp32-class forward (csrc/split.hip): per Linear layer
-    [Wh | Wh | Wl] bf16 [N, 3 K] with W = Wh + Wl, the biases and LayerNorm parameters in fp32.  Rebuilt when a parameter was written
-    to or replaced since the copy was taken."""
+class InferenceWeights(_BlockWeights):
+    """The parameters as they are (LayerNorm affines are used in fp32) and bf16 copies of the Linear weights and biases."""
 
-    def __init__(self, backbone):
-        self.heads = backbone.resblocks[0].attn.heads
-        self.params = [[dict(blk.named_parameters())[n] for n in _BLOCK_PARAMS] for blk in backbone.resblocks]
-        self.stamp, self.blocks = None, None
+    def convert(self, e, n, key, data):
+        e[key] = data
+        if not n.startswith("ln_"):
+            e[key + "_16"] = data.to(_bf16)
 
-    def current(self):
-        stamp = [(p._version, p.data_ptr()) for ps in self.params for p in ps]
-        if stamp != self.stamp:
-            self.blocks = []
-            for ps in self.params:
-                e = {}
-                for n, p in zip(_BLOCK_PARAMS, ps):
-                    key = n.replace(".", "_")
-                    w = p.data.to(_f32)
-                    if n.endswith("weight") and not n.startswith("ln_"):
-                        hi = w.to(_bf16)
-                        lo = (w - hi.float()).to(_bf16)
-                        e[key + "_x3"] = torch.cat((hi, hi, lo), dim=1).contiguous()
-                    else:
-                        e[key] = w.contiguous()
-                self.blocks.append(e)
-            self.stamp = stamp
-        return self.blocks
+
+class InferenceWeightsX2(_BlockWeights):
+    """The split-operand form of the fp32-class forward (csrc/split.hip): per Linear layer [Wh | Wh | Wl] bf16 [N, 3 K] with
+    W = Wh + Wl, the biases and LayerNorm parameters in fp32."""
+
+    def convert(self, e, n, key, data):
+        w = data.to(_f32)
+        if n.endswith("weight") and not n.startswith("ln_"):
+            hi = w.to(_bf16)
+            lo = (w - hi.float()).to(_bf16)
+            e[key + "_x3"] = torch.cat((hi, hi, lo), dim=1).contiguous()
+        else:
+            e[key] = w.contiguous()
 
 
 def backbone_forward_x2(x, blocks, heads):
@@ -521,6 +573,31 @@ def backbone_forward(x, blocks, heads, dtype=_bf16):
             delta = _linear(e["mlp_c_proj_bias_16"], g, e["mlp_c_proj_weight_16"])
         out = xs + delta
     return out.view(B, n, W)
+
+
+# opt-in (NPCD_OWN_DGELU=1): the data gradient of mlp.c_proj as the own NT product with the GELU backward and the c_fc bias-gradient
+# column sums in its epilogue (csrc/gemm_nt.hip, docs/experiments.md R4.1) on the full 256-row tiles of the token range; the remainder
+# rows keep the library product + the separate kernel.  Reads the engine's transposed shadow of the weight, brought up to date by this
+# step's forward.  The own launch only for what npcd_linear_dgelu_bwd takes -- contiguous 16-bit operands of one type; anything else
+# goes through the caller's library product + gelu_bwd instead of raising, like NPCD_ERR_UNSUPPORTED would.
+def _own_dgelu(e, dxb, h, dgrad_t, sums):
+    """dh = gelu'(h) * (dxb @ mlp.c_proj.weight) of block entry `e`, its column sums added to `sums`; None: declined."""
+    T, W = dxb.shape
+    Tm = T - T % 256
+    w2 = e["mlp_c_proj_weight_16"]
+    if not (Tm > 0 and hlin.supported(Tm, 4 * W, W) and dxb.is_contiguous() and h.is_contiguous() and w2.is_contiguous()
+            and dxb.dtype == w2.dtype == h.dtype and dxb.dtype in (torch.bfloat16, torch.float16)):
+        return None
+    wT = e["mlp_c_proj_weight_16T"]
+    dh = harena.empty_like(h)
+    extra = ew.lib().npcd_colsum_blocks(T - Tm) if Tm < T else 0
+    _, part, rows = hlin.linear_dgelu_bwd(dxb[:Tm], wT, h[:Tm], out=dh[:Tm], extra_part_rows=extra)
+    if Tm < T:       # remainder rows: library product + the separate kernel, partial rows behind the own kernel's
+        dg = torch.mm(dxb[Tm:], wT.t() if dgrad_t else w2)
+        ew.gelu_bwd(dg, h[Tm:], None, out=dh[Tm:], part_rows=part[rows:])
+        del dg
+    sums.add(part, rows + extra, 4 * W, e["mlp_c_fc_bias_g"])
+    return dh
 
 
 class _BackboneFn(torch.autograd.Function):
@@ -600,61 +677,32 @@ class _BackboneFn(torch.autograd.Function):
             dxb = dx.to(eng.dtype)
             last = eng.blocks[-1]
             last["mlp_c_proj_bias_g"].copy_(dx.sum(dim=0))
-            side, pending = _wgrad_side_ok(T), []
             # (the forward of this step brought the transposed shadow up to date, or did not: decided there, once)
             dgrad_t = ctx.transposed and not _DGRAD_NN and T >= _DGRAD_T_MIN_T
-
-            reducing = eng.reducer is not None and eng.reducer.active
-
-            def ready(entry):
-                if reducing:
-                    for p in entry["params"]:
-                        eng.reducer.mark_ready(p)
-            # the weight gradients of `group` blocks in one launch on the main stream (round 18): blocks [tail, L) in runs of `group`,
-            # counting down from the last; the `tail` blocks at the bottom keep the per-product calls
-            group = 0 if side else _wgrad_multiblock_blocks(T, W, eng.dtype, dx.device)
-            tail = len(eng.blocks) % group if group else len(eng.blocks)
-            queued, queued_blocks = [], []
+            wg = _WgradSchedule(eng, T, W, eng.dtype, dx.device)
             for bi in range(len(eng.blocks) - 1, -1, -1):
                 e = eng.blocks[bi]
                 x_cur, mean1, rstd1, y1, qkv, a, lse, x2, mean2, rstd2, y2, h, g = ctx.saved[bi]
                 ctx.saved[bi] = None
                 sums = ew.ColsumBatch()            # this block's 8 bias / LN-affine column sums: one finalize
-                # weight gradients: now, or queued for the side stream, or queued for the multi-block launch
-                wg = pending.append if side else queued.append if bi >= tail else (lambda t: _wgrad(*t))
                 # ---- MLP branch: x3 = x2 + c_proj(gelu(c_fc(ln_2(x2)))) ------------------------------
-                Tm = T - T % 256
-                w2 = e["mlp_c_proj_weight_16"]
-                # (the own launch only for what npcd_linear_dgelu_bwd takes -- contiguous 16-bit operands of one type; anything else
-                # goes through the library product + gelu_bwd below instead of raising, like NPCD_ERR_UNSUPPORTED would, ADVICE r4.
-                # The transposed weight is the engine's transposed shadow, brought up to date by this step's forward.)
-                if (_OWN_DGELU and ctx.transposed and Tm > 0 and hlin.supported(Tm, 4 * W, W) and dxb.is_contiguous() and h.is_contiguous()
-                        and w2.is_contiguous() and dxb.dtype == w2.dtype == h.dtype and dxb.dtype in (torch.bfloat16, torch.float16)):
-                    wT = e["mlp_c_proj_weight_16T"]
-                    dh = harena.empty_like(h)
-                    extra = ew.lib().npcd_colsum_blocks(T - Tm) if Tm < T else 0
-                    _, part, rows = hlin.linear_dgelu_bwd(dxb[:Tm], wT, h[:Tm], out=dh[:Tm], extra_part_rows=extra)
-                    if Tm < T:       # remainder rows: library product + the separate kernel, partial rows behind the own kernel's
-                        dg = torch.mm(dxb[Tm:], wT.t() if dgrad_t else w2)
-                        ew.gelu_bwd(dg, h[Tm:], None, out=dh[Tm:], part_rows=part[rows:])
-                        del dg
-                    sums.add(part, rows + extra, 4 * W, e["mlp_c_fc_bias_g"])
-                    wg((dxb, g, e["mlp_c_proj_weight_g"]))
-                    del g, h
-                else:
-                    dg = _dgrad(dxb, w2, e["mlp_c_proj_weight_16T"] if dgrad_t else None)
-                    wg((dxb, g, e["mlp_c_proj_weight_g"]))
+                # (dh from the own launch where it is on and takes the shapes, else from the library product + gelu_bwd; the weight
+                # gradient is issued right behind the data-gradient product either way)
+                dh = _own_dgelu(e, dxb, h, dgrad_t, sums) if (_OWN_DGELU and ctx.transposed) else None
+                dg = _dgrad(dxb, e["mlp_c_proj_weight_16"], e["mlp_c_proj_weight_16T"] if dgrad_t else None) if dh is None else None
+                wg.add(dxb, g, e["mlp_c_proj_weight_g"])
+                if dh is None:
                     dh = ew.gelu_bwd(dg, h, e["mlp_c_fc_bias_g"], batch=sums)
-                    del dg, g, h
+                del dg, g, h
                 dy2 = _dgrad(dh, e["mlp_c_fc_weight_16"], e["mlp_c_fc_weight_16T"] if dgrad_t else None)
-                wg((dh, y2, e["mlp_c_fc_weight_g"]))
+                wg.add(dh, y2, e["mlp_c_fc_weight_g"])
                 del dh, y2
                 dx2, dx2b = ew.ln_bwd(dy2, x2, mean2, rstd2, e["ln_2_weight"], dx, e["ln_2_weight_g"], e["ln_2_bias_g"],
                                       e["attn_c_proj_bias_g"], batch=sums)
                 del dy2, x2, dx, dxb
                 # ---- attention branch: x2 = x + c_proj(attn(c_qkv(ln_1(x)))) ---------------------------
                 da = _dgrad(dx2b, e["attn_c_proj_weight_16"], e["attn_c_proj_weight_16T"] if dgrad_t else None)
-                wg((dx2b, a, e["attn_c_proj_weight_g"]))
+                wg.add(dx2b, a, e["attn_c_proj_weight_g"])
                 dqkv = harena.empty_like(qkv)
                 q4, g4 = qkv.view(B, n, H, 3 * d), dqkv.view(B, n, H, 3 * d)
                 # the c_qkv bias gradient (column sums of dqkv) is a by-product of the attention backward's row stores
@@ -667,7 +715,7 @@ class _BackboneFn(torch.autograd.Function):
                 else:
                     ew.colsum_bf16(dqkv, e["attn_c_qkv_bias_g"], batch=sums)
                 dy1 = _dgrad(dqkv, e["attn_c_qkv_weight_16"], e["attn_c_qkv_weight_16T"] if dgrad_t else None)
-                wg((dqkv, y1, e["attn_c_qkv_weight_g"]))
+                wg.add(dqkv, y1, e["attn_c_qkv_weight_g"])
                 del dqkv, y1
                 prev_bias_g = eng.blocks[bi - 1]["mlp_c_proj_bias_g"] if bi > 0 else None
                 # (the last block's dx is what the node returns: allocated outside the arena, like everything that outlives the step)
@@ -676,35 +724,8 @@ class _BackboneFn(torch.autograd.Function):
                                         prev_bias_g, want_bf16=bi > 0, batch=sums)
                 del dy1, dx2
                 sums.flush()
-                if side and _JOIN_PER_BLOCK:
-                    # (the round-5 order, A/B) the block ABOVE had this block's critical path to finish its weight gradients beside: join
-                    # them, hand its gradients on, then start this block's four products on the side stream
-                    if bi + 1 < len(eng.blocks):
-                        _wgrad_join(dx.device)
-                        ready(eng.blocks[bi + 1])
-                    _wgrad_fork(pending, dx.device)
-                elif side:
-                    # the block ABOVE is handed to the reducer ON the side stream, behind its own weight gradients (and, through the
-                    # wait of the fork that started them, behind its critical path): the main stream does not wait; then this block's
-                    # four products start there
-                    above = eng.blocks[bi + 1] if (reducing and bi + 1 < len(eng.blocks)) else None
-                    _wgrad_fork(pending, dx.device, before=None if above is None else (lambda: ready(above)))
-                elif bi >= tail:
-                    queued_blocks.append(e)
-                    if (len(eng.blocks) - bi) % group == 0:
-                        # 4 x group products, one launch; the blocks are handed on only behind it, in descending order
-                        if not ew.wgrad_group(queued):
-                            for t in queued:
-                                _wgrad(*t)
-                        queued.clear()
-                        for qe in queued_blocks:
-                            ready(qe)
-                        queued_blocks.clear()
-                else:
-                    ready(e)       # this block's gradients are final (mlp.c_proj.bias was finished by the block above / the tail)
-            if side:
-                _wgrad_join(dx.device)
-                ready(eng.blocks[0])
+                wg.block_done(bi)
+            wg.finish()
         return dx.view(B, n, W), None
 
 
@@ -716,7 +737,6 @@ class _BackboneFn(torch.autograd.Function):
 # block by block, right behind the wait for that block's parameters: nothing is cached between steps, so a lazily gathered parameter,
 # load_state_dict or an EMA copy-in can never leave a stale operand behind.
 SPLIT_WIDTHS = (256, 512, 768, 1024, 2048)          # add_ln_split3 (W / 256 in 1, 2, 3, 4, 8, 16) and the LayerNorm backward (W <= 2048)
-_X2_LINEARS = ("attn_c_qkv", "attn_c_proj", "mlp_c_fc", "mlp_c_proj")
 
 
 def x2_supported(width, heads):
@@ -750,11 +770,6 @@ def _wgrad_x2(dy3, x3, out):
 # The form of the weight gradients (A/B switch, NPCD_X2_WGRAD): "library" = _wgrad_x2 above; "own" = the own kernels of csrc/gemm.hip on
 # the operands stacked along the token dimension -- dy [dyh ; dyl ; dyh] and x [xl ; xh ; xh], [3 T, N] / [3 T, K], one reduction over
 # 3 T rows (the four products of a block in one npcd_wgrad_group launch up to _WGRAD_GROUP_MAX_T rows, else npcd_wgrad per product).
-_X2_WGRAD = os.environ.get("NPCD_X2_WGRAD", "library")
-if _X2_WGRAD not in ("library", "own"):
-    raise ValueError(f"NPCD_X2_WGRAD={_X2_WGRAD!r}: expected library or own")
-
-
 def _stack_x2(a3, lo_first):
     """[T, 3 N] = [hi | lo | hi] -> [3 T, N] bf16 stacked along the tokens: [hi ; lo ; hi], or (lo_first) [lo ; hi ; hi]."""
     T, N = a3.shape[0], a3.shape[1] // 3
@@ -809,7 +824,7 @@ class _BackboneX2Fn(torch.autograd.Function):
             for bi, e in enumerate(eng.blocks):
                 if eng.wait_range is not None:
                     eng.wait_range(*eng.block_ranges[bi])        # this block's parameters (gathered lazily by the sharded optimizer)
-                split = dict(zip(_X2_LINEARS, ew.split_weights([e[k + "_weight"] for k in _X2_LINEARS])))
+                split = dict(zip(_LINEARS, ew.split_weights([e[k + "_weight"] for k in _LINEARS])))
                 x_cur, y1, mean1, rstd1 = ew.add_ln_split3_stats(xs, e["ln_1_weight"], e["ln_1_bias"], o, ob)
                 qkv = _mm_x2(y1, split["attn_c_qkv"][0].t()).add_(e["attn_c_qkv_bias"])
                 q4 = qkv.view(B, n, H, 3 * d)
@@ -838,7 +853,6 @@ class _BackboneX2Fn(torch.autograd.Function):
             dx = dout.reshape(T, W).contiguous().float()
             eng.blocks[-1]["mlp_c_proj_bias_g"].copy_(dx.sum(dim=0))
             dx3 = ew.split3(dx)
-            reducing = eng.reducer is not None and eng.reducer.active
             for bi in range(len(eng.blocks) - 1, -1, -1):
                 e = eng.blocks[bi]
                 x_cur, mean1, rstd1, y1, qkv, a, lse, x2, mean2, rstd2, y2, h, wd = ctx.saved[bi]
@@ -878,7 +892,5 @@ class _BackboneX2Fn(torch.autograd.Function):
                 if pending:
                     _wgrad_own(pending)
                 sums.flush()
-                if reducing:
-                    for p in e["params"]:          # this block's gradients are final (mlp.c_proj.bias: by the block above / the tail)
-                        eng.reducer.mark_ready(p)
+                _mark_ready(eng, e)                # this block's gradients are final (mlp.c_proj.bias: by the block above / the tail)
         return dx.view(B, n, W), None

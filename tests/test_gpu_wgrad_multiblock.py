@@ -1,6 +1,6 @@
 """The multi-block weight-gradient launch (round 18): npcd_wgrad_group with up to 16 products -- the four Linear layers of four residual
 blocks in one launch, a workgroup per 256 x 256 tile over all token rows -- and the engine path that queues the (dy, x, out) triples of
-G blocks for it (fused._BackboneFn._backward, NPCD_WGRAD_MULTIBLOCK).
+G blocks for it (fused._WgradSchedule, NPCD_WGRAD_MULTIBLOCK).
 
 Kernel level: 9 and 16 products (past the old limit of 8) with mixed N, K in {256, 512} over ragged token ranges (T = 33 is shorter than
 the LDS ring's three-stage prologue; none is a multiple of 8, so the zero page of dma_subtile serves rows) against the single-product
@@ -199,6 +199,48 @@ def test_engine_hands_blocks_to_the_reducer_behind_their_launch(multiblock, monk
     ready = [(i, ev[1]) for i, ev in enumerate(events) if ev[0] == "ready"]
     assert sorted({b for _, b in ready}) == list(range(L))
     assert all(i > launches[0] for i, b in ready if b >= 2), events
+    order = [b for _, b in ready]
+    assert order == sorted(order, reverse=True), order
+    tr.close()
+
+
+@pytest.mark.parametrize("join_per_block", [False, True], ids=["handover", "join"])
+def test_side_stream_hands_blocks_to_the_reducer_behind_their_launch(monkeypatch, join_per_block):
+    """The side stream (the module's default at this size), with the hand-over from the side stream and with the per-block join: one
+    grouped call per block, from the last block down, each with that block's four outputs; block b >= 1 is handed to the reducer
+    behind its own call and ahead of the call of block b - 1, block 0 last of all, in descending order."""
+    from npcd.hip import elementwise as ew
+    from npcd.models.diffusion import fused
+    assert fused._wgrad_side_ok(T) and fused._WGRAD_GROUP and T <= fused._WGRAD_GROUP_MAX_T
+    monkeypatch.setattr(fused, "_JOIN_PER_BLOCK", join_per_block)
+    tr = _trainer(torch.bfloat16)
+    eng = tr.model.denoiser.backbone.fused_engine
+    block_of = {id(p): bi for bi, e in enumerate(eng.blocks) for p in e["params"]}
+    outs_of = [sorted(e[k + "_weight_g"].data_ptr() for k in ("attn_c_qkv", "attn_c_proj", "mlp_c_fc", "mlp_c_proj")) for e in eng.blocks]
+    events = []
+
+    class Recorder:
+        active = True
+
+        def mark_ready(self, p):
+            events.append(("ready", block_of[id(p)]))
+    real = ew.wgrad_group
+
+    def recorded(triples):
+        events.append(("group", outs_of.index(sorted(t[2].data_ptr() for t in triples))))
+        return real(triples)
+    monkeypatch.setattr(ew, "wgrad_group", recorded)
+    monkeypatch.setattr(eng, "reducer", Recorder())
+    _backward(tr, torch.bfloat16)
+    launch = {ev[1]: i for i, ev in enumerate(events) if ev[0] == "group"}
+    assert [ev[1] for ev in events if ev[0] == "group"] == [5, 4, 3, 2, 1, 0], events
+    ready = [(i, ev[1]) for i, ev in enumerate(events) if ev[0] == "ready"]
+    assert sorted({b for _, b in ready}) == list(range(L)) and len(ready) == 12 * L
+    for i, b in ready:
+        assert i > launch[b], (b, events)
+        if b >= 1:
+            assert i < launch[b - 1], (b, events)
+    assert all(ev == ("ready", 0) for ev in events[launch[0] + 1:]) and len(events) == launch[0] + 1 + 12
     order = [b for _, b in ready]
     assert order == sorted(order, reverse=True), order
     tr.close()

@@ -295,30 +295,67 @@ def test_weight_gradient_stream_switch_is_parsed_once():
     assert fused._parse_wgrad_stream("12345") == (True, 12345)
 
 
-def _fused_switches_in_a_child(env_vars):
+_FUSED_SWITCHES_SHOWN = ("_JOIN_PER_BLOCK", "_OWN_WGRAD", "_OWN_DGELU", "_WGRAD_STREAM", "_WGRAD_STREAM_MAX_T")
+_FUSED_DEFAULT_ON_SHOWN = ("_SPLIT", "_SPLIT_BIG_FIRST", "_ATTN_COLSUM", "_SUM_KERNEL", "_LIN128")
+
+
+def _fused_switches_in_a_child(env_vars, shown=_FUSED_SWITCHES_SHOWN):
     """Import npcd.models.diffusion.fused in a fresh interpreter with `env_vars` set (the switches are read at import): its
-    (returncode, stdout, stderr)."""
+    (returncode, stdout with the globals `shown`, stderr)."""
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if not k.startswith("NPCD_")}
     env.update(env_vars)
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "neural-point-cloud-diffusion_amd"), ROOT])
     code = ("from npcd.models.diffusion import fused as f; "
-            "print(f._JOIN_PER_BLOCK, f._OWN_WGRAD, f._OWN_DGELU, f._WGRAD_STREAM, f._WGRAD_STREAM_MAX_T)")
+            f"print({', '.join('f.' + n for n in shown)})")
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
     return out.returncode, out.stdout.strip(), out.stderr
 
 
-@pytest.mark.parametrize("name,index", [("NPCD_WGRAD_JOIN_PER_BLOCK", 0), ("NPCD_OWN_WGRAD", 1), ("NPCD_OWN_DGELU", 2)])
+@pytest.mark.parametrize("name,index", [("NPCD_WGRAD_JOIN_PER_BLOCK", 0), ("NPCD_OWN_WGRAD", 1), ("NPCD_OWN_DGELU", 2),
+                                        ("NPCD_NO_GEMM_SPLIT", 5), ("NPCD_GEMM_SPLIT_SMALL_FIRST", 6), ("NPCD_NO_ATTN_COLSUM", 7),
+                                        ("NPCD_NO_SUM_KERNEL", 8), ("NPCD_NO_LIN128", 9)])
 def test_fused_env_switches_read_zero_as_off(name, index):
     """The A/B switches of the fused backbone: unset, "" and "0" are off, "1" (or any other value) is on -- NPCD_..._=0 had
-    switched the opt-in path ON (bool("0") is True)."""
+    switched the opt-in path ON (bool("0") is True).  The last five switch a default path OFF: the global they set (the 256-row
+    split, a True) keeps its default while they are off."""
+    off, on = ("False", "True") if index < 5 else ("256", "0") if index == 5 else ("True", "False")
     seen = {}
     for value in (None, "", "0", "1", "yes"):
-        rc, out, err = _fused_switches_in_a_child({} if value is None else {name: value})
+        rc, out, err = _fused_switches_in_a_child({} if value is None else {name: value}, _FUSED_SWITCHES_SHOWN + _FUSED_DEFAULT_ON_SHOWN)
         assert rc == 0, err
         seen[value] = out.split()[index]
-    assert seen == {None: "False", "": "False", "0": "False", "1": "True", "yes": "True"}, seen
+    assert seen == {None: off, "": off, "0": off, "1": on, "yes": on}, seen
+
+
+_FUSED_INTEGER_SWITCHES = ("NPCD_GEMM_SPLIT_MIN", "NPCD_GEMM_SPLIT_WIDE_N", "NPCD_LIN128_MAX_T", "NPCD_DGRAD_T_MIN_T",
+                           "NPCD_WGRAD_STREAM_PRIO", "NPCD_WGRAD_GROUP_MAX_T", "NPCD_WGRAD_MULTIBLOCK_MIN_T", "NPCD_STEP_ARENA_MAX_T")
+
+
+@pytest.mark.parametrize("name", _FUSED_INTEGER_SWITCHES)
+def test_fused_integer_switches_reject_a_word_by_name(name):
+    """An integer switch that holds no integer stops the import with a ValueError that names the variable and the value (it had
+    been a bare int() ValueError)."""
+    rc, _, err = _fused_switches_in_a_child({name: "abc"})
+    assert rc != 0 and "ValueError" in err and f"{name}='abc'" in err, err
+
+
+def test_fused_switches_are_read_in_one_block_and_listed_in_the_readme():
+    """Every NPCD_ variable npcd/models/diffusion/fused.py reads is read in the switch block at its top, and README.md lists it."""
+    import re
+    with open(os.path.join(ROOT, "neural-point-cloud-diffusion_amd", "npcd", "models", "diffusion", "fused.py")) as f:
+        src = f.read()
+    head, begin, rest = src.partition("# ---- the switches")
+    block, end, tail = rest.partition("# ---- end of the switches")
+    assert begin and end
+    assert "os.environ" not in head and "os.environ" not in tail, "an environment read outside the switch block"
+    names = set(re.findall(r'"(NPCD_[A-Z0-9_]+)"', block))
+    assert set(_FUSED_INTEGER_SWITCHES) < names and len(names) == 22, sorted(names)
+    with open(os.path.join(ROOT, "README.md")) as f:
+        readme = f.read()
+    missing = sorted(n for n in names if not re.search(r"\b" + n + r"\b", readme))
+    assert not missing, missing
 
 
 def test_wgrad_stream_switch_rejects_a_word_by_name():
