@@ -35,6 +35,7 @@ SOURCES = {
     # activation fragments (matrix-instruction operands only) in AGPRs
     "shade_rows.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
     "elementwise.hip": [],
+    "sampler.hip": [],
     "gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
     "gemm_nt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
     "pairs.hip": ["-ffp-contract=off"],

@@ -71,6 +71,21 @@ struct F16 {
     }
 };
 
+// ---- streaming kernels: four elements of an activation / eps type E as fp32 and back -----------
+// E: __bf16 (bf16 autocast), _Float16 (the reference's default --dtype, with loss scaling) or float
+template <class E>
+struct V {
+    typedef E x4 __attribute__((ext_vector_type(4)));
+    typedef E x8 __attribute__((ext_vector_type(8)));
+};
+template <class X4>
+__device__ __forceinline__ f32x4 to_f32(X4 v) { return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
+template <class E>
+__device__ __forceinline__ typename V<E>::x4 from_f32(f32x4 v) { return typename V<E>::x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]}; }
+
+// host: may a 16-byte access start at p?
+static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // Row r of a 32x32 MFMA accumulator register i on lane-half hh:  (i&3) + 8*(i>>2) + 4*hh
 __device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
 

@@ -10,10 +10,8 @@
 //   column sum of a bf16 matrix (bias gradient of c_qkv)          -> colsum
 //   AdamW + EMA + bf16 weight shadow + gradient zeroing           -> adamw_ema (1 pass over 310 M params)
 //   GradScaler + clip_grad_norm_ bookkeeping on the device        -> grad_stats, scaler_finalize, adamw_ema_gated
-// and of the sampler (gaussian_diffusion.py:100-146): the DDPM reverse step per tensor -> ddpm_reverse; a step of the scheduled sampler
-// (strided DDIM levels, eta, one tensor held), both tensors in one launch          -> sampler_step; the same step with a per-point
-// mask that keeps some points of a tensor (completion, local edits)               -> sampler_step_keep; the deterministic step in
-// second order, with the previous step's data prediction as history (DPM-Solver++ 2M) -> sampler_step_multistep
+//   forward process + eps-MSE loss of the DDPM                    -> q_sample, eps_mse_fwd / eps_mse_bwd
+// (the sampler's steps, which are inference, live in sampler.hip)
 // All are pure streaming kernels: 16-byte accesses per lane, fp32 math, no LDS except the cross-wave
 // reduction of column partials.  Roofline: HBM.
 #include <math.h>
@@ -26,16 +24,6 @@ namespace npcd {
 
 constexpr int kMaxChunks = 8;  // a wave covers 256 columns per chunk -> width <= 2048
 
-// the 16-bit activation type of a training run: __bf16 (bf16 autocast) or _Float16 (the reference's default --dtype, with loss scaling)
-template <class E>
-struct V {
-    typedef E x4 __attribute__((ext_vector_type(4)));
-    typedef E x8 __attribute__((ext_vector_type(8)));
-};
-template <class X4>
-__device__ __forceinline__ f32x4 to_f32(X4 v) { return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
-template <class E>
-__device__ __forceinline__ typename V<E>::x4 from_f32(f32x4 v) { return typename V<E>::x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]}; }
 __device__ __forceinline__ f32x4 bf16x4_to_f32(bf16x4 v) { return to_f32(v); }
 __device__ __forceinline__ bf16x4 f32_to_bf16x4(f32x4 v) { return from_f32<__bf16>(v); }
 
@@ -682,330 +670,6 @@ __global__ __launch_bounds__(256) void sum_slices_kernel(const f32x4* __restrict
     }
 }
 
-// DDPM reverse step (gaussian_diffusion.py:100-146 of the reference): x0 = a x_t - b eps (clamped), mean = c1 x0 + c2 x_t,
-// x_{t-1} = mean + [t > 0] exp(logvar / 2) noise; the five per-sample coefficients are looked up from the 1000-entry tables.
-struct DdpmTables {
-    const float *recip, *recipm1, *c1, *c2, *logvar;
-};
-template <class EPS>
-__global__ __launch_bounds__(256) void ddpm_reverse_kernel(const float* __restrict__ x_t, const EPS* __restrict__ eps, const float* __restrict__ noise,
-                                                           float* __restrict__ x_prev, float* __restrict__ x0_out, const int64_t* __restrict__ t,
-                                                           int64_t per_sample, DdpmTables tab, float lo, float hi, int has_clip) {
-    const int b = blockIdx.y;
-    const int64_t ts = t[b];
-    const float a = tab.recip[ts], bb = tab.recipm1[ts], c1 = tab.c1[ts], c2 = tab.c2[ts];
-    const float sd = ts != 0 ? expf(0.5f * tab.logvar[ts]) : 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * 256) {
-        const int64_t j = (int64_t)b * per_sample + i;
-        const float x = x_t[j];
-        float x0 = a * x - bb * (float)eps[j];
-        if (has_clip) x0 = fminf(fmaxf(x0, lo), hi);
-        if (x0_out) x0_out[j] = x0;
-        x_prev[j] = (c1 * x0 + c2 * x) + sd * noise[j];
-    }
-}
-
-// Scheduled sampler step (strided DDIM schedule with eta in [0, 1], and replacement conditioning): ONE launch advances both tensors of
-// a step, blockIdx.z = 0 coords, 1 feats, blockIdx.y = sample.  The seven coefficients of a sample are one 32-byte row of the
-// [T, 8] table, indexed by the timestep itself (GaussianDiffusion.sampling_schedule):
-//   reverse: x0 = clamp(r x - m eps) (the expression of ddpm_reverse_kernel: the same bits), out = (c1 x0 + c2 x) [+ s z]
-//   hold   : out = h1 known + h2 z       (the known tensor, forward-noised to the level the step arrives at)
-// `noise` of a reverse tensor may be null (eta = 0: every s is 0): the term is then skipped and nothing is read.  A timestep outside
-// [0, T) reads no table row and gives NaN outputs.  Tensors whose per_sample is a multiple of 4 and whose pointers are 16-byte
-// aligned (8 bytes for bf16 eps) move 16 bytes per lane; the others one element per lane, on the grid of ddpm_reverse_kernel.
-struct SamplerCoef {
-    float r, m, c1, c2, s, h1, h2;
-};
-struct SamplerArgs {
-    NpcdSamplerTensor tz[2];
-    int vec[2];
-};
-
-// The roundings are written out (fused multiply-adds), so that the 16-byte and the one-element path give the same bits and x0 is what
-// ddpm_reverse_kernel's `a * x - bb * eps` compiles to: fma(a, x, -(bb eps)).  x0: 2 roundings, out: 3 more, hold: 2.
-__device__ __forceinline__ float sampler_x0(const SamplerCoef& k, float x, float e, int has_clip, float lo, float hi) {
-    float x0 = __builtin_fmaf(k.r, x, -(k.m * e));
-    if (has_clip) x0 = fminf(fmaxf(x0, lo), hi);
-    return x0;
-}
-
-template <class EPS, bool VEC>
-__device__ __forceinline__ void sampler_reverse(const NpcdSamplerTensor& a, const SamplerCoef& k, int64_t base) {
-    const float* __restrict__ x_t = a.x_t + base;
-    const EPS* __restrict__ eps = static_cast<const EPS*>(a.eps) + base;
-    const float* __restrict__ noise = a.noise ? a.noise + base : nullptr;
-    float* __restrict__ out = a.out + base;
-    float* __restrict__ x0_out = a.x0_out ? a.x0_out + base : nullptr;
-    if constexpr (VEC) {
-        const int64_t n4 = a.per_sample / 4;
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-            const f32x4 x = reinterpret_cast<const f32x4*>(x_t)[i];
-            const f32x4 e = to_f32(reinterpret_cast<const typename V<EPS>::x4*>(eps)[i]);
-            f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (noise) z = reinterpret_cast<const f32x4*>(noise)[i];
-            f32x4 x0, o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                x0[q] = sampler_x0(k, x[q], e[q], a.has_clip, a.clip_lo, a.clip_hi);
-                o[q] = __builtin_fmaf(k.c1, x0[q], k.c2 * x[q]);
-                if (noise) o[q] = __builtin_fmaf(k.s, z[q], o[q]);
-            }
-            if (x0_out) reinterpret_cast<f32x4*>(x0_out)[i] = x0;
-            reinterpret_cast<f32x4*>(out)[i] = o;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256) {
-            const float x = x_t[i];
-            const float x0 = sampler_x0(k, x, (float)eps[i], a.has_clip, a.clip_lo, a.clip_hi);
-            float o = __builtin_fmaf(k.c1, x0, k.c2 * x);
-            if (noise) o = __builtin_fmaf(k.s, noise[i], o);
-            if (x0_out) x0_out[i] = x0;
-            out[i] = o;
-        }
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void sampler_hold(const NpcdSamplerTensor& a, const SamplerCoef& k, int64_t base) {
-    const float* __restrict__ known = a.known + base;
-    const float* __restrict__ noise = a.noise + base;
-    float* __restrict__ out = a.out + base;
-    if constexpr (VEC) {
-        const int64_t n4 = a.per_sample / 4;
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-            const f32x4 kn = reinterpret_cast<const f32x4*>(known)[i], z = reinterpret_cast<const f32x4*>(noise)[i];
-            f32x4 o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = __builtin_fmaf(k.h1, kn[q], k.h2 * z[q]);
-            reinterpret_cast<f32x4*>(out)[i] = o;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256)
-            out[i] = __builtin_fmaf(k.h1, known[i], k.h2 * noise[i]);
-    }
-}
-
-// the seven coefficients of sample b: its table row, or NaN for a timestep outside [0, T)
-__device__ __forceinline__ SamplerCoef sampler_coef(const int64_t* __restrict__ t, const float* __restrict__ table, int T, int b) {
-    const int64_t ts = t[b];
-    const float nan = __builtin_nanf("");
-    SamplerCoef k{nan, nan, nan, nan, nan, nan, nan};
-    if (ts >= 0 && ts < T) {
-        const f32x4 lo = reinterpret_cast<const f32x4*>(table)[2 * ts], hi = reinterpret_cast<const f32x4*>(table)[2 * ts + 1];
-        k = SamplerCoef{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2]};
-    }
-    return k;
-}
-
-// one tensor by its mode
-__device__ __forceinline__ void sampler_by_mode(const NpcdSamplerTensor& a, int vec, const SamplerCoef& k, int64_t base) {
-    if (a.mode == NPCD_SAMPLER_HOLD) {
-        if (vec) sampler_hold<true>(a, k, base);
-        else sampler_hold<false>(a, k, base);
-    } else if (a.eps_dtype == NPCD_F32) {
-        if (vec) sampler_reverse<float, true>(a, k, base);
-        else sampler_reverse<float, false>(a, k, base);
-    } else {
-        if (vec) sampler_reverse<__bf16, true>(a, k, base);
-        else sampler_reverse<__bf16, false>(a, k, base);
-    }
-}
-
-__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerArgs args, const int64_t* __restrict__ t, const float* __restrict__ table, int T) {
-    const int z = blockIdx.z, b = blockIdx.y;
-    const NpcdSamplerTensor& a = args.tz[z];
-    // (blocks of the wider tensor's grid that lie past this tensor's range fall through their loop)
-    sampler_by_mode(a, args.vec[z], sampler_coef(t, table, T, b), (int64_t)b * a.per_sample);
-}
-
-// Per-point keeping (npcd_sampler_step_keep): tensors are [B, channels, n_points], `keep` is this sample's mask row, one byte per
-// point.  Every element computes both parents with their own expressions and SELECTS: kept points take the hold expression, free
-// points the reverse step (clip and x0 are theirs alone; x0_out of a kept point is `known`).  A select, never a blend: what is
-// loaded for the branch not taken (NaN included) does not reach an output.  `det`: the s z term of free points is skipped, as a
-// reverse tensor without noise skips it.  The 16-byte path reads the four mask bytes of its four points as one dword (n_points % 4
-// == 0 and a 4-byte aligned mask: an item never straddles a channel row); the point index of an item is taken in 32 bits when it fits.
-__device__ __forceinline__ int64_t sampler_col(int64_t i, int64_t n) {
-    return ((uint64_t)(i | n) >> 32) == 0 ? (int64_t)((uint32_t)i % (uint32_t)n) : i % n;
-}
-
-template <class EPS, bool VEC>
-__device__ __forceinline__ void sampler_keep(const NpcdSamplerTensor& a, const uint8_t* __restrict__ keep, int64_t n_points, int det,
-                                             const SamplerCoef& k, int64_t base) {
-    const float* __restrict__ x_t = a.x_t + base;
-    const EPS* __restrict__ eps = static_cast<const EPS*>(a.eps) + base;
-    const float* __restrict__ noise = a.noise + base;
-    const float* __restrict__ known = a.known + base;
-    float* __restrict__ out = a.out + base;
-    float* __restrict__ x0_out = a.x0_out ? a.x0_out + base : nullptr;
-    if constexpr (VEC) {
-        const int64_t n4 = a.per_sample / 4, row4 = n_points / 4;
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-            const uint32_t m = reinterpret_cast<const uint32_t*>(keep)[sampler_col(i, row4)];
-            const f32x4 x = reinterpret_cast<const f32x4*>(x_t)[i];
-            const f32x4 e = to_f32(reinterpret_cast<const typename V<EPS>::x4*>(eps)[i]);
-            const f32x4 z = reinterpret_cast<const f32x4*>(noise)[i], kn = reinterpret_cast<const f32x4*>(known)[i];
-            f32x4 x0, o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float f0 = sampler_x0(k, x[q], e[q], a.has_clip, a.clip_lo, a.clip_hi);
-                float fo = __builtin_fmaf(k.c1, f0, k.c2 * x[q]);
-                if (!det) fo = __builtin_fmaf(k.s, z[q], fo);
-                const bool kept = ((m >> (8 * q)) & 0xffu) != 0;
-                x0[q] = kept ? kn[q] : f0;
-                o[q] = kept ? __builtin_fmaf(k.h1, kn[q], k.h2 * z[q]) : fo;
-            }
-            if (x0_out) reinterpret_cast<f32x4*>(x0_out)[i] = x0;
-            reinterpret_cast<f32x4*>(out)[i] = o;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256) {
-            const bool kept = keep[sampler_col(i, n_points)] != 0;
-            const float x = x_t[i], z = noise[i], kn = known[i];
-            const float f0 = sampler_x0(k, x, (float)eps[i], a.has_clip, a.clip_lo, a.clip_hi);
-            float fo = __builtin_fmaf(k.c1, f0, k.c2 * x);
-            if (!det) fo = __builtin_fmaf(k.s, z, fo);
-            if (x0_out) x0_out[i] = kept ? kn : f0;
-            out[i] = kept ? __builtin_fmaf(k.h1, kn, k.h2 * z) : fo;
-        }
-    }
-}
-
-struct SamplerKeepArgs {
-    NpcdSamplerTensor tz[2];
-    const uint8_t* keep[2];          // [B, n_points] or null: that tensor goes by its mode
-    int64_t n_points;
-    int vec[2];
-    int det;
-};
-
-__global__ __launch_bounds__(256) void sampler_step_keep_kernel(SamplerKeepArgs args, const int64_t* __restrict__ t, const float* __restrict__ table,
-                                                                int T) {
-    const int z = blockIdx.z, b = blockIdx.y;
-    const NpcdSamplerTensor& a = args.tz[z];
-    const int vec = args.vec[z];
-    const SamplerCoef k = sampler_coef(t, table, T, b);
-    const int64_t base = (int64_t)b * a.per_sample;
-    if (!args.keep[z]) {
-        sampler_by_mode(a, vec, k, base);
-        return;
-    }
-    const uint8_t* keep = args.keep[z] + (int64_t)b * args.n_points;
-    if (a.eps_dtype == NPCD_F32) {
-        if (vec) sampler_keep<float, true>(a, keep, args.n_points, args.det, k, base);
-        else sampler_keep<float, false>(a, keep, args.n_points, args.det, k, base);
-    } else {
-        if (vec) sampler_keep<__bf16, true>(a, keep, args.n_points, args.det, k, base);
-        else sampler_keep<__bf16, false>(a, keep, args.n_points, args.det, k, base);
-    }
-}
-
-// Second-order multistep step (npcd_sampler_step_multistep; DPM-Solver++ 2M in data prediction, Lu et al. 2022, on a deterministic
-// schedule): the reverse step with the data prediction extrapolated from the previous step's, which `hist` carries from launch to launch
-//   x0 = sampler_x0 (clipped),  D = (w == 0) ? x0 : fma(w, x0 - hist, x0),  out = fma(c1, D, c2 x),  hist = x0
-// w is column 7 of the sample's table row (0 in the tables of npcd_sampler_step).  A row with w = 0 -- the first step, which has no
-// history, and the step to the data -- loads nothing from `hist`, and its out is sampler_reverse's without noise: the same bits.  The
-// branch is uniform over the workgroup (one sample, one w).  Every lane reads and then overwrites its own elements of `hist`, which
-// no other lane touches.  roundings past x0: the subtraction, the fma of D, c2 x, the fma of out.
-// KEEP: the select of sampler_keep -- kept points take the hold expression on `known`, and hist and x0_out receive `known` there.
-__device__ __forceinline__ float sampler_multistep_d(float w, float x0, float h) { return __builtin_fmaf(w, x0 - h, x0); }
-
-template <class EPS, bool VEC, bool KEEP>
-__device__ __forceinline__ void sampler_multistep(const NpcdSamplerTensor& a, float* __restrict__ hist, const uint8_t* __restrict__ keep,
-                                                  int64_t n_points, const SamplerCoef& k, float w, int64_t base) {
-    const float* __restrict__ x_t = a.x_t + base;
-    const EPS* __restrict__ eps = static_cast<const EPS*>(a.eps) + base;
-    const float* __restrict__ noise = KEEP ? a.noise + base : nullptr;
-    const float* __restrict__ known = KEEP ? a.known + base : nullptr;
-    float* __restrict__ out = a.out + base;
-    float* __restrict__ x0_out = a.x0_out ? a.x0_out + base : nullptr;
-    hist += base;
-    const bool first_order = w == 0.f;
-    if constexpr (VEC) {
-        const int64_t n4 = a.per_sample / 4, row4 = KEEP ? n_points / 4 : 1;
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-            const f32x4 x = reinterpret_cast<const f32x4*>(x_t)[i];
-            const f32x4 e = to_f32(reinterpret_cast<const typename V<EPS>::x4*>(eps)[i]);
-            f32x4 h = f32x4{0.f, 0.f, 0.f, 0.f}, z = h, kn = h;
-            if (!first_order) h = reinterpret_cast<const f32x4*>(hist)[i];
-            uint32_t m = 0;
-            if constexpr (KEEP) {
-                m = reinterpret_cast<const uint32_t*>(keep)[sampler_col(i, row4)];
-                z = reinterpret_cast<const f32x4*>(noise)[i];
-                kn = reinterpret_cast<const f32x4*>(known)[i];
-            }
-            f32x4 x0, o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float f0 = sampler_x0(k, x[q], e[q], a.has_clip, a.clip_lo, a.clip_hi);
-                const float d = first_order ? f0 : sampler_multistep_d(w, f0, h[q]);
-                const float fo = __builtin_fmaf(k.c1, d, k.c2 * x[q]);
-                const bool kept = KEEP && ((m >> (8 * q)) & 0xffu) != 0;
-                x0[q] = kept ? kn[q] : f0;
-                o[q] = kept ? __builtin_fmaf(k.h1, kn[q], k.h2 * z[q]) : fo;
-            }
-            if (x0_out) reinterpret_cast<f32x4*>(x0_out)[i] = x0;
-            reinterpret_cast<f32x4*>(hist)[i] = x0;
-            reinterpret_cast<f32x4*>(out)[i] = o;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.per_sample; i += (int64_t)gridDim.x * 256) {
-            const float x = x_t[i];
-            const float f0 = sampler_x0(k, x, (float)eps[i], a.has_clip, a.clip_lo, a.clip_hi);
-            const float d = first_order ? f0 : sampler_multistep_d(w, f0, hist[i]);
-            float o = __builtin_fmaf(k.c1, d, k.c2 * x), x0 = f0;
-            if constexpr (KEEP) {
-                if (keep[sampler_col(i, n_points)] != 0) {
-                    x0 = known[i];
-                    o = __builtin_fmaf(k.h1, x0, k.h2 * noise[i]);
-                }
-            }
-            if (x0_out) x0_out[i] = x0;
-            hist[i] = x0;
-            out[i] = o;
-        }
-    }
-}
-
-struct SamplerMultistepArgs {
-    NpcdSamplerTensor tz[2];
-    float* hist[2];                  // [B, per_sample]; null only for a hold-mode tensor
-    const uint8_t* keep[2];          // [B, n_points] or null: that tensor goes by its mode
-    int64_t n_points;
-    int vec[2];
-};
-
-template <class EPS>
-__device__ __forceinline__ void sampler_multistep_by_path(const NpcdSamplerTensor& a, float* hist, const uint8_t* keep, int64_t n_points, int vec,
-                                                          const SamplerCoef& k, float w, int64_t base) {
-    if (keep) {
-        if (vec) sampler_multistep<EPS, true, true>(a, hist, keep, n_points, k, w, base);
-        else sampler_multistep<EPS, false, true>(a, hist, keep, n_points, k, w, base);
-    } else {
-        if (vec) sampler_multistep<EPS, true, false>(a, hist, keep, n_points, k, w, base);
-        else sampler_multistep<EPS, false, false>(a, hist, keep, n_points, k, w, base);
-    }
-}
-
-__global__ __launch_bounds__(256) void sampler_step_multistep_kernel(SamplerMultistepArgs args, const int64_t* __restrict__ t,
-                                                                     const float* __restrict__ table, int T) {
-    const int z = blockIdx.z, b = blockIdx.y;
-    const NpcdSamplerTensor& a = args.tz[z];
-    const SamplerCoef k = sampler_coef(t, table, T, b);
-    const int64_t base = (int64_t)b * a.per_sample;
-    if (!args.keep[z] && a.mode == NPCD_SAMPLER_HOLD) {
-        if (args.vec[z]) sampler_hold<true>(a, k, base);
-        else sampler_hold<false>(a, k, base);
-        return;
-    }
-    const int64_t ts = t[b];
-    const float w = (ts >= 0 && ts < T) ? table[8 * ts + 7] : __builtin_nanf("");
-    const uint8_t* keep = args.keep[z] ? args.keep[z] + (int64_t)b * args.n_points : nullptr;
-    if (a.eps_dtype == NPCD_F32) sampler_multistep_by_path<float>(a, args.hist[z], keep, args.n_points, args.vec[z], k, w, base);
-    else sampler_multistep_by_path<__bf16>(a, args.hist[z], keep, args.n_points, args.vec[z], k, w, base);
-}
-
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace npcd
 
 using namespace npcd;
@@ -1318,146 +982,6 @@ extern "C" int npcd_scaler_finalize(const double* stats, int nslots, NpcdScalerC
     if ((reinterpret_cast<uintptr_t>(stats) & 7) || (reinterpret_cast<uintptr_t>(ctl) & 15)) return NPCD_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(scaler_finalize_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), stats, nslots, ctl, scaling, clip, max_norm,
                        beta1, beta2, growth_factor, backoff_factor, growth_interval);
-    NPCD_HIP_CHECK(hipGetLastError());
-    return NPCD_OK;
-}
-
-extern "C" int npcd_ddpm_reverse_step(const float* x_t, const void* eps, int eps_dtype, const float* noise, float* x_prev, float* x0_out,
-                                      const int64_t* t, int B, int64_t per_sample, const float* tab_recip, const float* tab_recipm1,
-                                      const float* tab_coef1, const float* tab_coef2, const float* tab_logvar, float clip_lo, float clip_hi,
-                                      int has_clip, void* stream) {
-    if (!x_t || !eps || !noise || !x_prev || !t || B <= 0 || per_sample <= 0) return NPCD_ERR_ARG;
-    if (!tab_recip || !tab_recipm1 || !tab_coef1 || !tab_coef2 || !tab_logvar) return NPCD_ERR_ARG;
-    if (eps_dtype != NPCD_F32 && eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
-    const DdpmTables tab{tab_recip, tab_recipm1, tab_coef1, tab_coef2, tab_logvar};
-    const int gx = (int)((per_sample + 255) / 256 < 1024 ? (per_sample + 255) / 256 : 1024);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (eps_dtype == NPCD_F32)
-        hipLaunchKernelGGL(ddpm_reverse_kernel<float>, dim3(gx, B), dim3(256), 0, st, x_t, static_cast<const float*>(eps), noise, x_prev, x0_out, t,
-                           per_sample, tab, clip_lo, clip_hi, has_clip);
-    else
-        hipLaunchKernelGGL(ddpm_reverse_kernel<__bf16>, dim3(gx, B), dim3(256), 0, st, x_t, static_cast<const __bf16*>(eps), noise, x_prev, x0_out, t,
-                           per_sample, tab, clip_lo, clip_hi, has_clip);
-    NPCD_HIP_CHECK(hipGetLastError());
-    return NPCD_OK;
-}
-
-// One tensor of npcd_sampler_step by its mode: the operands it needs, whether it takes the 16-byte path
-static int sampler_check_mode(const NpcdSamplerTensor& a, int deterministic, bool* vec_out) {
-    if (!a.out || a.per_sample <= 0) return NPCD_ERR_ARG;
-    bool vec = a.per_sample % 4 == 0 && al16(a.out);
-    if (a.mode == NPCD_SAMPLER_HOLD) {
-        if (!a.known || !a.noise) return NPCD_ERR_ARG;
-        vec = vec && al16(a.known) && al16(a.noise);
-    } else if (a.mode == NPCD_SAMPLER_REVERSE) {
-        if (!a.x_t || !a.eps || (!a.noise && !deterministic)) return NPCD_ERR_ARG;
-        if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
-        vec = vec && al16(a.x_t) && (!a.noise || al16(a.noise)) && (!a.x0_out || al16(a.x0_out)) &&
-              (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
-    } else {
-        return NPCD_ERR_ARG;
-    }
-    *vec_out = vec;
-    return NPCD_OK;
-}
-
-// the grid of ddpm_reverse_kernel: one sweep of 256 lanes per workgroup, at most 1024 workgroups per sample, the rest strided
-static int sampler_grid(const NpcdSamplerTensor& a, bool vec) {
-    const int64_t items = vec ? a.per_sample / 4 : a.per_sample;
-    return (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
-}
-
-extern "C" int npcd_sampler_step(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const int64_t* t, const float* table, int T,
-                                 int B, int deterministic, void* stream) {
-    if (!coords || !feats || !t || !table || T <= 0 || B <= 0) return NPCD_ERR_ARG;
-    if (B > 65535 || !al16(table)) return NPCD_ERR_UNSUPPORTED;
-    SamplerArgs args;
-    int gx = 1;
-    for (int z = 0; z < 2; ++z) {
-        const NpcdSamplerTensor& a = z ? *feats : *coords;
-        bool vec = false;
-        const int rc = sampler_check_mode(a, deterministic, &vec);
-        if (rc != NPCD_OK) return rc;
-        args.tz[z] = a;
-        args.vec[z] = vec ? 1 : 0;
-        const int g = sampler_grid(a, vec);
-        gx = g > gx ? g : gx;
-    }
-    hipLaunchKernelGGL(sampler_step_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
-    NPCD_HIP_CHECK(hipGetLastError());
-    return NPCD_OK;
-}
-
-extern "C" int npcd_sampler_step_keep(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, const uint8_t* keep_coords,
-                                      const uint8_t* keep_feats, int64_t n_points, const int64_t* t, const float* table, int T, int B,
-                                      int deterministic, void* stream) {
-    if (!coords || !feats || !t || !table || T <= 0 || B <= 0 || n_points <= 0) return NPCD_ERR_ARG;
-    if (B > 65535 || !al16(table)) return NPCD_ERR_UNSUPPORTED;
-    SamplerKeepArgs args;
-    args.n_points = n_points;
-    args.det = deterministic ? 1 : 0;
-    int gx = 1;
-    for (int z = 0; z < 2; ++z) {
-        const NpcdSamplerTensor& a = z ? *feats : *coords;
-        const uint8_t* keep = z ? keep_feats : keep_coords;
-        bool vec = false;
-        if (!keep) {
-            const int rc = sampler_check_mode(a, deterministic, &vec);
-            if (rc != NPCD_OK) return rc;
-        } else {
-            if (!a.out || !a.x_t || !a.eps || !a.noise || !a.known || a.per_sample <= 0 || a.per_sample % n_points != 0) return NPCD_ERR_ARG;
-            if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
-            vec = n_points % 4 == 0 && (reinterpret_cast<uintptr_t>(keep) & 3) == 0 && al16(a.out) && al16(a.x_t) && al16(a.noise) &&
-                  al16(a.known) && (!a.x0_out || al16(a.x0_out)) &&
-                  (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
-        }
-        args.tz[z] = a;
-        args.keep[z] = keep;
-        args.vec[z] = vec ? 1 : 0;
-        const int g = sampler_grid(a, vec);
-        gx = g > gx ? g : gx;
-    }
-    hipLaunchKernelGGL(sampler_step_keep_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
-    NPCD_HIP_CHECK(hipGetLastError());
-    return NPCD_OK;
-}
-
-extern "C" int npcd_sampler_step_multistep(const NpcdSamplerTensor* coords, const NpcdSamplerTensor* feats, float* hist_coords,
-                                           float* hist_feats, const uint8_t* keep_coords, const uint8_t* keep_feats, int64_t n_points,
-                                           const int64_t* t, const float* table, int T, int B, void* stream) {
-    if (!coords || !feats || !t || !table || T <= 0 || B <= 0) return NPCD_ERR_ARG;
-    if ((keep_coords || keep_feats) && n_points <= 0) return NPCD_ERR_ARG;
-    if (B > 65535 || !al16(table)) return NPCD_ERR_UNSUPPORTED;
-    SamplerMultistepArgs args;
-    args.n_points = n_points;
-    int gx = 1;
-    for (int z = 0; z < 2; ++z) {
-        const NpcdSamplerTensor& a = z ? *feats : *coords;
-        const uint8_t* keep = z ? keep_feats : keep_coords;
-        float* hist = z ? hist_feats : hist_coords;
-        bool vec = false;
-        if (!keep) {
-            const int rc = sampler_check_mode(a, 1, &vec);          // the schedule is deterministic: a reverse tensor needs no noise
-            if (rc != NPCD_OK) return rc;
-        } else {
-            if (!a.out || !a.x_t || !a.eps || !a.noise || !a.known || a.per_sample <= 0 || a.per_sample % n_points != 0) return NPCD_ERR_ARG;
-            if (a.eps_dtype != NPCD_F32 && a.eps_dtype != NPCD_BF16) return NPCD_ERR_UNSUPPORTED;
-            vec = n_points % 4 == 0 && (reinterpret_cast<uintptr_t>(keep) & 3) == 0 && al16(a.out) && al16(a.x_t) && al16(a.noise) &&
-                  al16(a.known) && (!a.x0_out || al16(a.x0_out)) &&
-                  (reinterpret_cast<uintptr_t>(a.eps) & (a.eps_dtype == NPCD_F32 ? 15 : 7)) == 0;
-        }
-        if (keep || a.mode != NPCD_SAMPLER_HOLD) {
-            if (!hist) return NPCD_ERR_ARG;
-            vec = vec && al16(hist);
-        }
-        args.tz[z] = a;
-        args.hist[z] = hist;
-        args.keep[z] = keep;
-        args.vec[z] = vec ? 1 : 0;
-        const int g = sampler_grid(a, vec);
-        gx = g > gx ? g : gx;
-    }
-    hipLaunchKernelGGL(sampler_step_multistep_kernel, dim3(gx, B, 2), dim3(256), 0, static_cast<hipStream_t>(stream), args, t, table, T);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }

@@ -1,4 +1,4 @@
-"""Wrappers of the HBM-bound elementwise kernels (csrc/elementwise.hip)."""
+"""Wrappers of the HBM-bound elementwise kernels (csrc/elementwise.hip) and of the sampler's steps (csrc/sampler.hip)."""
 import ctypes
 
 import torch
@@ -456,6 +456,41 @@ def _sampler_tensor(spec, B):
     return rec, out, x0, mask, keep
 
 
+def _sampler_launch(name, coords, feats, t, table, deterministic):
+    """The launch behind sampler_step and sampler_step_multistep (deterministic None: the multistep step, whose tensors carry `hist`):
+    checks t and table, builds both records, reconciles the masks and calls the entry that the step needs."""
+    multistep = deterministic is None
+    require_gpu(t, table)
+    if t.dtype != torch.int64 or table.dtype != _f32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise RuntimeError(f"{name}: t is int64 [B], table a contiguous fp32 [T, 8]")
+    t = t.contiguous()
+    B = t.shape[0]
+    rc, oc, x0c, mc, keep_c = _sampler_tensor(coords, B)
+    rf, of, x0f, mf, keep_f = _sampler_tensor(feats, B)
+    hist = []
+    for spec, rec in ((coords, rc), (feats, rf)):
+        h = spec.get("hist") if multistep else None
+        if h is not None:
+            require_gpu(h)
+            if h.dtype != _f32 or not h.is_contiguous() or h.numel() != B * rec.per_sample:
+                raise RuntimeError(f"{name}: hist is a contiguous fp32 tensor with the shape of x_t (it is written in place)")
+        hist.append(h)
+    if mc is not None and mf is not None and mc.shape != mf.shape:
+        raise RuntimeError(f"{name}: the two masks are [B, N] with one N")
+    masked = mc is not None or mf is not None
+    n_points = (mc if mc is not None else mf).shape[1] if masked else 0
+    recs, masks, tail = (ctypes.byref(rc), ctypes.byref(rf)), (ptr(mc), ptr(mf)), (ptr(t), ptr(table), table.shape[0], B)
+    if multistep:
+        check(lib().npcd_sampler_step_multistep(*recs, ptr(hist[0]), ptr(hist[1]), *masks, n_points, *tail, stream_ptr()),
+              "npcd_sampler_step_multistep")
+    elif masked:
+        check(lib().npcd_sampler_step_keep(*recs, *masks, n_points, *tail, int(bool(deterministic)), stream_ptr()), "npcd_sampler_step_keep")
+    else:
+        check(lib().npcd_sampler_step(*recs, *tail, int(bool(deterministic)), stream_ptr()), "npcd_sampler_step")
+    del keep_c, keep_f
+    return (oc, x0c), (of, x0f)
+
+
 def sampler_step(coords, feats, t, table, deterministic):
     """One step of the scheduled sampler for BOTH tensors in one launch.  `coords` / `feats` are dicts:
          mode "reverse" (default): x_t fp32 [B, ...], eps fp32 or bf16, noise fp32 or None, clip (lo, hi) floats or None, want_x0
@@ -466,24 +501,7 @@ def sampler_step(coords, feats, t, table, deterministic):
        and deterministic (eta == 0: every s of the table is 0, the only case in which a reverse tensor may come without noise) are
        SamplingSchedule.table / .deterministic.  npcd_sampler_step_keep when either tensor has a mask, npcd_sampler_step otherwise.
        -> ((out, x0 or None) of coords, (out, x0 or None) of feats)."""
-    require_gpu(t, table)
-    if t.dtype != torch.int64 or table.dtype != _f32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
-        raise RuntimeError("sampler_step: t is int64 [B], table a contiguous fp32 [T, 8]")
-    t = t.contiguous()
-    B = t.shape[0]
-    rc, oc, x0c, mc, keep_c = _sampler_tensor(coords, B)
-    rf, of, x0f, mf, keep_f = _sampler_tensor(feats, B)
-    if mc is None and mf is None:
-        check(lib().npcd_sampler_step(ctypes.byref(rc), ctypes.byref(rf), ptr(t), ptr(table), table.shape[0], B, int(bool(deterministic)),
-                                      stream_ptr()), "npcd_sampler_step")
-    else:
-        if mc is not None and mf is not None and mc.shape != mf.shape:
-            raise RuntimeError("sampler_step: the two masks are [B, N] with one N")
-        n_points = (mc if mc is not None else mf).shape[1]
-        check(lib().npcd_sampler_step_keep(ctypes.byref(rc), ctypes.byref(rf), ptr(mc), ptr(mf), n_points, ptr(t), ptr(table),
-                                           table.shape[0], B, int(bool(deterministic)), stream_ptr()), "npcd_sampler_step_keep")
-    del keep_c, keep_f
-    return (oc, x0c), (of, x0f)
+    return _sampler_launch("sampler_step", coords, feats, t, table, deterministic)
 
 
 def sampler_step_multistep(coords, feats, t, table):
@@ -493,28 +511,7 @@ def sampler_step_multistep(coords, feats, t, table):
                in place with this step's x0 (`known` at kept points)
        noise is read only by a hold-mode tensor and by a tensor with a mask.  t int64 [B]; table fp32 [T, 8] is
        SamplingSchedule.multistep_table (w in column 7).  -> ((out, x0 or None) of coords, (out, x0 or None) of feats)."""
-    require_gpu(t, table)
-    if t.dtype != torch.int64 or table.dtype != _f32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
-        raise RuntimeError("sampler_step_multistep: t is int64 [B], table a contiguous fp32 [T, 8]")
-    t = t.contiguous()
-    B = t.shape[0]
-    rc, oc, x0c, mc, keep_c = _sampler_tensor(coords, B)
-    rf, of, x0f, mf, keep_f = _sampler_tensor(feats, B)
-    hist = []
-    for spec, rec in ((coords, rc), (feats, rf)):
-        h = spec.get("hist")
-        if h is not None:
-            require_gpu(h)
-            if h.dtype != _f32 or not h.is_contiguous() or h.numel() != B * rec.per_sample:
-                raise RuntimeError("sampler_step_multistep: hist is a contiguous fp32 tensor with the shape of x_t (it is written in place)")
-        hist.append(h)
-    if mc is not None and mf is not None and mc.shape != mf.shape:
-        raise RuntimeError("sampler_step_multistep: the two masks are [B, N] with one N")
-    n_points = 0 if mc is None and mf is None else (mc if mc is not None else mf).shape[1]
-    check(lib().npcd_sampler_step_multistep(ctypes.byref(rc), ctypes.byref(rf), ptr(hist[0]), ptr(hist[1]), ptr(mc), ptr(mf), n_points,
-                                            ptr(t), ptr(table), table.shape[0], B, stream_ptr()), "npcd_sampler_step_multistep")
-    del keep_c, keep_f
-    return (oc, x0c), (of, x0f)
+    return _sampler_launch("sampler_step_multistep", coords, feats, t, table, None)
 
 
 def q_sample(x0, noise, t, tab_sqrt_acp, tab_sqrt_1macp):

@@ -307,15 +307,23 @@ class GaussianDiffusion(nn.Module):
         zf = torch.randn_like(f) if draw_f else None
         return zc, zf
 
-    def _multistep_update(self, c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist):
-        """_scheduled_update for solver="dpmpp2m": the reverse step with x0 replaced by D = x0 + w (x0 - hist) where the level's w is
-        not 0 (selected: a history that is not read may hold anything), hist = (coords history, feats history), each the previous
-        step's clipped x0 of its tensor (None for a held tensor), overwritten in place with this step's (the known values at kept
-        points).  fused: ONE npcd_sampler_step_multistep launch for both tensors."""
+    def _scheduled_update(self, c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist=None):
+        """The update of one step on given eps and noise.  fused: ONE launch for both tensors (npcd_sampler_step, or
+        npcd_sampler_step_keep when a tensor has a mask), clip_* are (lo, hi) floats or None; otherwise the same step in torch,
+        clip_* are the ranges as given to p_sample_loop.  A tensor with a mask: where(mask, the hold expression on its known values,
+        the reverse step) -- selected, so that nothing of the branch not taken reaches the result.
+        hist given (solver="dpmpp2m"): the second-order multistep step, ONE npcd_sampler_step_multistep launch when fused -- the
+        reverse step with x0 replaced by D = x0 + w (x0 - hist) where the level's w is not 0 (selected: a history that is not read may
+        hold anything) and without a noise term; hist = (coords history, feats history), each the previous step's clipped x0 of its
+        tensor (None for a held tensor), overwritten in place with this step's (the known values at kept points)."""
+        multistep = hist is not None
+        table = sched.multistep_table if multistep else sched.table         # [T, 8]: r, m, c1, c2, s, h1, h2, w (0 in sched.table)
+        tensors = (("coords", c, eps_c, zc, clip_c, hist[0] if multistep else None),
+                   ("feats", f, eps_f, zf, clip_f, hist[1] if multistep else None))
         if fused:
             from ...hip import elementwise as ew
             spec = []
-            for name, x, eps, z, clip, h in (("coords", c, eps_c, zc, clip_c, hist[0]), ("feats", f, eps_f, zf, clip_f, hist[1])):
+            for name, x, eps, z, clip, h in tensors:
                 if which == name:
                     spec.append(dict(mode="hold", known=known, noise=z))
                     continue
@@ -323,66 +331,32 @@ class GaussianDiffusion(nn.Module):
                 if name in keep:
                     spec.append(dict(mode="keep", x_t=x, eps=eps, noise=z, known=keep[name][0], keep=keep[name][1], clip=clip, hist=h))
                 else:
-                    spec.append(dict(mode="reverse", x_t=x, eps=eps, clip=clip, hist=h))
-            (c_next, _), (f_next, _) = ew.sampler_step_multistep(spec[0], spec[1], t, sched.multistep_table)
+                    spec.append(dict(mode="reverse", x_t=x, eps=eps, noise=None if multistep else z, clip=clip, hist=h))
+            if multistep:
+                (c_next, _), (f_next, _) = ew.sampler_step_multistep(spec[0], spec[1], t, table)
+            else:
+                (c_next, _), (f_next, _) = ew.sampler_step(spec[0], spec[1], t, table, sched.deterministic)
             return c_next, f_next
-        row = sched.multistep_table.to(t.device)[t]                         # [B, 8]: r, m, c1, c2, 0, h1, h2, w
+        row = table.to(t.device)[t]
         out = []
-        for name, x, eps, z, clip, h in (("coords", c, eps_c, zc, clip_c, hist[0]), ("feats", f, eps_f, zf, clip_f, hist[1])):
+        for name, x, eps, z, clip, h in tensors:
             k = [row[:, j].reshape((-1,) + (1,) * (x.dim() - 1)) for j in range(8)]
             if which == name:
                 out.append(k[5] * known + k[6] * z)
                 continue
-            x0 = k[0] * x - k[1] * (eps if eps.dtype == torch.float64 else eps.float())
+            x0 = k[0] * x - k[1] * (eps if multistep and eps.dtype == torch.float64 else eps.float())
             if clip is not None:
                 x0 = torch.clamp(x0, clip[0], clip[1])
-            nxt = k[2] * torch.where(k[7] == 0, x0, x0 + k[7] * (x0 - h)) + k[3] * x
+            nxt = k[2] * (torch.where(k[7] == 0, x0, x0 + k[7] * (x0 - h)) if multistep else x0) + k[3] * x
+            if not multistep and (not sched.deterministic if name in keep else z is not None):
+                nxt = nxt + k[4] * z
             if name in keep:
                 kn, mask = keep[name]
                 nxt = torch.where(mask[:, None, :], k[5] * kn + k[6] * z, nxt)
-                x0 = torch.where(mask[:, None, :], kn, x0)
-            h.copy_(x0)
+                x0 = torch.where(mask[:, None, :], kn, x0) if multistep else x0
+            if multistep:
+                h.copy_(x0)
             out.append(nxt)
-        return out[0], out[1]
-
-    def _scheduled_update(self, c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist=None):
-        """The update of one step on given eps and noise.  fused: ONE launch for both tensors (npcd_sampler_step, or
-        npcd_sampler_step_keep when a tensor has a mask), clip_* are (lo, hi) floats or None; otherwise the same step in torch,
-        clip_* are the ranges as given to p_sample_loop.  A tensor with a mask: where(mask, the hold expression on its known values,
-        the reverse step) -- selected, so that nothing of the branch not taken reaches the result.  hist given: the second-order
-        multistep step (_multistep_update)."""
-        if hist is not None:
-            return self._multistep_update(c, f, eps_c, eps_f, zc, zf, t, sched, which, known, clip_c, clip_f, fused, keep, hist)
-        if fused:
-            from ...hip import elementwise as ew
-            spec = []
-            for name, x, eps, z, clip in (("coords", c, eps_c, zc, clip_c), ("feats", f, eps_f, zf, clip_f)):
-                if which == name:
-                    spec.append(dict(mode="hold", known=known, noise=z))
-                    continue
-                eps = eps if eps.dtype in (torch.float32, torch.bfloat16) else eps.float()
-                if name in keep:
-                    spec.append(dict(mode="keep", x_t=x, eps=eps, noise=z, known=keep[name][0], keep=keep[name][1], clip=clip))
-                else:
-                    spec.append(dict(mode="reverse", x_t=x, eps=eps, noise=z, clip=clip))
-            (c_next, _), (f_next, _) = ew.sampler_step(spec[0], spec[1], t, sched.table, sched.deterministic)
-            return c_next, f_next
-        row = sched.table.to(t.device)[t]                                   # [B, 8]: r, m, c1, c2, s, h1, h2, 0
-        out = []
-        for name, x, eps, z, clip in (("coords", c, eps_c, zc, clip_c), ("feats", f, eps_f, zf, clip_f)):
-            k = [row[:, j].reshape((-1,) + (1,) * (x.dim() - 1)) for j in range(7)]
-            if which == name:
-                out.append(k[5] * known + k[6] * z)
-                continue
-            x0 = k[0] * x - k[1] * eps.float()
-            if clip is not None:
-                x0 = torch.clamp(x0, clip[0], clip[1])
-            nxt = k[2] * x0 + k[3] * x
-            if name in keep:
-                kn, mask = keep[name]
-                out.append(torch.where(mask[:, None, :], k[5] * kn + k[6] * z, nxt if sched.deterministic else nxt + k[4] * z))
-            else:
-                out.append(nxt if z is None else nxt + k[4] * z)
         return out[0], out[1]
 
     def _scheduled_step(self, denoise_fn, c, f, t, sched, which, known, clip_c, clip_f, fused, keep=None, hist=None):

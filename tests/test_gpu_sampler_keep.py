@@ -4,7 +4,7 @@ against the same loop composed by hand, the completion toy of tests/test_sampler
 DiffusionModel.generate with masks.
 
 Conventions and bars of tests/test_gpu_sampler_steps.py: guarded outputs that start as NaN, t = (0, one mid-chain level), the rounding
-counts of sampler_x0 / sampler_reverse / sampler_hold.  The masked kernel evaluates the two parents' expressions and selects, so the bar
+counts of sampler_x0 / sampler_element (csrc/sampler.hip).  The masked kernel evaluates the two parents' expressions and selects, so the bar
 of an element is its parent's.
 """
 import ctypes

@@ -5,8 +5,8 @@ convergence conditions of tests/test_sampler_multistep_cpu.py on the fused loop,
 Conventions of tests/test_gpu_sampler_steps.py: float64 references computed on the device from the kernel's own inputs, outputs (and
 here the history, which the kernel updates in place) between sentinel guard bands, t = (0, one mid-chain level) so that one sample has
 w = 0 and the other w > 0, bars from first-order rounding counts with U = 2^-24, a count of n roundings held to (n + 1) U as there.
-Read off the kernel (csrc/elementwise.hip, sampler_x0 / sampler_multistep: every rounding is a written-out subtraction, multiply or
-fused multiply-add):
+Read off the kernel (csrc/sampler.hip, sampler_x0 / sampler_element: every rounding is a written-out subtraction, multiply or fused
+multiply-add):
     x0  = fma(r, x, -(m eps))                   2 roundings  ->  x0bar = 3 U (|r x| + |m eps|); the clamp is 1-Lipschitz
     D   = fma(w, x0 - hist, x0)                 2 roundings  ->  Dbar  = (1 + |w|) x0bar + 3 U (|x0| + |w (x0 - hist)|); hist is an input
           w = 0: D = x0, nothing is added       0 roundings  ->  Dbar  = x0bar
@@ -19,7 +19,7 @@ import math
 import pytest
 import torch
 
-from test_gpu_sampler_steps import BF16, F32, SIZES, U, Guarded, _tiny_model, close, gen, randn, ref_hold, ref_reverse
+from test_gpu_sampler_steps import BF16, F32, SIZE_IDS, SIZES, U, Guarded, _tiny_model, close, gen, randn, ref_hold, ref_reverse
 from test_sampler_multistep_cpu import Gaussian, check_convergence
 
 pytestmark = pytest.mark.gpu
@@ -80,7 +80,7 @@ def _same(a, b):
 # =====================================================================================================================================
 # 1. the kernel against float64 and against the first-order step
 # =====================================================================================================================================
-@pytest.mark.parametrize("sizes", SIZES, ids=["small", "past_cap"])
+@pytest.mark.parametrize("sizes", SIZES, ids=SIZE_IDS)
 @pytest.mark.parametrize("modes", [("reverse", "reverse"), ("hold", "reverse"), ("reverse", "hold")], ids=["rev_rev", "hold_rev", "rev_hold"])
 @pytest.mark.parametrize("with_clip", [True, False], ids=["clip", "no_clip"])
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
@@ -145,8 +145,8 @@ def test_multistep_kernel_against_float64(sched50, dtype, with_clip, modes, size
 # 2. masks
 # =====================================================================================================================================
 # (channels, n_points) of coords and of feats: the smallest 16-byte case; one element per lane (mask rows not 4-byte addressable); the
-# protocol's shape
-MASK_SHAPES = [((3, 4), (32, 4)), ((3, 509), (32, 509)), ((3, 512), (32, 512))]
+# protocol's shape; feats past the grid cap of the 16-byte loop (32 x 32800 = 1,049,600 > 1,048,576), coords one element per lane
+MASK_SHAPES = [((3, 4), (32, 4)), ((3, 509), (32, 509)), ((3, 512), (32, 512)), ((3, 100001), (32, 32800))]
 
 
 def _mask(g, B, N):
@@ -155,7 +155,7 @@ def _mask(g, B, N):
     return m
 
 
-@pytest.mark.parametrize("shapes", MASK_SHAPES, ids=["vec_min", "scalar_509", "protocol_512"])
+@pytest.mark.parametrize("shapes", MASK_SHAPES, ids=["vec_min", "scalar_509", "protocol_512", "past_cap"])
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
 def test_masked_multistep_is_a_select_of_hold_and_the_unmasked_step(sched50, dtype, shapes):
     """Kept points: the bits of the hold mode on `known`; free points: the bits of the unmasked multistep call; x0_out and the
@@ -164,13 +164,15 @@ def test_masked_multistep_is_a_select_of_hold_and_the_unmasked_step(sched50, dty
     ew = _ew()
     sched, ddim, t = sched50
     table = sched.multistep_table
-    B, N = 2, shapes[0][1]
-    g = gen(N + 11)
-    mask = _mask(g, B, N)
-    m3 = mask[:, None, :]
-    byte_mask = mask.to(torch.uint8) * 173 if dtype == BF16 else mask          # a byte mask: any non-zero value keeps
+    B = 2
+    g = gen(shapes[0][1] + 11)
+    one_n = shapes[0][1] == shapes[1][1]
+    masks = [_mask(g, B, shapes[0][1])]
+    masks.append(masks[0] if one_n else _mask(g, B, shapes[1][1]))
+    byte_masks = [m.to(torch.uint8) * 173 if dtype == BF16 else m for m in masks]       # a byte mask: any non-zero value keeps
     clean, dirty = [], []
-    for C, _ in shapes:
+    for (C, N), mask in zip(shapes, masks):
+        m3 = mask[:, None, :]
         x, eps, known, noise, hist = randn(g, B, C, N), randn(g, B, C, N).to(dtype), randn(g, B, C, N), randn(g, B, C, N), randn(g, B, C, N)
         nan = torch.full_like(x, NAN)
         clean.append((x, eps, known, noise, hist))
@@ -181,24 +183,32 @@ def test_masked_multistep_is_a_select_of_hold_and_the_unmasked_step(sched50, dty
     free_hist = [c[4].clone() for c in clean]
     free = [(o.clone(), x0.clone()) for o, x0 in ew.sampler_step_multistep(
         *[dict(x_t=c[0], eps=c[1], clip=cl, want_x0=True, hist=h) for c, cl, h in zip(clean, CLIPS, free_hist)], t, table)]
-    outs = [(Guarded((B,) + s), Guarded((B,) + s), Guarded((B,) + s)) for s in shapes]
-    for (_, _, h), d in zip(outs, dirty):
-        h.t.copy_(d[4])
-    specs = [dict(mode="keep", x_t=d[0], eps=d[1], known=d[2], noise=d[3], keep=byte_mask, clip=cl, out=o.t, x0_out=x0.t, hist=h.t)
-             for d, cl, (o, x0, h) in zip(dirty, CLIPS, outs)]
-    ew.sampler_step_multistep(specs[0], specs[1], t, table)
-    for name, (x, eps, known, noise, hist), cl, (o, x0, h), oh, (om, x0m), fh in zip(("coords", "feats"), clean, CLIPS, outs, hold, free, free_hist):
-        for buf, what in ((o, "out"), (x0, "x0"), (h, "hist")):
-            buf.check(f"{name} {what}")
-        assert 0 < int(m3.sum()) < m3.numel()
-        assert torch.equal(o.t, torch.where(m3, oh, om)), f"{name}: out is not where(mask, hold, multistep)"
-        assert torch.equal(x0.t, torch.where(m3, known, x0m)), f"{name}: x0 is not where(mask, known, x0)"
-        assert torch.equal(h.t, x0.t) and torch.equal(fh, x0m), f"{name}: the history after the call is not x0"
-        href, hbar = ref_hold(table, t, known, noise)
-        _, _, rref, rbar = ref_multistep(table, t, x, eps, hist, cl)
-        close(f"masked {name}{tuple(x.shape[1:])}", o.t, torch.where(m3, href, rref), torch.where(m3, hbar, rbar))
-        k0 = m3[0].expand_as(o.t[0])
-        assert torch.equal(o.t[0][k0], known[0][k0])                          # the step to the data: the known values themselves
+    # a launch has one n_points: where the two tensors differ in it, each is masked in a launch of its own, beside the other without a mask
+    for plan in [(True, True)] if one_n else [(True, False), (False, True)]:
+        outs = [(Guarded((B,) + s), Guarded((B,) + s), Guarded((B,) + s)) for s in shapes]
+        for masked, (_, _, h), c, d in zip(plan, outs, clean, dirty):
+            h.t.copy_(d[4] if masked else c[4])
+        specs = [dict(mode="keep", x_t=d[0], eps=d[1], known=d[2], noise=d[3], keep=bm, clip=cl, out=o.t, x0_out=x0.t, hist=h.t) if masked else
+                 dict(x_t=c[0], eps=c[1], clip=cl, out=o.t, x0_out=x0.t, hist=h.t)
+                 for masked, c, d, bm, cl, (o, x0, h) in zip(plan, clean, dirty, byte_masks, CLIPS, outs)]
+        ew.sampler_step_multistep(specs[0], specs[1], t, table)
+        for name, masked, mask, (x, eps, known, noise, hist), cl, (o, x0, h), oh, (om, x0m), fh in zip(
+                ("coords", "feats"), plan, masks, clean, CLIPS, outs, hold, free, free_hist):
+            m3 = mask[:, None, :]
+            for buf, what in ((o, "out"), (x0, "x0"), (h, "hist")):
+                buf.check(f"{name} {what}")
+            if not masked:
+                assert torch.equal(o.t, om) and torch.equal(x0.t, x0m) and torch.equal(h.t, x0m), f"{name}: without a mask, not the unmasked call"
+                continue
+            assert 0 < int(m3.sum()) < m3.numel()
+            assert torch.equal(o.t, torch.where(m3, oh, om)), f"{name}: out is not where(mask, hold, multistep)"
+            assert torch.equal(x0.t, torch.where(m3, known, x0m)), f"{name}: x0 is not where(mask, known, x0)"
+            assert torch.equal(h.t, x0.t) and torch.equal(fh, x0m), f"{name}: the history after the call is not x0"
+            href, hbar = ref_hold(table, t, known, noise)
+            _, _, rref, rbar = ref_multistep(table, t, x, eps, hist, cl)
+            close(f"masked {name}{tuple(x.shape[1:])}", o.t, torch.where(m3, href, rref), torch.where(m3, hbar, rbar))
+            k0 = m3[0].expand_as(o.t[0])
+            assert torch.equal(o.t[0][k0], known[0][k0])                      # the step to the data: the known values themselves
 
 
 def test_one_masked_tensor_beside_a_held_and_a_plain_one(sched50):

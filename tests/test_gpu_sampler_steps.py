@@ -3,8 +3,8 @@ and DiffusionModel.generate / npcd.eval.sample_and_render with the new arguments
 
 Conventions of tests/test_gpu_streaming_kernels.py: float64 references computed on the device from the kernel's own inputs, outputs
 between sentinel guard bands that start as NaN, bars from first-order rounding counts with U = 2^-24.  The counts are upper bounds read
-off the kernel (csrc/elementwise.hip, sampler_x0 / sampler_reverse / sampler_hold: every rounding is written out as a multiply or a
-fused multiply-add):
+off the kernel (csrc/sampler.hip, sampler_x0 / sampler_element: every rounding is written out as a multiply or a fused
+multiply-add):
     x0     = fma(r, x, -(m eps))                2 roundings  ->  x0bar = 3 U (|r x| + |m eps|); the clamp is 1-Lipschitz, no element exempt
     x_prev = fma(s, z, fma(c1, x0, c2 x))       3 roundings  ->  |c1| x0bar + 4 U (|c1 x0| + |c2 x|) + 3 U |s z|
     hold   = fma(h1, k, h2 z)                   2 roundings  ->  3 U (|h1 k| + |h2 z|)
@@ -22,7 +22,10 @@ pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
 BF16, F32 = torch.bfloat16, torch.float32
 SENT = 1536.0
-SIZES = [(255, 2720), (300001, 1024 * 256 * 2 + 4465)]          # (coords, feats) elements per sample; the second pair lies past the grid cap
+# (coords, feats) elements per sample; the second pair lies past the grid cap with one element per lane (odd sizes), the third takes
+# feats past the cap of the 16-byte loop: 4 (1024 x 256) + 4 x 257 elements, a stride of 1024 workgroups x 256 lanes x 4 elements
+SIZES = [(255, 2720), (300001, 1024 * 256 * 2 + 4465), (300001, 1_049_604)]
+SIZE_IDS = ["small", "past_cap", "past_cap_vec"]
 
 
 def _ew():
@@ -103,7 +106,7 @@ def process():
 # =====================================================================================================================================
 # 1. the kernel against float64
 # =====================================================================================================================================
-@pytest.mark.parametrize("sizes", SIZES, ids=["small", "past_cap"])
+@pytest.mark.parametrize("sizes", SIZES, ids=SIZE_IDS)
 @pytest.mark.parametrize("modes", [("reverse", "reverse"), ("hold", "reverse"), ("reverse", "hold")], ids=["rev_rev", "hold_rev", "rev_hold"])
 @pytest.mark.parametrize("with_noise", [True, False], ids=["noise", "no_noise"])
 @pytest.mark.parametrize("with_clip", [True, False], ids=["clip", "no_clip"])
@@ -150,6 +153,82 @@ def test_step_kernel_against_float64(process, dtype, with_clip, with_noise, mode
     for (o1, z1), (_, _, _, _, _, _, _, out, x0) in zip(first, refs):
         assert torch.equal(out.t, o1) and torch.equal(x0.t.nan_to_num(7.0), z1.nan_to_num(7.0))
         out.check("second call")
+
+
+# (entry, modes of (coords, feats), eta): every form of the three entries.  coords [2, 3, 8] and feats [2, 32, 36] have different point
+# counts, so a launch carries a mask on one tensor at a time.
+ACCESS_FORMS = {"step_noise": ("step", ("reverse", "reverse"), 0.5), "step_no_noise": ("step", ("reverse", "reverse"), 0.0),
+                "step_hold": ("step", ("hold", "reverse"), 0.5),
+                "keep_coords": ("step", ("keep", "reverse"), 0.5), "keep_feats": ("step", ("reverse", "keep"), 0.5),
+                "keep_coords_det": ("step", ("keep", "reverse"), 0.0), "keep_feats_det": ("step", ("reverse", "keep"), 0.0),
+                "multistep": ("multistep", ("reverse", "reverse"), 0.0),
+                "multistep_keep_coords": ("multistep", ("keep", "reverse"), 0.0), "multistep_keep_feats": ("multistep", ("reverse", "keep"), 0.0)}
+
+
+def _operands_read(entry, mode, eta):
+    """the operands that a tensor of this mode reads or writes in this form"""
+    if mode == "hold":
+        return ["known", "noise", "out"]
+    used = ["x_t", "eps", "out", "x0_out"] + (["hist"] if entry == "multistep" else [])
+    if mode == "keep":
+        return used + ["noise", "known", "keep"]
+    return used + (["noise"] if eta > 0 and entry == "step" else [])
+
+
+def _four_bytes_off(v):
+    """The same values, contiguous, 4 bytes (a mask: 1 byte) past a 16-byte boundary: a [k:] slice of a flat buffer."""
+    k = 1 if v.dtype in (torch.bool, torch.uint8) else 4 // v.element_size()
+    off = torch.empty(v.numel() + k, dtype=v.dtype, device=v.device)[k:].view(v.shape).copy_(v)
+    assert off.is_contiguous() and off.data_ptr() % 16 == k * v.element_size()
+    return off
+
+
+@pytest.mark.parametrize("form", list(ACCESS_FORMS))
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_both_access_paths_give_the_same_bits(process, dtype, form):
+    """Each form once with every operand 16-byte aligned (16 bytes per lane: per_sample and n_points are multiples of 4), then once
+    per operand with that one operand 4 bytes off (one element per lane): out, x0 and the history are the same bits.  Every access is
+    dword-aligned (eps and mask: element-aligned) either way."""
+    ew = _ew()
+    entry, modes, eta = ACCESS_FORMS[form]
+    multistep = entry == "multistep"
+    sched = process.sampling_schedule(steps=50, solver="dpmpp2m") if multistep else process.sampling_schedule(steps=50, eta=eta)
+    table = sched.multistep_table if multistep else sched.table
+    t = torch.tensor([0, int(sched.timesteps[31])], device="cuda")
+    B, g = 2, gen(41)
+    base = []
+    for C, N in ((3, 8), (32, 36)):
+        b = {k: randn(g, B, C, N) for k in ("x_t", "eps", "noise", "known", "hist")}
+        b["eps"] = b["eps"].to(dtype)
+        b["keep"] = torch.rand(B, N, device="cuda", generator=g) < 0.5
+        base.append(b)
+
+    def run(off_tensor=None, off_operand=None):
+        specs, outs = [], []
+        for z, (mode, b) in enumerate(zip(modes, base)):
+            o = dict(b, out=torch.full_like(b["x_t"], SENT), x0_out=torch.full_like(b["x_t"], SENT), hist=b["hist"].clone())
+            assert all(v.data_ptr() % 16 == 0 for v in o.values())
+            if z == off_tensor:
+                o[off_operand] = _four_bytes_off(o[off_operand])
+            if mode == "hold":
+                spec = dict(mode="hold", known=o["known"], noise=o["noise"], out=o["out"])
+            else:
+                spec = dict(mode=mode, x_t=o["x_t"], eps=o["eps"], clip=(-1.5, 1.5), out=o["out"], x0_out=o["x0_out"])
+                spec.update({k: o[k] for k in _operands_read(entry, mode, eta) if k not in spec})
+            specs.append(spec)
+            outs.append((o["out"], o["x0_out"], o["hist"]))
+        if multistep:
+            ew.sampler_step_multistep(specs[0], specs[1], t, table)
+        else:
+            ew.sampler_step(specs[0], specs[1], t, table, sched.deterministic)
+        return outs
+
+    aligned = run()
+    for z, mode in enumerate(modes):
+        assert bool((aligned[z][0] != SENT).all())
+        for operand in _operands_read(entry, mode, eta):
+            for (a, a0, ah), (o, o0, oh) in zip(aligned, run(z, operand)):
+                assert torch.equal(o, a) and torch.equal(o0, a0) and torch.equal(oh, ah), (form, ("coords", "feats")[z], operand)
 
 
 def test_step_kernel_refuses_missing_operands_before_any_launch(process):

@@ -1,4 +1,4 @@
-"""Register and scratch budget of the kernels of csrc/geometry.hip and csrc/attention.hip, read from the compiler's own output (no GPU
+"""Register and scratch budget of the kernels of csrc/geometry.hip, csrc/attention.hip and csrc/sampler.hip, read from the compiler's own output (no GPU
 needed).
 
 Round 6 folded two opt-in experiments into grid_query_wave_kernel as run-time branches; its default form went from 46 to 100
@@ -64,6 +64,7 @@ def _compile(source, out):
 
 kernels = _kernels_of("geometry.hip")
 attention = _kernels_of("attention.hip")
+sampler = _kernels_of("sampler.hip")
 
 
 def _form(kernels, name, *flags):
@@ -134,3 +135,17 @@ def test_attention_forward_has_no_shelved_forms(attention):
     in LDS is gone (docs/experiments.md R11.1 has both as patches)."""
     assert len(_instances(attention, "attn_fwd_kernel")) == 2, sorted(attention)
     assert not [k for k in attention if "attn_fwd_res" in k], sorted(attention)
+
+
+def test_sampler_kernels_keep_eight_waves_per_simd_without_scratch(sampler):
+    """One kernel template stands behind the three entries of the scheduled step (no masks and no history, masks, masks and history);
+    written as three separate kernels they took 24 / 32 / 38 VGPRs.  64 is the most that still allows all 8 waves per SIMD: below
+    it the occupancy of these streaming kernels cannot change.  No kernel of the file spills."""
+    steps = _instances(sampler, "sampler_step_kernel")
+    assert len(steps) == 3 and len(_instances(sampler, "ddpm_reverse_kernel")) == 2, sorted(sampler)
+    for masks, hist in ((False, False), (True, False), (True, True)):
+        k = _form(sampler, "sampler_step_kernel", masks, hist)
+        print(f"sampler_step_kernel<masks={masks}, hist={hist}>: {k}")
+        assert k["vgpr"] <= 64, (masks, hist, k)
+    spilling = {k: v["scratch"] for k, v in sampler.items() if v["scratch"] != 0}
+    assert not spilling, spilling
