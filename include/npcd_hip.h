@@ -851,6 +851,28 @@ int npcd_feature_knn(const void* x, const void* y, int dtype, int n, int m, int 
 int npcd_feature_ball_counts(const void* x, const void* y, int dtype, int n, int m, int D, int64_t ldx, int64_t ldy, const double* rho_y,
                              int splits, double* workspace, int32_t* cnt, double* near, void* stream);
 
+/* ---- isosurface of a density volume (csrc/isosurface.hip): marching tetrahedra on the Kuhn triangulation of the
+ * lattice, the operator under npcd/eval/mesh.py.  vol [B, gz, gy, gx] fp32 contiguous, x fastest; node (x, y, z) has the index
+ * (z gy + y) gx + x and lies at origin + spacing * (x, y, z) (origin_host / spacing_host: three floats each, x y z).  A node is
+ * inside iff f > level.  The surface is a function of the volume alone -- which edges carry a vertex, the vertex on an edge
+ * (t = (level - f_lo) / (f_hi - f_lo), fp32 as written), the order of vertices and triangles, the winding (inside -> outside) and
+ * the canonical form of a triangle are stated in DESIGN.md 5.13 and restated by npcd.eval.mesh.marching_tetrahedra_reference.
+ *   npcd_isosurface_count: counts [B, 2] int64 = (vertices, triangles) of every volume, and in ws (npcd_isosurface_ws_bytes, 8-byte
+ *       aligned) what the second call needs: per node one word (bits 0-6 the crossed edge types, bit 7 "inside", bits 8.. the vertices
+ *       of the node's 1,024-node strip before it), per strip the exclusive vertex (int32) and triangle (int64) bases.  Two launches.
+ *   npcd_isosurface_emit:  vertices [sum V, 3] fp32 and faces [sum F, 3] int32 with indices local to their volume; volume b writes at
+ *       rows vert_offsets[b] / face_offsets[b] (int64 [B], the exclusive sums of counts).  What it writes follows from ws alone: exactly
+ *       counts[b] rows, whatever vol and level hold at this call.  One launch.
+ * The caller reads counts between the two calls to size the outputs.  Exclusive sums in a fixed order, no atomics: the same bits on
+ * every run.  A volume without a crossing is valid: (0, 0), and emit need not be called when nothing is to be written.
+ * NPCD_ERR_ARG for B < 1, an axis below 2 nodes, a NULL pointer or a misaligned ws; NPCD_ERR_UNSUPPORTED for 7 gz gy gx >= 2^31 (the
+ * workspace query returns both too).  Nothing is launched in either case. */
+int64_t npcd_isosurface_ws_bytes(int B, int gz, int gy, int gx);
+int npcd_isosurface_count(const float* vol, int B, int gz, int gy, int gx, float level, void* ws, int64_t* counts, void* stream);
+int npcd_isosurface_emit(const float* vol, int B, int gz, int gy, int gx, float level, const float* origin_host, const float* spacing_host,
+                         const void* ws, const int64_t* vert_offsets, const int64_t* face_offsets, float* vertices, int32_t* faces,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,9 @@ SOURCES = {
     # the feature k-NN forms d2 = max((nx + ny) - 2 g, +0) and the squares of the norms as written: the exact-integer tests and "the same
     # bits for every split" rest on it
     "feature_manifold.hip": ["-ffp-contract=off"],
+    # the isosurface's vertices are the bits of t = (level - f_lo) / (f_hi - f_lo) and origin + spacing * (i + t) as written: the
+    # kernel is compared with its numpy restatement bit for bit
+    "isosurface.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

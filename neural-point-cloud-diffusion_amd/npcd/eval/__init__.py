@@ -10,6 +10,7 @@ from typing import Dict, Iterable, List
 import torch
 
 from ..hip.image_metrics import image_metrics
+from .mesh import extract_mesh, marching_tetrahedra_reference, write_ply  # noqa: F401
 from .shapes import (evaluate_shapes, jensen_shannon_divergence, jsd_from_counts, metrics_from_chamfer,  # noqa: F401
                      metrics_from_distance, normalize_clouds, occupancy_entropy, shape_metrics)
 

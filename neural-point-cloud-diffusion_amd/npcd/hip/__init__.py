@@ -156,6 +156,9 @@ SIGNATURES = {
     "npcd_feature_rows_workspace_bytes": (c_int64, [c_int] * 4),
     "npcd_feature_knn": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, _P, _P, _P]),
     "npcd_feature_ball_counts": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, c_int, _P, _P, _P, _P]),
+    "npcd_isosurface_ws_bytes": (c_int64, [c_int] * 4),
+    "npcd_isosurface_count": (c_int, [_P] + [c_int] * 4 + [c_float, _P, _P, _P]),
+    "npcd_isosurface_emit": (c_int, [_P] + [c_int] * 4 + [c_float, POINTER(c_float), POINTER(c_float)] + [_P] * 5 + [_P]),
 }
 
 _lib = None

@@ -110,3 +110,117 @@ class PointNeRF(nn.Module):
             return self.renderer(coords, feats, extrinsics, intrinsics, resolution, sample_rays)
         finally:
             agg.max_shading_pts, self.renderer.shade_dtype = prev, prev_dtype
+
+    # ---- the field at explicit positions (not in the reference, which reaches it through camera rays only) ---------------------------
+    def _field_numerics(self, mlp_dtype, what: str) -> bool:
+        """-> shade in the fp32 class?  The conditions of render(mlp_dtype=...)."""
+        if mlp_dtype is None:
+            return False
+        if mlp_dtype != torch.float32 or not self.field.fp32_class_ok():
+            raise ValueError(f"{what}(mlp_dtype=...): torch.float32 on the published field architecture, or None")
+        return True
+
+    def _shade_positions(self, coords, feats, x, fp32: bool, view_dir, status):
+        """One chunk: x [B, q, 3] contiguous -> sigma [B, q], rgb [B, q, 3].  The grid holds `coords` already.  view_dir: None,
+        [3] or [B, q, 3]."""
+        field, agg = self.field, self.field.aggregator
+        B, q = x.shape[:2]
+        idx, loc, _, _ = self.voxel_grid.query_dense(agg.k, agg.r, 1, x=x.view(B, q, 1, 3), mode=0, points=coords)
+        valid = (idx[..., 0] >= 0).view(B * q)
+        nb = idx.view(B * q, agg.k)[valid]                            # compact, row-major over [cloud, position]
+        pts = loc.view(B * q, 3)[valid]
+        sigma = torch.zeros(B * q, dtype=torch.float32, device=x.device)
+        rgb = torch.zeros((B * q, 3), dtype=torch.float32, device=x.device)
+        if nb.shape[0]:
+            per_point = view_dir is not None and view_dir.dim() == 3
+            if fp32:
+                point_dir = None
+                if view_dir is not None:
+                    point_dir = view_dir.reshape(-1, 3)[valid] if per_point else view_dir.expand(nb.shape[0], 3)
+                s, c = field.shade_fp32(nb, pts, coords, feats, point_dir)
+            else:
+                dir_bias = point_ray = None
+                if view_dir is not None:          # one bias row per direction; a compact point names its row
+                    dir_bias = field.dir_bias(view_dir.reshape(-1, 3)[valid] if per_point else view_dir.view(1, 3))
+                    point_ray = (torch.arange(nb.shape[0], dtype=torch.int32, device=x.device) if per_point
+                                 else torch.zeros(nb.shape[0], dtype=torch.int32, device=x.device))
+                s, c = field.shade(nb, pts, coords, feats, dir_bias, point_ray, status=status)
+            sigma[valid], rgb[valid] = s, c
+        return sigma.view(B, q), rgb.view(B, q, 3)
+
+    def _view_dir(self, view_dir, B, Q, what: str):
+        if not self.field.use_dir:
+            return None          # a field without view directions ignores the argument
+        if view_dir is None:
+            raise ValueError(f"{what}: this field was built with use_view_dir and needs view_dir ([3] or [B, Q, 3], normalised)")
+        if tuple(view_dir.shape) not in ((3,), (B, Q, 3)):
+            raise ValueError(f"{what}: view_dir must be [3] or [B, Q, 3] = {(B, Q, 3)}; got {tuple(view_dir.shape)}")
+        return view_dir.float()
+
+    @torch.no_grad()
+    def query_field(self, coords, feats, x, mlp_dtype=None, view_dir=None, chunk: int = 1 << 22):
+        """The field at explicit positions: coords [B, N, 3], feats [B, N, F], x [B, Q, 3] -> sigma [B, Q], rgb [B, Q, 3], fp32.
+
+        The path of the renderer's option branches with one position per "ray": the neighbour query of the aggregator (its k, r
+        and the voxel grid), the positions that have a neighbour compacted by torch indexing, shaded by the fused fp16-operand
+        kernels (mlp_dtype=None; their range guard acts as renderer.range_guard says, except that "promote" raises) or in the
+        reference's fp32 class (mlp_dtype=torch.float32, as for render), and scattered into zeros: a position without a neighbour has
+        sigma = 0 and rgb = 0, like an empty slot of the renderer.  `chunk` positions per cloud go through the kernels at a time; the
+        result does not depend on it.  A field with view directions needs view_dir ([3], or [B, Q, 3] -- then every chunk holds one
+        bias row of 256 floats per shaded position), normalised by the caller; the other fields ignore it.  No gradients."""
+        if x.dim() != 3 or x.shape[0] != coords.shape[0] or x.shape[2] != 3:
+            raise ValueError(f"query_field: x must be [B, Q, 3] with B = {coords.shape[0]}; got {tuple(x.shape)}")
+        if chunk < 1:
+            raise ValueError(f"query_field: chunk must be positive; got {chunk}")
+        B, Q = x.shape[:2]
+        fp32 = self._field_numerics(mlp_dtype, "query_field")
+        view_dir = self._view_dir(view_dir, B, Q, "query_field")
+        x = x.detach().float()
+        self._set_pointset(coords)
+        sigma = torch.zeros((B, Q), dtype=torch.float32, device=x.device)
+        rgb = torch.zeros((B, Q, 3), dtype=torch.float32, device=x.device)
+        status = torch.zeros(1, dtype=torch.int32, device=x.device)
+        for q0 in range(0, Q, chunk):
+            q1 = min(Q, q0 + chunk)
+            dirs = view_dir if view_dir is None or view_dir.dim() == 1 else view_dir[:, q0:q1].contiguous()
+            sigma[:, q0:q1], rgb[:, q0:q1] = self._shade_positions(coords, feats, x[:, q0:q1].contiguous(), fp32, dirs, status)
+        if not fp32:
+            self.renderer.check_shading_status(status)
+        return sigma, rgb
+
+    @torch.no_grad()
+    def density_grid(self, coords, feats, resolution=128, bound=None, mlp_dtype=None, chunk: int = 1 << 22):
+        """The density on a lattice: coords [B, N, 3], feats [B, N, F] -> (sigma [B, Gz, Gy, Gx] fp32 contiguous, x fastest,
+        origin [3], spacing [3]).
+
+        resolution: G, or (Gz, Gy, Gx).  Along every axis the nodes are torch.linspace(-bound, bound, G); bound defaults to the
+        renderer's cube_scale.  sigma equals query_field at the node positions; the colour heads' direction input plays no part in
+        the density, so a field with view directions is queried with a fixed one.  origin and spacing are fp32 host tensors in
+        (x, y, z) order: origin = -bound, spacing = 2 bound / (G - 1) per axis -- what npcd.hip.isosurface takes.  The positions
+        are made `chunk` nodes at a time: a 256^3 lattice never exists as a list."""
+        if isinstance(resolution, int):
+            resolution = (resolution,) * 3
+        gz, gy, gx = (int(g) for g in resolution)
+        if min(gz, gy, gx) < 2:
+            raise ValueError(f"density_grid: every axis needs at least 2 nodes; got {(gz, gy, gx)}")
+        bound = float(self.renderer.cube_scale if bound is None else bound)
+        if not bound > 0:
+            raise ValueError(f"density_grid: bound must be positive; got {bound}")
+        fp32 = self._field_numerics(mlp_dtype, "density_grid")
+        B, dev = coords.shape[0], coords.device
+        view_dir = torch.tensor([0.0, 0.0, 1.0], device=dev) if self.field.use_dir else None
+        lz, ly, lx = (torch.linspace(-bound, bound, g, dtype=torch.float32, device=dev) for g in (gz, gy, gx))
+        self._set_pointset(coords)
+        Q = gz * gy * gx
+        sigma = torch.empty((B, Q), dtype=torch.float32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        for q0 in range(0, Q, chunk):
+            node = torch.arange(q0, min(Q, q0 + chunk), device=dev)
+            row = node // gx
+            x = torch.stack((lx[node - row * gx], ly[row % gy], lz[row // gy]), dim=-1)
+            sigma[:, q0:q0 + chunk] = self._shade_positions(coords, feats, x[None].expand(B, -1, 3).contiguous(), fp32, view_dir, status)[0]
+        if not fp32:
+            self.renderer.check_shading_status(status)
+        origin = torch.tensor([-bound] * 3, dtype=torch.float32)
+        spacing = torch.tensor([2.0 * bound / (g - 1) for g in (gx, gy, gz)], dtype=torch.float32)
+        return sigma.view(B, gz, gy, gx), origin, spacing
