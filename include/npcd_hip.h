@@ -873,6 +873,29 @@ int npcd_isosurface_emit(const float* vol, int B, int gz, int gy, int gx, float 
                          const void* ws, const int64_t* vert_offsets, const int64_t* face_offsets, float* vertices, int32_t* faces,
                          void* stream);
 
+/* ---- finishing a mesh (added within ABI 10): connected components of the volume, to drop floaters before the
+ * isosurface is taken, and vertex normals.  vol as above; the specification is restated by connected_components_reference and
+ * vertex_normals_reference of npcd/eval/mesh.py, and the kernels are held to them bit for bit.
+ *   npcd_components_label (csrc/components.hip): two inside nodes (f > level, NaN outside) are adjacent iff they are the two ends of
+ *       one of the isosurface's seven edge types -- 14 neighbours a node.  labels [B, gz, gy, gx] int32 = -1 outside, otherwise the
+ *       smallest node index of the node's component, local to its volume; sizes, the same shape = the component's number of nodes at
+ *       its root node, 0 elsewhere; both fully written.  ws: npcd_components_ws_bytes = 4 B gz gy gx bytes, contents irrelevant
+ *       before and after.  A union-find in three launches (bricks of 16 x 8 x 8 nodes in LDS, the edges between bricks, the labels
+ *       and sizes) on integer minima and additions only: the same bits on every run.  No host synchronisation, no allocation.
+ *       NPCD_ERR_ARG for B < 1, an axis below 2 nodes, a NULL pointer or one that is not 4-byte aligned; NPCD_ERR_UNSUPPORTED for
+ *       gz gy gx >= 2^31 (the workspace query returns both too).  Nothing is launched in either case.
+ *   npcd_isosurface_normals (csrc/isosurface_normals.hip): normals [sum V, 3] fp32 in the rows npcd_isosurface_emit writes its
+ *       vertices to, from the workspace npcd_isosurface_count(vol, ...) left (ws, vert_offsets, level and spacing_host as for emit).
+ *       The vertex on the edge (lo, hi), t = (level - f_lo) / (f_hi - f_lo) from vol, gets n = (-g) / sqrt((gx gx + gy gy) + gz gz),
+ *       g = g_lo + t (g_hi - g_lo), where the node gradients are those of `field` (which may be vol): (f[i + 1] - f[i - 1]) / (2 s) in
+ *       the interior, (f[1] - f[0]) / (1 s) and (f[last] - f[last - 1]) / (1 s) at the borders, fp32 as written.  A normal with a
+ *       component that is not finite is (+0, +0, +0).  One launch.  Refusals as for npcd_isosurface_emit. */
+int64_t npcd_components_ws_bytes(int B, int gz, int gy, int gx);
+int npcd_components_label(const float* vol, int B, int gz, int gy, int gx, float level, void* ws, int32_t* labels, int32_t* sizes,
+                          void* stream);
+int npcd_isosurface_normals(const float* vol, const float* field, int B, int gz, int gy, int gx, float level, const float* spacing_host,
+                            const void* ws, const int64_t* vert_offsets, float* normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

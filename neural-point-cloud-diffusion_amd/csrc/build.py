@@ -67,6 +67,11 @@ SOURCES = {
     # the isosurface's vertices are the bits of t = (level - f_lo) / (f_hi - f_lo) and origin + spacing * (i + t) as written: the
     # kernel is compared with its numpy restatement bit for bit
     "isosurface.hip": ["-ffp-contract=off"],
+    # the vertex normals are the bits of their numpy restatement as well: gradient differences, the interpolation and the
+    # normalisation as written
+    "isosurface_normals.hip": ["-ffp-contract=off"],
+    # the labelling is integer work; its one float operation is the isosurface's own inside test f > level
+    "components.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

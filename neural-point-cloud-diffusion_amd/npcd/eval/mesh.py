@@ -1,7 +1,9 @@
 """Generated objects as triangle meshes: the density of a PointNeRF field on a lattice (PointNeRF.density_grid), its isosurface on
 the GPU (npcd.hip.isosurface, csrc/isosurface.hip) and the field's colour at the vertices (PointNeRF.query_field), plus a PLY
 writer.  `marching_tetrahedra_reference` restates the surface's specification in numpy; the kernel is held to it
-bit for bit (tests/test_gpu_isosurface.py), and it is held to geometry (tests/test_isosurface_cpu.py).
+bit for bit (tests/test_gpu_isosurface.py), and it is held to geometry (tests/test_isosurface_cpu.py).  What finishes a mesh is
+specified the same way: `connected_components_reference`, `select_components` and `filter_components_reference`
+for dropping floaters from the volume, `vertex_normals_reference` for the normals.
 
 This module imports without a GPU; only extract_mesh needs one."""
 import itertools
@@ -117,6 +119,132 @@ def marching_tetrahedra_reference(volume, level: float, origin: Sequence[float] 
     return vertices, faces
 
 
+def _volume(volume, who: str) -> np.ndarray:
+    f = np.ascontiguousarray(np.asarray(volume, dtype=np.float32))
+    if f.ndim != 3 or min(f.shape) < 2:
+        raise ValueError(f"{who}: a volume [Gz, Gy, Gx] with at least 2 nodes per axis; got {f.shape}")
+    return f
+
+
+def connected_components_reference(volume, level: float) -> np.ndarray:
+    """volume [Gz, Gy, Gx] -> labels int64 [Gz, Gy, Gx]: the specification of the component labelling on the CPU.
+
+    Inside: f > level, as in the isosurface (NaN is outside).  Two inside nodes are adjacent iff they are the two ends of one lattice
+    edge of the seven EDGE_TYPES -- the edges of the Kuhn triangulation, 14 neighbours a node; the anti-diagonals do not connect.
+    A node outside gets -1, a node inside the smallest node index (z Gy + y) Gx + x of its component.
+
+    Hooking and pointer jumping: every edge whose ends carry different labels lowers the larger label's own entry to the smaller
+    (a minimum, so the order of the edges does not matter), then every node takes its label's label until nothing changes; repeated
+    until no edge has two labels.  At that point a label is constant on a component, is one of its nodes, and is at most every node
+    that carries it: the smallest."""
+    f = _volume(volume, "connected_components_reference")
+    gz, gy, gx = f.shape
+    with np.errstate(invalid="ignore"):
+        inside = f > np.float32(level)
+    index = np.arange(f.size, dtype=np.int64).reshape(f.shape)
+    lower, upper = [], []
+    for dx, dy, dz in EDGE_TYPES:
+        lo = (slice(0, gz - dz), slice(0, gy - dy), slice(0, gx - dx))
+        hi = (slice(dz, gz), slice(dy, gy), slice(dx, gx))
+        both = inside[lo] & inside[hi]
+        lower.append(index[lo][both])
+        upper.append(index[hi][both])
+    a, b = np.concatenate(lower), np.concatenate(upper)
+    labels = np.where(inside, index, -1).reshape(-1)
+    nodes = np.nonzero(inside.reshape(-1))[0]
+    while a.size:
+        la, lb = labels[a], labels[b]
+        differ = la != lb
+        a, b, la, lb = a[differ], b[differ], la[differ], lb[differ]          # equal labels stay equal: the edge is done
+        np.minimum.at(labels, np.maximum(la, lb), np.minimum(la, lb))
+        while True:
+            jumped = labels[labels[nodes]]
+            if np.array_equal(jumped, labels[nodes]):
+                break
+            labels[nodes] = jumped
+    return labels.reshape(f.shape)
+
+
+def select_components(labels, largest: Optional[int] = None, min_nodes: Optional[int] = None) -> np.ndarray:
+    """labels as connected_components_reference gives them -> the roots of the kept components, ascending (int64).
+
+    largest=k keeps the k components with the most nodes, ties to the smaller root; min_nodes=m those with at least m nodes; both
+    the intersection, neither all."""
+    if largest is not None and int(largest) < 1:
+        raise ValueError(f"select_components: largest must be at least 1; got {largest}")
+    if min_nodes is not None and int(min_nodes) < 1:
+        raise ValueError(f"select_components: min_nodes must be at least 1; got {min_nodes}")
+    labels = np.asarray(labels)
+    roots, nodes = np.unique(labels[labels >= 0], return_counts=True)
+    keep = np.ones(len(roots), dtype=bool)
+    if largest is not None:
+        keep[np.lexsort((roots, -nodes))[int(largest):]] = False          # by (-nodes, root)
+    if min_nodes is not None:
+        keep &= nodes >= int(min_nodes)
+    return roots[keep].astype(np.int64)
+
+
+def filter_components_reference(volume, level: float, largest: Optional[int] = None, min_nodes: Optional[int] = None) -> np.ndarray:
+    """The volume with every inside node of a component that select_components does not keep set to float32(level) -- outside, and
+    no crossing on an edge to another outside node; everything else bit for bit.  A removed node has no kept inside node on any of its
+    Kuhn edges, so the isosurface of the result is the isosurface of the volume without the removed components' vertices and faces."""
+    f = _volume(volume, "filter_components_reference")
+    labels = connected_components_reference(f, level)
+    kept = select_components(labels, largest, min_nodes)
+    out = f.copy()
+    out[(labels >= 0) & ~np.isin(labels, kept)] = np.float32(level)
+    return out
+
+
+def node_gradient_reference(field, spacing: Sequence[float]) -> np.ndarray:
+    """field [Gz, Gy, Gx] -> [3, Gz, Gy, Gx] float32, the gradient (x, y, z) at the nodes as written: central differences
+    (f[i + 1] - f[i - 1]) / (2 s) in the interior, one-sided (f[1] - f[0]) / (1 s) and (f[last] - f[last - 1]) / (1 s) at the borders."""
+    f = _volume(field, "node_gradient_reference")
+    spacing = np.asarray(spacing, dtype=np.float32)
+    out = np.empty((3,) + f.shape, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for a in range(3):          # axis a = x, y, z is array axis 2 - a
+            m = np.moveaxis(f, 2 - a, 0)
+            g = np.moveaxis(out[a], 2 - a, 0)
+            g[1:-1] = (m[2:] - m[:-2]) / (np.float32(2) * spacing[a])
+            g[0] = (m[1] - m[0]) / (np.float32(1) * spacing[a])
+            g[-1] = (m[-1] - m[-2]) / (np.float32(1) * spacing[a])
+    return out
+
+
+def vertex_normals_reference(volume, level: float, spacing: Sequence[float] = (1.0, 1.0, 1.0), gradient_of=None) -> np.ndarray:
+    """-> [V, 3] float32 unit normals in the vertex order of marching_tetrahedra_reference(volume, level, ., spacing): the
+    specification of the isosurface's vertex normals on the CPU, float32 arithmetic as written.
+
+    The vertex on the edge (lo, hi) with the isosurface's t = (level - f_lo) / (f_hi - f_lo), f from `volume`, takes the gradient
+    g = g_lo + t (g_hi - g_lo) of `gradient_of` (default: the volume; node_gradient_reference), n2 = (gx gx + gy gy) + gz gz and
+    n = (-g) / sqrt(n2): the density falls toward the outside.  A vertex with a component that is not finite gets (+0, +0, +0)."""
+    f = _volume(volume, "vertex_normals_reference")
+    field = f if gradient_of is None else _volume(gradient_of, "vertex_normals_reference")
+    if field.shape != f.shape:
+        raise ValueError(f"vertex_normals_reference: gradient_of {field.shape} is not the volume's shape {f.shape}")
+    gz, gy, gx = f.shape
+    level = np.float32(level)
+    grad = node_gradient_reference(field, spacing)
+    with np.errstate(invalid="ignore"):
+        inside = f > level
+    keys, rows = [], []
+    for t, (dx, dy, dz) in enumerate(EDGE_TYPES):
+        lo = (slice(0, gz - dz), slice(0, gy - dy), slice(0, gx - dx))
+        hi = (slice(dz, gz), slice(dy, gy), slice(dx, gx))
+        z, y, x = np.nonzero(inside[lo] != inside[hi])
+        with np.errstate(all="ignore"):
+            s = (level - f[z, y, x]) / (f[z + dz, y + dy, x + dx] - f[z, y, x])
+            g_lo, g_hi = grad[:, z, y, x], grad[:, z + dz, y + dy, x + dx]
+            g = g_lo + s * (g_hi - g_lo)
+            n2 = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]
+            rows.append(((-g) / np.sqrt(n2)).T.astype(np.float32))
+        keys.append(((z * gy + y) * gx + x) * 7 + t)
+    normals = np.concatenate(rows)[np.argsort(np.concatenate(keys), kind="stable")].reshape(-1, 3)
+    normals[~np.isfinite(normals).all(axis=1)] = 0.0
+    return normals
+
+
 def default_level(pointnerf) -> float:
     """ln 2 / (2 cube_scale / (depth_resolution - 1)): the density at which one depth step of an axis-parallel ray through the box
     is half opaque."""
@@ -126,20 +254,35 @@ def default_level(pointnerf) -> float:
 
 @torch.no_grad()
 def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolution=128, level: Optional[float] = None, colors: bool = True,
-                 bound: Optional[float] = None, mlp_dtype=None, view_dir: Optional[torch.Tensor] = None) -> List[Dict[str, torch.Tensor]]:
+                 bound: Optional[float] = None, mlp_dtype=None, view_dir: Optional[torch.Tensor] = None, components: Optional[int] = None,
+                 min_component_nodes: Optional[int] = None, normals: bool = False) -> List[Dict[str, torch.Tensor]]:
     """coords [B, N, 3], feats [B, N, F] on the GPU -> per cloud {"vertices" [V, 3] fp32, "faces" [F, 3] int32, "colors" [V, 3] fp32
     in [0, 1] (with colors=True)}, all on the GPU.
 
     The density on PointNeRF.density_grid(resolution, bound), its isosurface at `level` (npcd.hip.isosurface), and the field's
     colour at the vertices (PointNeRF.query_field; `view_dir` [3] for a field with view directions, `mlp_dtype` as for render).
     level=None takes default_level(pointnerf).  Nobody has looked at this default on trained weights: it is a statement about one
-    depth step of the renderer, not about where a trained car's surface lies -- choose the level by eye."""
+    depth step of the renderer, not about where a trained car's surface lies -- choose the level by eye.
+
+    components=k keeps the k largest connected components of the density above the level, min_component_nodes=m those of at least m
+    lattice nodes (npcd.hip.components.filter_components, between the density and the isosurface); the mesh then also holds
+    "component_nodes", the kept components' node counts in descending order (int64, on the GPU).  normals=True adds "normals"
+    [V, 3] fp32, the unit normals of vertex_normals_reference from the gradient of the unfiltered density."""
     from ..hip.isosurface import isosurface
     sigma, origin, spacing = pointnerf.density_grid(coords, feats, resolution=resolution, bound=bound, mlp_dtype=mlp_dtype)
-    meshes = isosurface(sigma, default_level(pointnerf) if level is None else float(level), origin, spacing)
+    level = default_level(pointnerf) if level is None else float(level)
+    filtered, kept_nodes = sigma, None
+    if components is not None or min_component_nodes is not None:
+        from ..hip.components import filter_components_counted
+        filtered, kept_nodes = filter_components_counted(sigma, level, largest=components, min_nodes=min_component_nodes)
+    meshes = isosurface(filtered, level, origin, spacing, normals=normals, gradient_of=sigma if normals else None)
     out = []
-    for b, (vertices, faces) in enumerate(meshes):
+    for b, (vertices, faces, *rest) in enumerate(meshes):
         mesh = {"vertices": vertices, "faces": faces}
+        if normals:
+            mesh["normals"] = rest[0]
+        if kept_nodes is not None:
+            mesh["component_nodes"] = kept_nodes[b]
         if colors:
             if vertices.shape[0]:
                 mesh["colors"] = pointnerf.query_field(coords[b:b + 1], feats[b:b + 1], vertices[None], mlp_dtype=mlp_dtype,
@@ -158,14 +301,22 @@ def colors_to_uint8(colors) -> np.ndarray:
     return np.rint(np.clip(c.astype(np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
 
 
-def write_ply(path, vertices, faces, colors=None) -> None:
-    """Binary little-endian PLY, written on the host: float32 x y z, optional uchar red green blue, faces as `uchar int` lists."""
+def write_ply(path, vertices, faces, colors=None, normals=None) -> None:
+    """Binary little-endian PLY, written on the host: float32 x y z, optional float32 nx ny nz, optional uchar red green blue, faces
+    as `uchar int` lists."""
     v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
     f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
     v = np.asarray(v, dtype="<f4").reshape(-1, 3)
     f = np.asarray(f, dtype="<i4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", "property float x", "property float y", "property float z"]
+    if normals is not None:
+        n = normals.detach().cpu().numpy() if isinstance(normals, torch.Tensor) else np.asarray(normals)
+        n = np.asarray(n, dtype="<f4").reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError(f"write_ply: {len(v)} vertices and {len(n)} normals")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         c = colors_to_uint8(colors).reshape(-1, 3)
         if len(c) != len(v):
@@ -175,6 +326,8 @@ def write_ply(path, vertices, faces, colors=None) -> None:
     header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
     vert = np.empty(len(v), dtype=fields)
     vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if colors is not None:
         vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
     face = np.empty(len(f), dtype=[("n", "u1"), ("v", "<i4", (3,))])

@@ -159,6 +159,9 @@ SIGNATURES = {
     "npcd_isosurface_ws_bytes": (c_int64, [c_int] * 4),
     "npcd_isosurface_count": (c_int, [_P] + [c_int] * 4 + [c_float, _P, _P, _P]),
     "npcd_isosurface_emit": (c_int, [_P] + [c_int] * 4 + [c_float, POINTER(c_float), POINTER(c_float)] + [_P] * 5 + [_P]),
+    "npcd_components_ws_bytes": (c_int64, [c_int] * 4),
+    "npcd_components_label": (c_int, [_P] + [c_int] * 4 + [c_float, _P, _P, _P, _P]),
+    "npcd_isosurface_normals": (c_int, [_P, _P] + [c_int] * 4 + [c_float, POINTER(c_float)] + [_P] * 3 + [_P]),
 }
 
 _lib = None
