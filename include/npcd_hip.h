@@ -896,6 +896,37 @@ int npcd_components_label(const float* vol, int B, int gz, int gy, int gx, float
 int npcd_isosurface_normals(const float* vol, const float* field, int B, int gz, int gy, int gx, float level, const float* spacing_host,
                             const void* ws, const int64_t* vert_offsets, float* normals, void* stream);
 
+/* ---- points on mesh surfaces, uniform by area (added within ABI 10; csrc/surface.hip, csrc/surface.h).  A batch of B
+ * meshes is packed: vertices [V_total, 3] fp32 and faces [F_total, 3] int32 concatenated, a face's indices local to its mesh, and
+ * vert_offsets / face_offsets [B + 1] int32 ON THE DEVICE (ascending, first 0, last the total; a member whose pair of offsets does
+ * not ascend inside [0, total] counts as empty).  The specification is restated by face_weights_reference and
+ * surface_sample_reference of npcd/eval/mesh.py, and the kernels are held to them bit for bit.
+ *   npcd_surface_prepare: per face d = |e1 x e2| (fp32 as written; +0 where not finite or an index lies outside [0, V), through which
+ *       nothing is read), per mesh d_max by an integer maximum on the bits, k = 31 - floor(log2 d_max), the integer weights
+ *       w = floor(float64(d) 2^k) < 2^32, their inclusive sums inside every tile of 256 faces (kSurfTile of csrc/surface.h) and the
+ *       inclusive sums of the tile totals; area [B] float64 = 0.5 float64(W) 2^-k, 0 for a mesh without faces or measure.  ws:
+ *       npcd_surface_ws_bytes(B, F_total), 8-byte aligned; contents irrelevant before, the input of npcd_surface_sample after.  One
+ *       4 B-byte memset and three launches; integer sums and maxima only: the same bits on every run.
+ *   npcd_surface_sample: u [B, S, 3] fp32 -> points [B, S, 3]; faces_out [B, S] int32 or NULL (the face of every sample, local to its
+ *       mesh); normals_mode 0: none (normals_out NULL), 1: the face's n / d (vertex_normals NULL), 2: the vertex_normals [V_total, 3]
+ *       mixed with the sample's barycentric weights and normalised, (+0, +0, +0) where a component is not finite; normals_out [B, S, 3];
+ *       attributes [V_total, C] fp32 mixed the same way into attributes_out [B, S, C], 1 <= C <= 16, or C = 0 and both NULL.
+ *       k0 = clamp(floor(u0 2^24), 0, 2^24 - 1), r = floor(k0 W / 2^24) exactly, the face the smallest i whose inclusive sum exceeds
+ *       r; s = sqrt(u1), b = (1 - s, s (1 - u2), s u2), every row (b0 x0 + b1 x1) + b2 x2.  A mesh with W = 0 gives face -1 and +0
+ *       rows.  One launch; the tile sums of a mesh of up to 4,096 tiles (kSurfLdsTiles) are searched in LDS, those of a
+ *       larger one in global memory.  vertices, faces and the offsets are those npcd_surface_prepare saw.
+ * No host synchronisation, no allocation, no workgroup that waits on another.  NPCD_ERR_ARG for B < 1, S < 1, a negative total or C,
+ * a NULL pointer (or one that the mode does not take), a misaligned ws or area; NPCD_ERR_UNSUPPORTED for V_total or F_total >= 2^31,
+ * C > 16, B > 65,535 in npcd_surface_sample and B S max(3, C) >= 2^31 (the workspace query returns both too).  Nothing is launched in
+ * either case. */
+int64_t npcd_surface_ws_bytes(int B, int64_t F_total);
+int npcd_surface_prepare(const float* vertices, const int32_t* faces, const int32_t* vert_offsets, const int32_t* face_offsets, int B,
+                         int64_t V_total, int64_t F_total, void* ws, double* area, void* stream);
+int npcd_surface_sample(const float* vertices, const int32_t* faces, const int32_t* vert_offsets, const int32_t* face_offsets, int B,
+                        int64_t V_total, int64_t F_total, const void* ws, const float* u, int S, float* points, int32_t* faces_out,
+                        int normals_mode, const float* vertex_normals, float* normals_out, const float* attributes, int C,
+                        float* attributes_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,10 @@ SOURCES = {
     "isosurface_normals.hip": ["-ffp-contract=off"],
     # the labelling is integer work; its one float operation is the isosurface's own inside test f > level
     "components.hip": ["-ffp-contract=off"],
+    # surface sampling picks a face from integer weights floor(float64(d) 2^k) and places the point with (b0 v0 + b1 v1) + b2 v2: the
+    # face measure d, the barycentric expressions and the normalisations are the bits of their numpy restatement only as written,
+    # a fused multiply-add in the cross product would already move a weight
+    "surface.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

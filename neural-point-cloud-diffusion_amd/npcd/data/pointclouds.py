@@ -16,6 +16,23 @@ def cached_name(num_points: int) -> str:
     return f"pointcloud3_{num_points}.npz"
 
 
+def write_raw_pointcloud(directory: str, points, normals) -> str:
+    """Write `<directory>/pointcloud3.npz` with the raw surface cloud of one object: `points` [P, 3] and `normals` [P, 3] as float32,
+    the two keys load_pointclouds reads -- e.g. what npcd.hip.surface.sample_surface draws from an extracted mesh.  -> the path."""
+    arrays = []
+    for name, a in (("points", points), ("normals", normals)):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"write_raw_pointcloud: {name} must be [P, 3]; got {a.shape}")
+        arrays.append(np.ascontiguousarray(a, dtype=np.float32))
+    if len(arrays[0]) != len(arrays[1]):
+        raise ValueError(f"write_raw_pointcloud: {len(arrays[0])} points and {len(arrays[1])} normals")
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, RAW_NAME)
+    np.savez(path, points=arrays[0], normals=arrays[1])
+    return path
+
+
 def _default_sampler():
     from npcd.hip.fps import sample_farthest_points
     return sample_farthest_points

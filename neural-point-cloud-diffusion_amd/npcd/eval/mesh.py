@@ -3,9 +3,11 @@ the GPU (npcd.hip.isosurface, csrc/isosurface.hip) and the field's colour at the
 writer.  `marching_tetrahedra_reference` restates the surface's specification in numpy; the kernel is held to it
 bit for bit (tests/test_gpu_isosurface.py), and it is held to geometry (tests/test_isosurface_cpu.py).  What finishes a mesh is
 specified the same way: `connected_components_reference`, `select_components` and `filter_components_reference`
-for dropping floaters from the volume, `vertex_normals_reference` for the normals.
+for dropping floaters from the volume, `vertex_normals_reference` for the normals.  Reading a mesh back as a cloud is specified the
+same way: `face_weights_reference` and `surface_sample_reference` restate npcd.hip.surface, and
+`sample_mesh_clouds` draws the clouds that the shape metrics take.
 
-This module imports without a GPU; only extract_mesh needs one."""
+This module imports without a GPU; only extract_mesh and sample_mesh_clouds need one."""
 import itertools
 import math
 from typing import Dict, List, Optional, Sequence
@@ -243,6 +245,131 @@ def vertex_normals_reference(volume, level: float, spacing: Sequence[float] = (1
     normals = np.concatenate(rows)[np.argsort(np.concatenate(keys), kind="stable")].reshape(-1, 3)
     normals[~np.isfinite(normals).all(axis=1)] = 0.0
     return normals
+
+
+def _mesh_arrays(vertices, faces, who: str):
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32)).reshape(-1, 3)
+    f = np.ascontiguousarray(np.asarray(faces)).reshape(-1, 3)
+    if f.size and not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"{who}: faces must be integers; got {f.dtype}")
+    return v, f.astype(np.int64)
+
+
+def face_weights_reference(vertices, faces):
+    """vertices [V, 3], faces [F, 3] -> (weights uint64 [F], k, d float32 [F], n float32 [F, 3]): the integer face weights of the
+    surface sampler on the CPU, float32 arithmetic as written.
+
+    e1 = v1 - v0, e2 = v2 - v0, n = e1 x e2, d = sqrt((nx nx + ny ny) + nz nz) -- twice the area; d = +0 where it is not finite or
+    an index lies outside [0, V).  d_max the largest d, k = 31 - floor(log2 d_max) from the exponent of float64(d_max), and
+    w = floor(float64(d) 2^k): the scaling is exact, d_max maps into [2^31, 2^32), a face below 2^-31 of the largest weighs 0.  Integers,
+    so every order of summation gives the same prefix sums.  k is None for a mesh without measure (all weights 0)."""
+    v, f = _mesh_arrays(vertices, faces, "face_weights_reference")
+    valid = ((f >= 0) & (f < len(v))).all(axis=1)
+    safe = np.where(valid[:, None], f, 0) if len(v) else np.zeros_like(f)
+    corners = v[safe] if len(v) else np.zeros((len(f), 3, 3), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        e1, e2 = corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0]
+        n = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                      e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1).astype(np.float32)
+        d = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]).astype(np.float32)
+    d = np.where(valid & np.isfinite(d), d, np.float32(0.0)).astype(np.float32)
+    d_max = float(d.view(np.uint32).max().view(np.float32)) if len(d) else 0.0          # the integer maximum of the bits: d >= +0
+    if d_max == 0.0:
+        return np.zeros(len(f), dtype=np.uint64), None, d, n
+    k = 31 - (math.frexp(d_max)[1] - 1)          # frexp: d_max = m 2^e with m in [0.5, 1), exact for denormals too
+    weights = np.floor(np.ldexp(d.astype(np.float64), k)).astype(np.uint64)
+    return weights, k, d, n
+
+
+def surface_sample_reference(vertices, faces, u, normals=None, attributes=None) -> Dict[str, np.ndarray]:
+    """One mesh (vertices [V, 3], faces [F, 3]) and uniform draws u [S, 3] -> {"points" [S, 3] float32, "face" [S] int32, "area"
+    float64, and "normals" [S, 3] / "attributes" [S, C] float32 where asked for}: the specification of the surface sampler on the
+    CPU, float32 arithmetic as written.
+
+    With the weights w of face_weights_reference, C their inclusive sums (integers) and W the last: k0 = clamp(floor(u0 2^24), 0,
+    2^24 - 1) (NaN: 0), r = floor(k0 W / 2^24) in exact integer arithmetic, the face the smallest i with C_i > r -- a face of weight 0
+    is never chosen.  s = sqrt(u1), b = (1 - s, s (1 - u2), s u2), p = (b0 v0 + b1 v1) + b2 v2.  normals="face": n / d of the face;
+    normals [V, 3]: g = (b0 g0 + b1 g1) + b2 g2, g / sqrt((gx gx + gy gy) + gz gz), (+0, +0, +0) where a component is not finite;
+    attributes [V, C]: the same three-term expression.  area = 0.5 float64(W) 2^-k.  A mesh without faces or measure: area 0, face -1
+    and +0 in every other row."""
+    v, f = _mesh_arrays(vertices, faces, "surface_sample_reference")
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float32))
+    if u.ndim != 2 or u.shape[1] != 3:
+        raise ValueError(f"surface_sample_reference: u must be [S, 3]; got {u.shape}")
+    S = len(u)
+    face_mode = isinstance(normals, str)
+    if face_mode and normals != "face":
+        raise ValueError(f"surface_sample_reference: normals is \"face\" or a [V, 3] array; got {normals!r}")
+    vn = None if normals is None or face_mode else np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+    at = None if attributes is None else np.asarray(attributes, dtype=np.float32)
+    if vn is not None and len(vn) != len(v):
+        raise ValueError(f"surface_sample_reference: {len(v)} vertices and {len(vn)} normals")
+    if at is not None and (at.ndim != 2 or len(at) != len(v)):
+        raise ValueError(f"surface_sample_reference: attributes must be [{len(v)}, C]; got {at.shape}")
+    weights, k, d, n = face_weights_reference(v, f)
+    out = {"points": np.zeros((S, 3), dtype=np.float32), "face": np.full(S, -1, dtype=np.int32), "area": np.float64(0.0)}
+    if normals is not None:
+        out["normals"] = np.zeros((S, 3), dtype=np.float32)
+    if at is not None:
+        out["attributes"] = np.zeros((S, at.shape[1]), dtype=np.float32)
+    if k is None:
+        return out
+    sums = np.cumsum(weights, dtype=np.uint64)
+    W = int(sums[-1])
+    out["area"] = np.float64(math.ldexp(0.5 * float(W), -k))          # float(W): the nearest float64, ties to even
+    with np.errstate(invalid="ignore"):
+        t = np.floor(u[:, 0] * np.float32(16777216.0))
+    k0 = np.where(t > 0, np.minimum(t, np.float32(16777215.0)), np.float32(0.0)).astype(np.int64)          # NaN > 0 is false
+    r = np.array([(int(q) * W) >> 24 for q in k0], dtype=np.uint64)
+    face = np.searchsorted(sums, r, side="right")
+    assert (face < len(f)).all() and (weights[face] > 0).all()
+    out["face"] = face.astype(np.int32)
+
+    def mix(rows):          # rows [S, 3 corners, C] float32
+        return ((b0[:, None] * rows[:, 0] + b1[:, None] * rows[:, 1]) + b2[:, None] * rows[:, 2]).astype(np.float32)
+    with np.errstate(all="ignore"):
+        s = np.sqrt(u[:, 1]).astype(np.float32)
+        one = np.float32(1.0)
+        b0, b1, b2 = one - s, s * (one - u[:, 2]), s * u[:, 2]
+        idx = f[face]
+        out["points"] = mix(v[idx])
+        if face_mode:
+            out["normals"] = (n[face] / d[face][:, None]).astype(np.float32)
+        elif vn is not None:
+            g = mix(vn[idx])
+            unit = (g / np.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])[:, None]).astype(np.float32)
+            unit[~np.isfinite(unit).all(axis=1)] = 0.0
+            out["normals"] = unit
+        if at is not None:
+            out["attributes"] = mix(at[idx])
+    return out
+
+
+def _mesh_parts(mesh):
+    """(vertices, faces, normals or None) of a mesh as isosurface (a tuple) or extract_mesh (a dict) returns it."""
+    if isinstance(mesh, dict):
+        return mesh["vertices"], mesh["faces"], mesh.get("normals")
+    return mesh[0], mesh[1], (mesh[2] if len(mesh) > 2 else None)
+
+
+@torch.no_grad()
+def sample_mesh_clouds(meshes, num_points: int, generator: Optional[torch.Generator] = None, normals: bool = False, sampler=None):
+    """Meshes on the GPU, as isosurface or extract_mesh return them -> clouds [B, num_points, 3] fp32 drawn uniformly by area from
+    their surfaces (npcd.hip.surface.sample_surface): what shape_metrics takes.  normals=True -> (clouds, normals
+    [B, num_points, 3]), the meshes' vertex normals (extract_mesh(..., normals=True)) interpolated at the points.  A mesh without
+    surface gives a cloud of zeros.  `sampler` stands in for sample_surface (tests of the host logic)."""
+    if sampler is None:
+        from ..hip.surface import sample_surface as sampler
+    if isinstance(meshes, dict) or (len(meshes) and isinstance(meshes[0], torch.Tensor)):
+        meshes = [meshes]
+    parts = [_mesh_parts(m) for m in meshes]
+    vertex_normals = None
+    if normals:
+        if any(p[2] is None for p in parts):
+            raise ValueError("sample_mesh_clouds: normals=True needs meshes with vertex normals (extract_mesh(..., normals=True))")
+        vertex_normals = [p[2] for p in parts]
+    got = sampler([(p[0], p[1]) for p in parts], int(num_points), generator=generator, normals=vertex_normals)
+    return (got[0], got[2]) if normals else got[0]
 
 
 def default_level(pointnerf) -> float:

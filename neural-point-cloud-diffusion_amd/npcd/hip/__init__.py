@@ -162,6 +162,9 @@ SIGNATURES = {
     "npcd_components_ws_bytes": (c_int64, [c_int] * 4),
     "npcd_components_label": (c_int, [_P] + [c_int] * 4 + [c_float, _P, _P, _P, _P]),
     "npcd_isosurface_normals": (c_int, [_P, _P] + [c_int] * 4 + [c_float, POINTER(c_float)] + [_P] * 3 + [_P]),
+    "npcd_surface_ws_bytes": (c_int64, [c_int, c_int64]),
+    "npcd_surface_prepare": (c_int, [_P] * 4 + [c_int, c_int64, c_int64, _P, _P, _P]),
+    "npcd_surface_sample": (c_int, [_P] * 4 + [c_int, c_int64, c_int64, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, c_int, _P, _P]),
 }
 
 _lib = None
