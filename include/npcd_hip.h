@@ -927,6 +927,41 @@ int npcd_surface_sample(const float* vertices, const int32_t* faces, const int32
                         int normals_mode, const float* vertex_normals, float* normals_out, const float* attributes, int C,
                         float* attributes_out, void* stream);
 
+/* ---- vertex clustering of one mesh (added within ABI 10; csrc/simplify.hip, csrc/simplify.h).  vertices [V, 3] fp32,
+ * faces [F, 3] int32, attributes [V, C] fp32 (0 <= C <= 16, NULL with C = 0) on the device; the grid on the HOST: origin_host [3] and
+ * cell_host [3] float64 (finite, cell > 0), dims_host [3] int (each >= 1, the product at most 2^30).  The specification is restated
+ * by simplify_reference of npcd/eval/mesh.py, and the kernels are held to it bit for bit.  The four calls of one mesh take the same
+ * V, F, C and dims and one workspace of npcd_simplify_ws_bytes(V, F, C, dims_host) bytes, 8-byte aligned, contents irrelevant before.
+ *   npcd_simplify_cluster: per vertex u = (float64(v) - origin) / cell, lost (-1) if not finite, c = clamp(floor(u), 0, dims - 1),
+ *       key = (cz dims_y + cy) dims_x + cx, r = clamp(floor((u - c) 2^32), 0, 2^32 - 1); vertex_cluster [V] int32 = the rank of the
+ *       vertex's key among the occupied cells; counts[0] (int64 [2] on the device) = V', the occupied cells; in ws the integer sums of
+ *       r, of 1 and of the attributes q = rint(float64(a) 2^(30 - e)), e the exponent of the largest finite |a| of the call (a value
+ *       that is not finite counts as 0).  One memset and four launches; V >= 1.
+ *   npcd_simplify_faces: per face the clusters of its corners (in ws) and the sort keys of its sorted triple: key_hi NULL: one key
+ *       a 2^42 + b 2^21 + c in key_lo [F] int64 (refused with NPCD_ERR_ARG when min(V, cells) > 2^21), else key_hi [F] = a and
+ *       key_lo = b 2^32 + c; INT64_MAX in both for a face that goes: an index outside [0, V) (nothing is read through it), a lost
+ *       corner, two corners in one cluster.  One launch; F >= 1.
+ *   npcd_simplify_unique: order [F] int64 = the faces in a STABLE ascending order of those keys (by key_lo, then stably by key_hi).  A
+ *       face stays if it is valid and the first of its run of equal sorted triples: the lowest input index.  counts[1] = F'.  An
+ *       entry of order outside [0, F) is not followed.  One memset and three launches.
+ *   npcd_simplify_emit: V_out = V' and F_out = F' as read from counts.  vertices_out [V', 3] fp32 = origin + cell (c + (float64(S) /
+ *       float64(n)) 2^-32) in float64 as written; attributes_out [V', C] = fp32 of (float64(sum) / float64(n)) 2^(e - 30); faces_out
+ *       [F', 3] the kept faces on the new vertices, corner order and input order kept, face_source [F'] int32 their input indices
+ *       (both NULL with F_out = 0).  Two launches.  V_out in [1, min(V, cells)], F_out in [0, F].
+ * Integer ORs, maxima and sums only: the same bits on every run.  No host synchronisation, no allocation, no workgroup that waits on
+ * another.  NPCD_ERR_ARG for a negative size, V < 1 or F < 1 where stated, a dims entry below 1, an origin or cell that is not
+ * finite or a cell <= 0, a NULL pointer (or one that the sizes do not take) or a misaligned one; NPCD_ERR_UNSUPPORTED for C > 16, V or
+ * F >= 2^31 and more than 2^30 cells (the workspace query returns both too).  Nothing is launched in either case. */
+int64_t npcd_simplify_ws_bytes(int64_t V, int64_t F, int C, const int* dims_host);
+int npcd_simplify_cluster(const float* vertices, int64_t V, int64_t F, const float* attributes, int C, const double* origin_host,
+                          const double* cell_host, const int* dims_host, void* ws, int32_t* vertex_cluster, int64_t* counts, void* stream);
+int npcd_simplify_faces(const int32_t* faces, int64_t V, int64_t F, int C, const int* dims_host, const int32_t* vertex_cluster, void* ws,
+                        int64_t* key_hi, int64_t* key_lo, void* stream);
+int npcd_simplify_unique(const int64_t* order, int64_t V, int64_t F, int C, const int* dims_host, void* ws, int64_t* counts, void* stream);
+int npcd_simplify_emit(int64_t V, int64_t F, int C, const double* origin_host, const double* cell_host, const int* dims_host,
+                       const void* ws, int64_t V_out, int64_t F_out, float* vertices_out, float* attributes_out, int32_t* faces_out,
+                       int32_t* face_source, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,10 @@ SOURCES = {
     # face measure d, the barycentric expressions and the normalisations are the bits of their numpy restatement only as written,
     # a fused multiply-add in the cross product would already move a weight
     "surface.hip": ["-ffp-contract=off"],
+    # vertex clustering places a vertex in its cell and a cluster's representative by float64 expressions -- (u - c) 2^32 and
+    # origin + cell (c + (S / n) 2^-32) -- that are the bits of their numpy restatement only as written: a fused multiply-add would
+    # skip the rounding of a product
+    "simplify.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

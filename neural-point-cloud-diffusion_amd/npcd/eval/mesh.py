@@ -5,7 +5,8 @@ bit for bit (tests/test_gpu_isosurface.py), and it is held to geometry (tests/te
 specified the same way: `connected_components_reference`, `select_components` and `filter_components_reference`
 for dropping floaters from the volume, `vertex_normals_reference` for the normals.  Reading a mesh back as a cloud is specified the
 same way: `face_weights_reference` and `surface_sample_reference` restate npcd.hip.surface, and
-`sample_mesh_clouds` draws the clouds that the shape metrics take.
+`sample_mesh_clouds` draws the clouds that the shape metrics take.  Bringing a mesh down to a usable triangle count likewise
+(DESIGN.md 5.16): `simplify_reference` restates npcd.hip.simplify, exact vertex clustering, and extract_mesh(simplify=k) applies it.
 
 This module imports without a GPU; only extract_mesh and sample_mesh_clouds need one."""
 import itertools
@@ -345,6 +346,114 @@ def surface_sample_reference(vertices, faces, u, normals=None, attributes=None) 
     return out
 
 
+MAX_CLUSTER_CELLS = 2 ** 30
+
+
+def clustering_grid(cell, origin=None, dims=None, lower=None, upper=None):
+    """The grid of simplify_reference / npcd.hip.simplify.simplify_mesh as host values -> (origin [3] float64, cell [3] float64,
+    dims [3] int).  `cell`: a float or three (x, y, z), finite and positive.  origin=None takes `lower`, the smallest coordinates of
+    the finite vertices; dims=None takes floor((upper - origin) / cell) + 1 per axis in float64, at least 1 -- the cells that reach the
+    largest coordinates.  Without a finite vertex (lower and upper None) the origin is 0 and the grid one cell."""
+    cell = np.array(np.broadcast_to(np.asarray(cell, dtype=np.float64), (3,)))
+    if not (np.isfinite(cell).all() and (cell > 0).all()):
+        raise ValueError(f"clustering_grid: cell must be finite and positive; got {cell.tolist()}")
+    if origin is None:
+        origin = np.zeros(3) if lower is None else np.asarray(lower, dtype=np.float64)
+    origin = np.array(np.broadcast_to(np.asarray(origin, dtype=np.float64), (3,)))
+    if not np.isfinite(origin).all():
+        raise ValueError(f"clustering_grid: origin must be finite; got {origin.tolist()}")
+    if dims is None:
+        if upper is None:
+            dims = [1, 1, 1]
+        else:
+            reach = np.floor((np.asarray(upper, dtype=np.float64) - origin) / cell)
+            dims = [int(min(max(d, 0.0), float(2 ** 31 - 2))) + 1 for d in reach]
+    dims = [int(d) for d in dims]
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError(f"clustering_grid: dims must be three positive integers; got {dims}")
+    if dims[0] * dims[1] * dims[2] > MAX_CLUSTER_CELLS:
+        raise ValueError(f"clustering_grid: {dims[0]} x {dims[1]} x {dims[2]} = {dims[0] * dims[1] * dims[2]} cells; at most 2^30 = "
+                         f"{MAX_CLUSTER_CELLS} -- take a larger cell")
+    return origin, cell, dims
+
+
+def attribute_means_reference(attributes, cluster, num_clusters: int) -> np.ndarray:
+    """attributes [V, C], cluster [V] (-1: none) -> the cluster means [num_clusters, C] as FLOAT64, before simplify_reference rounds
+    them to float32.
+
+    A = the largest finite |a| of the whole array, e = floor(log2 A), the quantum 2^(e - 30): q = rint(float64(a) 2^(30 - e)), an
+    integer of at most 2^31 (a value that is not finite counts as 0; the product is exact), the sums of q over a cluster as signed
+    64-bit integers, and the mean (float64(sum) / float64(n)) 2^(e - 30).  Every q is within half a quantum of its value, so the mean
+    is within A 2^-31 of the exact one, and the one float64 division adds A 2^-53: inside A 2^-29."""
+    a = np.ascontiguousarray(np.asarray(attributes, dtype=np.float32))
+    cluster = np.asarray(cluster)
+    out = np.zeros((num_clusters, a.shape[1]), dtype=np.float64)
+    finite = np.isfinite(a)
+    bits = np.where(finite, np.abs(a), np.float32(0.0)).astype(np.float32).view(np.uint32)
+    top = float(bits.max().view(np.float32)) if a.size else 0.0          # the integer maximum of the bits: |a| >= +0
+    if top == 0.0 or num_clusters == 0:
+        return out
+    shift = 30 - (math.frexp(top)[1] - 1)
+    q = np.rint(np.ldexp(np.where(finite, a, np.float32(0.0)).astype(np.float64), shift)).astype(np.int64)
+    member = cluster >= 0
+    sums = np.zeros((num_clusters, a.shape[1]), dtype=np.int64)
+    np.add.at(sums, cluster[member], q[member])
+    n = np.bincount(cluster[member], minlength=num_clusters).astype(np.float64)
+    return np.ldexp(sums.astype(np.float64) / n[:, None], -shift)
+
+
+def simplify_reference(vertices, faces, cell, origin=None, dims=None, attributes=None) -> Dict[str, np.ndarray]:
+    """One mesh (vertices [V, 3], faces [F, 3]) -> {"vertices" [V', 3] float32, "faces" [F', 3] int32, "vertex_cluster" [V] int32,
+    "face_source" [F'] int32, and "attributes" [V', C] float32 where given}: the specification of vertex clustering (Rossignac and
+    Borrel) on the CPU, float64 and integers.  The grid as clustering_grid makes it from cell, origin and dims.
+
+    u = (float64(v) - origin) / cell per axis; a vertex with a u that is not finite is lost: cluster -1.  c = clamp(floor(u), 0,
+    dims - 1), key = (cz dims_y + cy) dims_x + cx, and the cluster of a vertex is the rank of its key among the occupied cells, V' of
+    them.  r = clamp(floor((u - c) 2^32), 0, 2^32 - 1), S the sum of r over the cluster and n its size, both integers: the
+    representative is float32(origin + cell (c + (float64(S) / float64(n)) 2^-32)).  Attributes: attribute_means_reference, rounded
+    to float32.  A face maps to its corners' clusters, corner order kept; it goes if an index lies outside [0, V), a corner is lost or
+    two corners share a cluster, and among the others with the same SET of three clusters only the lowest input index stays.  The
+    kept faces keep the input order; face_source holds their input indices.  The result may be non-manifold: clustering can pinch."""
+    v, f = _mesh_arrays(vertices, faces, "simplify_reference")
+    at = None if attributes is None else np.ascontiguousarray(np.asarray(attributes, dtype=np.float32))
+    if at is not None and (at.ndim != 2 or len(at) != len(v) or not 1 <= at.shape[1] <= 16):
+        raise ValueError(f"simplify_reference: attributes must be [{len(v)}, C] with 1 <= C <= 16; got {at.shape}")
+    whole = np.isfinite(v).all(axis=1)
+    lower, upper = (v[whole].min(axis=0), v[whole].max(axis=0)) if whole.any() else (None, None)
+    origin, cell, dims = clustering_grid(cell, origin, dims, lower, upper)
+    with np.errstate(all="ignore"):
+        u = (v.astype(np.float64) - origin) / cell
+        lost = ~np.isfinite(u).all(axis=1)
+        top = np.asarray(dims, dtype=np.float64) - 1.0
+        c = np.where(np.isfinite(u), np.minimum(np.maximum(np.floor(u), 0.0), top), 0.0)
+        r = np.minimum(np.maximum(np.floor((u - c) * 4294967296.0), 0.0), 4294967295.0)
+    r = np.where(np.isfinite(r), r, 0.0).astype(np.uint64)
+    ci = c.astype(np.int64)
+    key = np.where(lost, -1, (ci[:, 2] * dims[1] + ci[:, 1]) * dims[0] + ci[:, 0])
+    occupied = np.unique(key[~lost])
+    cluster = np.where(lost, -1, np.searchsorted(occupied, key)).astype(np.int64)
+    count = len(occupied)
+    S = np.zeros((count, 3), dtype=np.uint64)
+    np.add.at(S, cluster[~lost], r[~lost])
+    n = np.bincount(cluster[~lost], minlength=count).astype(np.uint64)
+    cc = np.stack([occupied % dims[0], (occupied // dims[0]) % dims[1], occupied // dims[0] // dims[1]], axis=1).astype(np.float64)
+    # np.float64(np.uint64): to the nearest float64, ties to even, as the device converts
+    position = origin + cell * (cc + (S.astype(np.float64) / n.astype(np.float64)[:, None]) * 2.0 ** -32)
+    out = {"vertices": position.astype(np.float32).reshape(-1, 3), "vertex_cluster": cluster.astype(np.int32)}
+    if at is not None:
+        out["attributes"] = attribute_means_reference(at, cluster, count).astype(np.float32)
+    inside = ((f >= 0) & (f < len(v))).all(axis=1)
+    m = cluster[np.where(inside[:, None], f, 0)] if len(v) else np.full_like(f, -1)
+    valid = inside & (m >= 0).all(axis=1) & (m[:, 0] != m[:, 1]) & (m[:, 1] != m[:, 2]) & (m[:, 0] != m[:, 2])
+    source = np.nonzero(valid)[0]
+    if len(source):
+        _, first = np.unique(np.sort(m[source], axis=1), axis=0, return_index=True)          # the first row of every set of three
+        source = source[np.sort(first)]
+    out["faces"] = m[source].astype(np.int32).reshape(-1, 3)
+    out["face_source"] = source.astype(np.int32)
+    return out
+
+
 def _mesh_parts(mesh):
     """(vertices, faces, normals or None) of a mesh as isosurface (a tuple) or extract_mesh (a dict) returns it."""
     if isinstance(mesh, dict):
@@ -382,7 +491,8 @@ def default_level(pointnerf) -> float:
 @torch.no_grad()
 def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolution=128, level: Optional[float] = None, colors: bool = True,
                  bound: Optional[float] = None, mlp_dtype=None, view_dir: Optional[torch.Tensor] = None, components: Optional[int] = None,
-                 min_component_nodes: Optional[int] = None, normals: bool = False) -> List[Dict[str, torch.Tensor]]:
+                 min_component_nodes: Optional[int] = None, normals: bool = False, simplify: Optional[float] = None,
+                 simplifier=None) -> List[Dict[str, torch.Tensor]]:
     """coords [B, N, 3], feats [B, N, F] on the GPU -> per cloud {"vertices" [V, 3] fp32, "faces" [F, 3] int32, "colors" [V, 3] fp32
     in [0, 1] (with colors=True)}, all on the GPU.
 
@@ -394,8 +504,15 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
     components=k keeps the k largest connected components of the density above the level, min_component_nodes=m those of at least m
     lattice nodes (npcd.hip.components.filter_components, between the density and the isosurface); the mesh then also holds
     "component_nodes", the kept components' node counts in descending order (int64, on the GPU).  normals=True adds "normals"
-    [V, 3] fp32, the unit normals of vertex_normals_reference from the gradient of the unfiltered density."""
+    [V, 3] fp32, the unit normals of vertex_normals_reference from the gradient of the unfiltered density.
+
+    simplify=k > 0 clusters the vertices on a grid of k lattice spacings from the volume's own origin (npcd.hip.simplify.simplify_mesh,
+    DESIGN.md 5.16): a mesh of roughly 1 / k^2 the triangles.  Colours and normals are averaged per cluster as attributes; the normals
+    are normalised again, and a mean of zero stays zero.  The mesh then also holds "vertex_cluster" [V] and "face_source" [F'].
+    `simplifier` stands in for simplify_mesh (tests of the host logic).  simplify=None leaves the mesh as the isosurface gave it."""
     from ..hip.isosurface import isosurface
+    if simplify is not None and not (isinstance(simplify, (int, float)) and math.isfinite(simplify) and simplify > 0):
+        raise ValueError(f"extract_mesh: simplify must be a positive number of lattice spacings; got {simplify!r}")
     sigma, origin, spacing = pointnerf.density_grid(coords, feats, resolution=resolution, bound=bound, mlp_dtype=mlp_dtype)
     level = default_level(pointnerf) if level is None else float(level)
     filtered, kept_nodes = sigma, None
@@ -416,7 +533,29 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
                                                        view_dir=view_dir)[1][0]
             else:
                 mesh["colors"] = torch.zeros((0, 3), dtype=torch.float32, device=vertices.device)
+        if simplify is not None:
+            mesh = _simplified(mesh, float(simplify), origin, spacing, sigma.shape[1:], simplifier)
         out.append(mesh)
+    return out
+
+
+def _simplified(mesh: Dict[str, torch.Tensor], k: float, origin, spacing, nodes, simplifier=None) -> Dict[str, torch.Tensor]:
+    """The mesh of extract_mesh clustered at k lattice spacings on the volume's origin; nodes = (Gz, Gy, Gx)."""
+    if simplifier is None:
+        from ..hip.simplify import simplify_mesh as simplifier
+    cell = [k * float(s) for s in spacing]
+    dims = [int(math.floor((g - 1) / k)) + 1 for g in (nodes[2], nodes[1], nodes[0])]          # the cells that reach the last node
+    carried = [name for name in ("colors", "normals") if name in mesh]
+    attributes = torch.cat([mesh[name] for name in carried], dim=1) if carried else None
+    got = simplifier(mesh["vertices"], mesh["faces"], cell, origin=[float(o) for o in origin], dims=dims, attributes=attributes)
+    out = dict(mesh)
+    out.update(vertices=got["vertices"], faces=got["faces"], vertex_cluster=got["vertex_cluster"], face_source=got["face_source"])
+    for i, name in enumerate(carried):
+        out[name] = got["attributes"][:, 3 * i:3 * i + 3].contiguous()
+    if "normals" in out:
+        g = out["normals"]
+        unit = g / torch.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])[:, None]
+        out["normals"] = torch.where(torch.isfinite(unit).all(dim=1, keepdim=True), unit, torch.zeros_like(unit))
     return out
 
 

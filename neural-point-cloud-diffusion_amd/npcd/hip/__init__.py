@@ -165,6 +165,12 @@ SIGNATURES = {
     "npcd_surface_ws_bytes": (c_int64, [c_int, c_int64]),
     "npcd_surface_prepare": (c_int, [_P] * 4 + [c_int, c_int64, c_int64, _P, _P, _P]),
     "npcd_surface_sample": (c_int, [_P] * 4 + [c_int, c_int64, c_int64, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, c_int, _P, _P]),
+    "npcd_simplify_ws_bytes": (c_int64, [c_int64, c_int64, c_int, POINTER(c_int)]),
+    "npcd_simplify_cluster": (c_int, [_P, c_int64, c_int64, _P, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int), _P, _P, _P, _P]),
+    "npcd_simplify_faces": (c_int, [_P, c_int64, c_int64, c_int, POINTER(c_int), _P, _P, _P, _P, _P]),
+    "npcd_simplify_unique": (c_int, [_P, c_int64, c_int64, c_int, POINTER(c_int), _P, _P, _P]),
+    "npcd_simplify_emit": (c_int, [c_int64, c_int64, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int), _P, c_int64, c_int64,
+                                   _P, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -229,3 +235,6 @@ def stream_ptr():
     if _raw_stream is not None:
         return c_void_p(_raw_stream(torch.cuda.current_device()))
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+from .simplify import simplify_mesh  # noqa: E402,F401  (after the binding it is written on)
