@@ -962,6 +962,44 @@ int npcd_simplify_emit(int64_t V, int64_t F, int C, const double* origin_host, c
                        const void* ws, int64_t V_out, int64_t F_out, float* vertices_out, float* attributes_out, int32_t* faces_out,
                        int32_t* face_source, void* stream);
 
+/* ---- the edges of one mesh and Taubin smoothing on an integer lattice (added within ABI 10; csrc/smooth.hip,
+ * csrc/smooth.h).  faces [F, 3] int32 and vertices [V, 3] fp32 on the device, 1 <= V < 2^31, 1 <= F < 2^28.  The specification is
+ * restated by mesh_edges_reference and smooth_reference of npcd/eval/mesh.py, and the kernels are held to both bit for bit.
+ *   npcd_mesh_edges_keys: keys [F, 6] int64.  A face is valid if its indices lie in [0, V) and differ pairwise; (i, j, k) gives the
+ *       pairs i->j, j->k, k->i (forward), then j->i, k->j, i->k (backward).  The key of a->b is a 2^31 + b; what is written, and
+ *       sorted, is key 2 + backward.  A face that is not valid gives six times INT64_MAX, and nothing is read through it.  One launch.
+ *   npcd_mesh_edges_unique: sorted_keys [6F] int64 = those keys in ascending order.  counts (int64 [6] on the device) is zeroed, then
+ *       counts[0] = D, the distinct keys (even), counts[1] = F_v, the valid faces; in ws (npcd_mesh_edges_ws_bytes(V, F) bytes, 8-byte
+ *       aligned, contents irrelevant before) the ranks of the run heads.  One memset and two launches.
+ *   npcd_mesh_edges_emit: D as read from counts[0], at least 2.  neighbours [D] int32 = the b of the distinct keys in order; row_start
+ *       [V + 1] int32 = the distinct keys with a < v; edges [D / 2, 2] int32 = the distinct keys with a < b in order; edge_faces [D / 2]
+ *       int32 = the faces that hold the edge (the length of its run), edge_forward [D / 2] int32 = those that traverse it as a->b;
+ *       boundary_vertex [V] uint8 = 1 on an edge of one face; counts[2..5] = the used vertices (rows that are not empty), the edges
+ *       of one face, of three or more, and of two that both traverse it the same way, summed per strip in ws and then by one workgroup:
+ *       no atomics.  One memset and two launches.
+ *   npcd_smooth_mesh: `iterations` (0 .. 1000) times a step with factor lam (0 < lam <= 1), then one with mu (-1 <= mu <= 0; mu = 0:
+ *       no second step) on the adjacency (row_start, neighbours, D) of the calls above.  A = the largest finite |coordinate|, e =
+ *       floor(log2 A), q = rint(float64(x) 2^(29 - e)); a vertex with a coordinate that is not finite is lost.  A vertex moves if it is
+ *       not lost, has a neighbour that is not lost and neither fixed[v] nor boundary_vertex[v] (uint8 [V], either may be NULL) is set.
+ *       A step: S the integer sum of q over the d neighbours that are not lost, q' = clamp(q + rint(f (float64(S) / float64(d) -
+ *       float64(q))), -(2^31 - 1), 2^31 - 1), every vertex reading the old state.  vertices_out [V, 3] = fp32 of float64(q) 2^(e - 29)
+ *       for a vertex that moves, the input bits for every other (for all with iterations = 0, D = 0 or A = 0).  ws:
+ *       npcd_smooth_ws_bytes(V) bytes, 16-byte aligned.  One memset and 3 + steps launches; the step launches use no atomics.
+ * Integer maxima and sums only: the same bits on every run.  No host synchronisation, no allocation, no workgroup that waits on
+ * another.  NPCD_ERR_ARG for a negative size, V < 1 or F < 1, a D that is odd, below 2 or above 6F, iterations, lam or mu outside
+ * their ranges, a NULL pointer that the call takes or a misaligned one; NPCD_ERR_UNSUPPORTED for V >= 2^31 or F >= 2^28 (the
+ * workspace queries return both too).  Nothing is launched in either case. */
+int64_t npcd_mesh_edges_ws_bytes(int64_t V, int64_t F);
+int npcd_mesh_edges_keys(const int32_t* faces, int64_t V, int64_t F, int64_t* keys, void* stream);
+int npcd_mesh_edges_unique(const int64_t* sorted_keys, int64_t V, int64_t F, void* ws, int64_t* counts, void* stream);
+int npcd_mesh_edges_emit(const int64_t* sorted_keys, int64_t V, int64_t F, void* ws, int64_t D, int32_t* row_start,
+                         int32_t* neighbours, int32_t* edges, int32_t* edge_faces, int32_t* edge_forward, uint8_t* boundary_vertex,
+                         int64_t* counts, void* stream);
+int64_t npcd_smooth_ws_bytes(int64_t V);
+int npcd_smooth_mesh(const float* vertices, int64_t V, const int32_t* row_start, const int32_t* neighbours, int64_t D,
+                     const uint8_t* boundary_vertex, const uint8_t* fixed, int iterations, double lam, double mu, void* ws,
+                     float* vertices_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,9 @@ SOURCES = {
     # origin + cell (c + (S / n) 2^-32) -- that are the bits of their numpy restatement only as written: a fused multiply-add would
     # skip the rounding of a product
     "simplify.hip": ["-ffp-contract=off"],
+    # a smoothing step moves a vertex by rint(f (S / d - q)) in float64, and the lattice is x 2^(29 - e) and back q 2^(e - 29): held
+    # bit for bit to their numpy restatement, so every product, quotient and difference is rounded as written
+    "smooth.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

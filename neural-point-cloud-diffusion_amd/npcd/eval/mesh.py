@@ -7,6 +7,9 @@ for dropping floaters from the volume, `vertex_normals_reference` for the normal
 same way: `face_weights_reference` and `surface_sample_reference` restate npcd.hip.surface, and
 `sample_mesh_clouds` draws the clouds that the shape metrics take.  Bringing a mesh down to a usable triangle count likewise
 (DESIGN.md 5.16): `simplify_reference` restates npcd.hip.simplify, exact vertex clustering, and extract_mesh(simplify=k) applies it.
+What a mesh's connectivity is and Taubin smoothing likewise: `mesh_edges_reference` and `smooth_reference` restate
+npcd.hip.smooth, `mesh_topology` reports edges, boundary and non-manifold edges and the Euler characteristic, and
+extract_mesh(smooth=n, topology=True) applies both.
 
 This module imports without a GPU; only extract_mesh and sample_mesh_clouds need one."""
 import itertools
@@ -454,6 +457,131 @@ def simplify_reference(vertices, faces, cell, origin=None, dims=None, attributes
     return out
 
 
+MAX_EDGE_VERTICES, MAX_EDGE_FACES = 2 ** 31, 2 ** 28
+COUNT_NAMES = ("distinct_pairs", "valid_faces", "used_vertices", "boundary_edges", "nonmanifold_edges", "misoriented_edges")
+
+
+def mesh_edges_reference(num_vertices: int, faces) -> Dict[str, np.ndarray]:
+    """faces [F, 3] over vertices 0 .. V - 1 -> {"row_start" [V + 1], "neighbours" [D], "edges" [E, 2], "edge_faces" [E], "edge_forward"
+    [E] int32, "boundary_vertex" [V] uint8, "counts" [6] int64}: the specification of the mesh-edges operator on the CPU, integers only
+    (DESIGN.md 5.17).
+
+    A face is valid if its three indices lie in [0, V) and differ pairwise; every other face contributes nothing.  A valid face
+    (i, j, k) gives the directed pairs i->j, j->k, k->i (forward) and the three reversed (backward); the key of a->b is a 2^31 + b.
+    The D distinct keys in ascending order are the adjacency in CSR form: neighbours holds their b, row_start[v] the number of them
+    with a < v, so a vertex's neighbours ascend and a vertex in no valid face has an empty row.  Those with a < b, in that order, are
+    the E = D / 2 edges; edge_faces counts the valid faces that hold the edge, edge_forward those that traverse it as a->b.  counts =
+    (D, valid faces, vertices with a row that is not empty, edges of one face, edges of three or more faces, edges of two faces that
+    both traverse them the same way); boundary_vertex is 1 on the ends of an edge of one face."""
+    V = int(num_vertices)
+    f = np.ascontiguousarray(np.asarray(faces)).reshape(-1, 3)
+    if f.size and not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"mesh_edges_reference: faces must be integers; got {f.dtype}")
+    if not 0 <= V < MAX_EDGE_VERTICES or len(f) >= MAX_EDGE_FACES:
+        raise ValueError(f"mesh_edges_reference: {V} vertices and {len(f)} faces; vertices must stay below 2^31 = {MAX_EDGE_VERTICES} and "
+                         f"faces below 2^28 = {MAX_EDGE_FACES}")
+    f = f.astype(np.int64)
+    valid = ((f >= 0) & (f < V)).all(axis=1) & (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+    g = f[valid]
+    a, b = g.reshape(-1), g[:, [1, 2, 0]].reshape(-1)
+    forward = a * 2 ** 31 + b
+    keys, runs = np.unique(np.concatenate([forward, b * 2 ** 31 + a]), return_counts=True)
+    source, target = keys >> 31, keys & (2 ** 31 - 1)
+    is_edge = source < target
+    edge_keys = keys[is_edge]
+    traversed = np.zeros(len(edge_keys), dtype=np.int64)
+    np.add.at(traversed, np.searchsorted(edge_keys, forward[a < b]), 1)
+    edge_faces = runs[is_edge]
+    counts = np.array([len(keys), len(g), len(np.unique(source)), int((edge_faces == 1).sum()), int((edge_faces >= 3).sum()),
+                       int(((edge_faces == 2) & (traversed != 1)).sum())], dtype=np.int64)
+    edges = np.stack([source[is_edge], target[is_edge]], axis=1).astype(np.int32).reshape(-1, 2)
+    boundary = np.zeros(V, dtype=np.uint8)
+    boundary[edges[edge_faces == 1].reshape(-1)] = 1
+    return {"row_start": np.searchsorted(source, np.arange(V + 1), side="left").astype(np.int32), "neighbours": target.astype(np.int32),
+            "edges": edges, "edge_faces": edge_faces.astype(np.int32), "edge_forward": traversed.astype(np.int32),
+            "boundary_vertex": boundary, "counts": counts}
+
+
+def topology_from_counts(counts) -> Dict[str, object]:
+    """The counts of mesh_edges_reference / npcd.hip.mesh_edges as Python numbers: edges, valid_faces, used_vertices, boundary_edges,
+    nonmanifold_edges, misoriented_edges, euler_characteristic = used vertices - edges + valid faces, and closed = no boundary edge
+    and no non-manifold edge.  Reading a device array here is one host read."""
+    c = [int(x) for x in (counts.cpu() if isinstance(counts, torch.Tensor) else np.asarray(counts)).reshape(-1).tolist()]
+    if len(c) != len(COUNT_NAMES):
+        raise ValueError(f"topology_from_counts: {len(COUNT_NAMES)} counts {COUNT_NAMES}; got {len(c)}")
+    distinct, valid_faces, used, boundary, nonmanifold, misoriented = c
+    return {"edges": distinct // 2, "valid_faces": valid_faces, "used_vertices": used, "boundary_edges": boundary,
+            "nonmanifold_edges": nonmanifold, "misoriented_edges": misoriented,
+            "euler_characteristic": used - distinct // 2 + valid_faces, "closed": boundary == 0 and nonmanifold == 0}
+
+
+def mesh_topology(num_vertices: int, faces, edges=None) -> Dict[str, object]:
+    """What a mesh's connectivity is, as topology_from_counts gives it.  faces as a tensor: the counts of npcd.hip.mesh_edges (on the
+    GPU; there is no CPU path for tensors); as a numpy array: those of mesh_edges_reference, the specification.  `edges`: a dict
+    that either of them returned for this mesh, to use again."""
+    if edges is None:
+        if isinstance(faces, torch.Tensor):
+            from ..hip.smooth import mesh_edges
+            edges = mesh_edges(num_vertices, faces)
+        else:
+            edges = mesh_edges_reference(num_vertices, faces)
+    return topology_from_counts(edges["counts"])
+
+
+def smooth_reference(vertices, faces, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, fixed=None, fix_boundary: bool = True):
+    """One mesh (vertices [V, 3], faces [F, 3]) -> (vertices' [V, 3] float32, state [V, 3] int32, e): the specification of Taubin's
+    lambda | mu smoothing on an integer lattice on the CPU, float64 and integers.  `state` is the lattice after the last
+    step and e the exponent of its quantum 2^(e - 29) (None where the largest coordinate is 0): the stage before the fp32 rounding.
+
+    A vertex with a coordinate that is not finite is lost: it never moves and is no one's neighbour.  A = the largest finite
+    |coordinate| (an integer maximum on the bits), e = floor(log2 A), q = rint(float64(x) 2^(29 - e)), ties to even.  With the adjacency
+    of mesh_edges_reference, d_i counts the neighbours of i that are not lost; i moves if it is not lost, d_i > 0, it is not in
+    `fixed` [V] and, with fix_boundary, not a boundary vertex.  A step with factor f: S_i the integer sum of q over those neighbours,
+    q_i' = clamp(q_i + rint(f (float64(S_i) / float64(d_i) - float64(q_i))), -(2^31 - 1), 2^31 - 1) per axis, every vertex reading the
+    old state.  An iteration is a step with lam, then one with mu; mu = 0 leaves the second out.  A vertex that moves comes back as
+    float32(float64(q) 2^(e - 29)), every other as its input bits -- as do all with iterations = 0 or A = 0."""
+    v, f = _mesh_arrays(vertices, faces, "smooth_reference")
+    iterations, lam, mu = int(iterations), float(lam), float(mu)
+    if not 0 <= iterations <= 1000:
+        raise ValueError(f"smooth_reference: iterations must lie in [0, 1000]; got {iterations}")
+    if not (0.0 < lam <= 1.0 and -1.0 <= mu <= 0.0):
+        raise ValueError(f"smooth_reference: lam must lie in (0, 1] and mu in [-1, 0]; got {lam} and {mu}")
+    V = len(v)
+    pinned = np.zeros(V, dtype=bool) if fixed is None else np.asarray(fixed).astype(bool).reshape(-1)
+    if len(pinned) != V:
+        raise ValueError(f"smooth_reference: fixed must be [{V}]; got {len(pinned)}")
+    adjacency = mesh_edges_reference(V, f)
+    finite = np.isfinite(v)
+    lost = ~finite.all(axis=1)
+    bits = np.where(finite, np.abs(v), np.float32(0.0)).astype(np.float32).view(np.uint32)
+    top = float(bits.max().view(np.float32)) if v.size else 0.0          # the integer maximum of the bits: |x| >= +0
+    state = np.zeros((V, 3), dtype=np.int64)
+    if top == 0.0:
+        return v.copy(), state.astype(np.int32), None
+    e = math.frexp(top)[1] - 1
+    state[~lost] = np.rint(np.ldexp(v[~lost].astype(np.float64), 29 - e)).astype(np.int64)
+    row, nb = adjacency["row_start"].astype(np.int64), adjacency["neighbours"].astype(np.int64)
+    counted = ~lost[nb]
+
+    def row_sums(values):          # [D, ...] -> [V, ...]: the sums over each vertex's row, in integers
+        total = np.concatenate([np.zeros((1,) + values.shape[1:], dtype=np.int64), np.cumsum(values, axis=0, dtype=np.int64)])
+        return total[row[1:]] - total[row[:-1]]
+    degree = row_sums(counted.astype(np.int64))
+    moves = ~lost & (degree > 0) & ~pinned
+    if fix_boundary:
+        moves &= adjacency["boundary_vertex"] == 0
+    for _ in range(iterations):
+        for factor in (lam, mu) if mu != 0.0 else (lam,):
+            S = row_sums(np.where(counted[:, None], state[nb], 0))[moves]
+            q = state[moves]
+            step = np.rint(factor * (S.astype(np.float64) / degree[moves].astype(np.float64)[:, None] - q.astype(np.float64))).astype(np.int64)
+            state[moves] = np.clip(q + step, -(2 ** 31 - 1), 2 ** 31 - 1)
+    out = v.copy()
+    if iterations:
+        out[moves] = np.ldexp(state[moves].astype(np.float64), e - 29).astype(np.float32)
+    return out, state.astype(np.int32), e
+
+
 def _mesh_parts(mesh):
     """(vertices, faces, normals or None) of a mesh as isosurface (a tuple) or extract_mesh (a dict) returns it."""
     if isinstance(mesh, dict):
@@ -492,7 +620,8 @@ def default_level(pointnerf) -> float:
 def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolution=128, level: Optional[float] = None, colors: bool = True,
                  bound: Optional[float] = None, mlp_dtype=None, view_dir: Optional[torch.Tensor] = None, components: Optional[int] = None,
                  min_component_nodes: Optional[int] = None, normals: bool = False, simplify: Optional[float] = None,
-                 simplifier=None) -> List[Dict[str, torch.Tensor]]:
+                 simplifier=None, smooth: Optional[int] = None, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
+                 topology: bool = False, smoother=None) -> List[Dict[str, torch.Tensor]]:
     """coords [B, N, 3], feats [B, N, F] on the GPU -> per cloud {"vertices" [V, 3] fp32, "faces" [F, 3] int32, "colors" [V, 3] fp32
     in [0, 1] (with colors=True)}, all on the GPU.
 
@@ -509,8 +638,18 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
     simplify=k > 0 clusters the vertices on a grid of k lattice spacings from the volume's own origin (npcd.hip.simplify.simplify_mesh,
     DESIGN.md 5.16): a mesh of roughly 1 / k^2 the triangles.  Colours and normals are averaged per cluster as attributes; the normals
     are normalised again, and a mean of zero stays zero.  The mesh then also holds "vertex_cluster" [V] and "face_source" [F'].
-    `simplifier` stands in for simplify_mesh (tests of the host logic).  simplify=None leaves the mesh as the isosurface gave it."""
+    `simplifier` stands in for simplify_mesh (tests of the host logic).  simplify=None leaves the mesh as the isosurface gave it.
+
+    smooth=n runs n iterations of Taubin's smoothing with the factors smooth_lambda and smooth_mu last, after `simplify`
+    (npcd.hip.smooth.smooth_mesh): boundary vertices stay where they are.  Only "vertices" changes: normals and
+    colours are NOT recomputed -- the normals stay the gradient normals of the unsmoothed surface.  topology=True adds "topology", the
+    dict of mesh_topology for the final mesh (one more host read per mesh).  `smoother` stands in for smooth_mesh (tests of the host
+    logic); with it, topology=True takes the counts of mesh_edges_reference.  smooth=None, topology=False: the mesh as before."""
     from ..hip.isosurface import isosurface
+    if smooth is not None and not (isinstance(smooth, int) and not isinstance(smooth, bool) and 0 <= smooth <= 1000):
+        raise ValueError(f"extract_mesh: smooth must be a number of iterations in [0, 1000]; got {smooth!r}")
+    if smooth is not None and not (0.0 < float(smooth_lambda) <= 1.0 and -1.0 <= float(smooth_mu) <= 0.0):
+        raise ValueError(f"extract_mesh: smooth_lambda must lie in (0, 1] and smooth_mu in [-1, 0]; got {smooth_lambda!r} and {smooth_mu!r}")
     if simplify is not None and not (isinstance(simplify, (int, float)) and math.isfinite(simplify) and simplify > 0):
         raise ValueError(f"extract_mesh: simplify must be a positive number of lattice spacings; got {simplify!r}")
     sigma, origin, spacing = pointnerf.density_grid(coords, feats, resolution=resolution, bound=bound, mlp_dtype=mlp_dtype)
@@ -535,7 +674,25 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
                 mesh["colors"] = torch.zeros((0, 3), dtype=torch.float32, device=vertices.device)
         if simplify is not None:
             mesh = _simplified(mesh, float(simplify), origin, spacing, sigma.shape[1:], simplifier)
+        if smooth is not None or topology:
+            mesh = _smoothed(mesh, smooth, float(smooth_lambda), float(smooth_mu), topology, smoother)
         out.append(mesh)
+    return out
+
+
+def _smoothed(mesh: Dict[str, torch.Tensor], iterations: Optional[int], lam: float, mu: float, topology: bool, smoother=None):
+    """The mesh of extract_mesh after `iterations` of smoothing (None: none), with its topology where asked for.  On the GPU the
+    edges are built once and serve both."""
+    out = dict(mesh)
+    vertices, faces = mesh["vertices"], mesh["faces"]
+    edges = None
+    if smoother is None:
+        from ..hip.smooth import mesh_edges, smooth_mesh as smoother
+        edges = mesh_edges(vertices.shape[0], faces)
+    if iterations is not None:
+        out["vertices"] = smoother(vertices, faces, iterations=iterations, lam=lam, mu=mu, edges=edges)
+    if topology:
+        out["topology"] = mesh_topology(vertices.shape[0], faces.cpu().numpy() if edges is None else faces, edges=edges)
     return out
 
 

@@ -171,6 +171,12 @@ SIGNATURES = {
     "npcd_simplify_unique": (c_int, [_P, c_int64, c_int64, c_int, POINTER(c_int), _P, _P, _P]),
     "npcd_simplify_emit": (c_int, [c_int64, c_int64, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int), _P, c_int64, c_int64,
                                    _P, _P, _P, _P, _P]),
+    "npcd_mesh_edges_ws_bytes": (c_int64, [c_int64, c_int64]),
+    "npcd_mesh_edges_keys": (c_int, [_P, c_int64, c_int64, _P, _P]),
+    "npcd_mesh_edges_unique": (c_int, [_P, c_int64, c_int64, _P, _P, _P]),
+    "npcd_mesh_edges_emit": (c_int, [_P, c_int64, c_int64, _P, c_int64] + [_P] * 7 + [_P]),
+    "npcd_smooth_ws_bytes": (c_int64, [c_int64]),
+    "npcd_smooth_mesh": (c_int, [_P, c_int64, _P, _P, c_int64, _P, _P, c_int, c_double, c_double, _P, _P, _P]),
 }
 
 _lib = None
@@ -238,3 +244,4 @@ def stream_ptr():
 
 
 from .simplify import simplify_mesh  # noqa: E402,F401  (after the binding it is written on)
+from .smooth import mesh_edges, smooth_mesh  # noqa: E402,F401
