@@ -1000,6 +1000,27 @@ int npcd_smooth_mesh(const float* vertices, int64_t V, const int32_t* row_start,
                      const uint8_t* boundary_vertex, const uint8_t* fixed, int iterations, double lam, double mu, void* ws,
                      float* vertices_out, void* stream);
 
+/* ---- the closest point of one mesh to every query point (added within ABI 10; csrc/mesh_distance.hip,
+ * csrc/mesh_distance.h).  points [S, 3], vertices [V, 3] fp32 and faces [F, 3] int32 on the device, V < 2^31, 1 <= F < 2^28,
+ * 1 <= S < 2^31.  The specification is restated by point_mesh_distance_reference of npcd/eval/mesh.py, and the kernels are held to it
+ * bit for bit.
+ *   npcd_mesh_distance_boxes: ws (npcd_mesh_distance_ws_bytes(V, F) bytes, 16-byte aligned, contents irrelevant before) takes the
+ *       corners of every face as three 16-byte words -- NaN for a face with an index outside [0, V), which is not followed -- and per
+ *       tile of 256 consecutive faces the box of its finite corners.  One launch.
+ *   npcd_mesh_distance_query: ws as the boxes call of the same (vertices, V, faces, F) left it.  Per point the lexicographic minimum of
+ *       (dist2, face) over the faces with dist2 < +inf, dist2 the region form of Ericson's closest point on a triangle in fp32 as
+ *       written: sqdist [S] fp32, face [S] int32, closest [S, 3] fp32; (+inf, -1, zeros) for a point that no face wins.  cull = 1
+ *       skips a tile whose box lies farther from every point of a wave than the wave's best; cull = 0 evaluates every tile.  The
+ *       outputs are the same bits.  evaluated (int64 on the device, may be NULL, not zeroed here) takes the (wave, tile) evaluations,
+ *       one integer add per wave.  One launch.
+ * No float atomics, no host synchronisation, no allocation, no workgroup that waits on another.  NPCD_ERR_UNSUPPORTED for V >= 2^31,
+ * F >= 2^28 or S >= 2^31 (the workspace query returns it too); NPCD_ERR_ARG for a negative size, F < 1 or S < 1, a cull that is not 0
+ * or 1, a NULL pointer that the call takes or a misaligned one.  Nothing is launched in either case. */
+int64_t npcd_mesh_distance_ws_bytes(int64_t V, int64_t F);
+int npcd_mesh_distance_boxes(const float* vertices, int64_t V, const int32_t* faces, int64_t F, void* ws, void* stream);
+int npcd_mesh_distance_query(const float* points, int64_t S, const float* vertices, int64_t V, const int32_t* faces, int64_t F,
+                             const void* ws, int cull, float* sqdist, int32_t* face, float* closest, int64_t* evaluated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

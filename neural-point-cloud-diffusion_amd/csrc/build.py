@@ -83,6 +83,10 @@ SOURCES = {
     # a smoothing step moves a vertex by rint(f (S / d - q)) in float64, and the lattice is x 2^(29 - e) and back q 2^(e - 29): held
     # bit for bit to their numpy restatement, so every product, quotient and difference is rounded as written
     "smooth.hip": ["-ffp-contract=off"],
+    # the closest face of a point is picked by comparing fp32 squared distances bit for bit with their numpy restatement: the six dot
+    # products, the three cross terms and q = a + (v ab + w ac) are rounded as written.  Its pair loop is nothing
+    # but fp32 VALU: single operations rather than packed ones, as for chamfer.hip (docs/experiments.md R15.1)
+    "mesh_distance.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

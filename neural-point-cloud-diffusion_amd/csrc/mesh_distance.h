@@ -1,0 +1,170 @@
+// The closest point of a triangle mesh to a query point: the per-lane arithmetic of csrc/mesh_distance.hip, written
+// once for the device and the host.  The kernels run these functions one lane per face (the corners launch) or per query point; the
+// stand-alone program csrc/mesh_distance_host.cpp runs them as plain loops (tests/test_mesh_distance_cpu.py): this header includes
+// nothing of HIP.  All fp32 arithmetic is as written -- the file is compiled without FMA contraction (build.py) -- and the division
+// is the correctly rounded one.
+//
+//   Pair      (p; a, b, c): the region form of Ericson's closest point on a triangle, md_pair below; dot(u, v) = (ux vx + uy vy) +
+//             uz vz.  The first region that holds gives (v, w); q = a + (v ab + w ac), dist2 = dot(p - q, p - q).  One division: the
+//             regions differ in which quotient they take, not in how it is rounded.
+//   Corners   a face takes part if its three indices lie in [0, V); the corners launch writes its nine coordinates as three 16-byte
+//             words.  Every other face, and the padding of the last tile, is written as NaN: its dist2 is NaN and never wins.
+//   Winner    the lexicographic minimum of (dist2, face) over the faces with dist2 < +inf; a NaN never wins.  dist2 >= +0, so its
+//             bits order as unsigned integers: md_key packs (bits << 32) | face.
+//   Box       per tile of kMdTile consecutive faces the axis-aligned box of the corners that are finite, of the faces that take part,
+//             and slack = 2^-20 the largest power of two at or below the largest |coordinate| among them: 8 ulp.
+//   Bound     md_bound: g = (max(lo - p, p - hi) - max(slack, the point's own)) (1 - 2^-11), clamped at 0 per axis; (gx gx + gy gy) +
+//             gz gz.  A tile is evaluated if bound <= best and bound < +inf (md_needs); the box of a tile without a finite corner
+//             is (+inf, -inf), whose bound is +inf for every finite point.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "smooth.h"          // simp_bits, simp_float, sm_finite, sm_lost
+
+namespace npcd {
+
+constexpr int kMdThreads = 64;                                // lanes per workgroup of the query launch: one wave, one point per lane
+constexpr int kMdTile = 256;                                  // faces per tile; the corners launch runs one workgroup of kMdTile lanes per tile
+constexpr int kMdScan = 4;                                    // boxes a wave takes bounds to at a time: their loads are in flight together
+constexpr int64_t kMdMaxVertices = (int64_t)1 << 31;
+constexpr int64_t kMdMaxFaces = (int64_t)1 << 28;
+constexpr int64_t kMdMaxPoints = (int64_t)1 << 31;
+constexpr uint32_t kMdInfBits = 0x7f800000u;
+constexpr uint64_t kMdNoKey = ((uint64_t)kMdInfBits << 32) | 0xffffffffu;          // (+inf, -1): what a point without a face keeps
+constexpr float kMdShrink = 0.99951171875f;                   // 1 - 2^-11, per axis: 2^-10 of the bound
+
+struct alignas(16) MdCorner {          // one corner of a face: a 16-byte word, the fourth float is not read
+    float x, y, z, pad;
+};
+struct alignas(16) MdBox {          // one tile
+    float lo[3], slack, hi[3];
+    int32_t count;          // the corners inside: 0 for a tile that is always skipped
+};
+
+NPCD_SIMP_HD int64_t md_tiles(int64_t F) { return (F + kMdTile - 1) / kMdTile; }
+NPCD_SIMP_HD float md_dot(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
+
+// ---- one pair -------------------------------------------------------------------------------------------------------------------------
+// -> dist2; q [3] the closest point
+NPCD_SIMP_HD float md_pair(const float* p, const float* a, const float* b, const float* c, float* q) {
+    const float abx = b[0] - a[0], aby = b[1] - a[1], abz = b[2] - a[2];
+    const float acx = c[0] - a[0], acy = c[1] - a[1], acz = c[2] - a[2];
+    const float apx = p[0] - a[0], apy = p[1] - a[1], apz = p[2] - a[2];
+    const float bpx = p[0] - b[0], bpy = p[1] - b[1], bpz = p[2] - b[2];
+    const float cpx = p[0] - c[0], cpy = p[1] - c[1], cpz = p[2] - c[2];
+    const float d1 = md_dot(abx, aby, abz, apx, apy, apz), d2 = md_dot(acx, acy, acz, apx, apy, apz);
+    const float d3 = md_dot(abx, aby, abz, bpx, bpy, bpz), d4 = md_dot(acx, acy, acz, bpx, bpy, bpz);
+    const float d5 = md_dot(abx, aby, abz, cpx, cpy, cpz), d6 = md_dot(acx, acy, acz, cpx, cpy, cpz);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float d43 = d4 - d3, d56 = d5 - d6;
+    // no short-circuit anywhere below: the lanes of a wave fall into different regions, and selects cost less than branches
+    const bool at_a = (d1 <= 0.f) & (d2 <= 0.f);
+    const bool at_b = (d3 >= 0.f) & (d4 <= d3);
+    const bool on_ab = (vc <= 0.f) & (d1 >= 0.f) & (d3 <= 0.f);
+    const bool at_c = (d6 >= 0.f) & (d5 <= d6);
+    const bool on_ac = (vb <= 0.f) & (d2 >= 0.f) & (d6 <= 0.f);
+    const bool on_bc = (va <= 0.f) & (d43 >= 0.f) & (d56 >= 0.f);
+    // the first region that holds: a, b, ab, c, ac, bc, inside
+    const bool is_b = !at_a & at_b, none2 = !at_a & !at_b;
+    const bool is_ab = none2 & on_ab, none3 = none2 & !on_ab;
+    const bool is_c = none3 & at_c, none4 = none3 & !at_c;
+    const bool is_ac = none4 & on_ac, none5 = none4 & !on_ac;
+    const bool is_bc = none5 & on_bc, inside = none5 & !on_bc;
+    float num = 1.f, den = (va + vb) + vc;
+    num = is_ab ? d1 : num, den = is_ab ? d1 - d3 : den;
+    num = is_ac ? d2 : num, den = is_ac ? d2 - d6 : den;
+    num = is_bc ? d43 : num, den = is_bc ? d43 + d56 : den;
+    const float r = num / den;          // not used by the corner regions, whatever it is
+    float v = 0.f, w = 0.f;
+    v = is_b ? 1.f : v;
+    v = is_ab ? r : v;
+    w = is_c ? 1.f : w;
+    w = is_ac ? r : w;
+    v = is_bc ? 1.f - r : v, w = is_bc ? r : w;
+    v = inside ? vb * r : v, w = inside ? vc * r : w;
+    q[0] = a[0] + (v * abx + w * acx), q[1] = a[1] + (v * aby + w * acy), q[2] = a[2] + (v * abz + w * acz);
+    const float ex = p[0] - q[0], ey = p[1] - q[1], ez = p[2] - q[2];
+    return md_dot(ex, ey, ez, ex, ey, ez);
+}
+
+// ---- the winner -----------------------------------------------------------------------------------------------------------------------
+// (dist2, face) replaces (best, best_face) if it is below it lexicographically; a NaN and +inf never do
+NPCD_SIMP_HD bool md_better(float dist2, int32_t face, float best, int32_t best_face) {
+    return (dist2 < best) | ((dist2 == best) & (face < best_face));
+}
+// the same order on one word: a dist2 that cannot win (NaN, +inf) gives kMdNoKey
+NPCD_SIMP_HD uint64_t md_key(float dist2, int32_t face) {
+    return dist2 < simp_float(kMdInfBits) ? ((uint64_t)simp_bits(dist2) << 32) | (uint32_t)face : kMdNoKey;
+}
+
+// ---- one face of the corners launch -----------------------------------------------------------------------------------------------------
+// out [3]: the corners of face f, NaN where the face does not take part (or f >= F).  -> true if it takes part
+NPCD_SIMP_HD bool md_corners_lane(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int64_t f, MdCorner* out) {
+    const float nan = simp_float(0x7fc00000u);
+    bool valid = f < F;
+    int64_t idx[3] = {0, 0, 0};
+    if (valid)
+        for (int k = 0; k < 3; ++k) {
+            idx[k] = faces[f * 3 + k];
+            valid = valid && idx[k] >= 0 && idx[k] < V;
+        }
+    for (int k = 0; k < 3; ++k) {
+        out[k].pad = 0.f;
+        if (valid) {
+            out[k].x = vertices[idx[k] * 3], out[k].y = vertices[idx[k] * 3 + 1], out[k].z = vertices[idx[k] * 3 + 2];
+        } else {
+            out[k].x = out[k].y = out[k].z = nan;
+        }
+    }
+    return valid;
+}
+// a corner joins a box if its three coordinates are finite
+NPCD_SIMP_HD bool md_corner_counts(const MdCorner& c) { return sm_finite(c.x) && sm_finite(c.y) && sm_finite(c.z); }
+NPCD_SIMP_HD uint32_t md_abs_bits(const MdCorner& c) {
+    const uint32_t x = simp_bits(c.x) & 0x7fffffffu, y = simp_bits(c.y) & 0x7fffffffu, z = simp_bits(c.z) & 0x7fffffffu;
+    return x > y ? (x > z ? x : z) : (y > z ? y : z);
+}
+// 8 ulp of a finite |coordinate| given by its bits: 2^-20 of the power of two at or below it, at least 8 times the smallest float
+NPCD_SIMP_HD float md_slack(uint32_t abs_bits) {
+    const float unit = simp_float(abs_bits & kMdInfBits) * 9.5367431640625e-07f;          // 2^-20, exact or a denormal power of two
+    const float least = simp_float(8u);
+    return unit > least ? unit : least;
+}
+NPCD_SIMP_HD float md_point_slack(const float* p) {
+    const MdCorner c = {p[0], p[1], p[2], 0.f};
+    return md_corner_counts(c) ? md_slack(md_abs_bits(c)) : simp_float(8u);
+}
+// the box of `n` corners (n a multiple of three, NaN corners do not count)
+NPCD_SIMP_HD MdBox md_box_of(const MdCorner* corners, int64_t n) {
+    const float inf = simp_float(kMdInfBits);
+    MdBox box = {{inf, inf, inf}, 0.f, {-inf, -inf, -inf}, 0};
+    uint32_t top = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        const MdCorner& c = corners[j];
+        if (!md_corner_counts(c)) continue;
+        const float x[3] = {c.x, c.y, c.z};
+        for (int k = 0; k < 3; ++k) box.lo[k] = x[k] < box.lo[k] ? x[k] : box.lo[k], box.hi[k] = x[k] > box.hi[k] ? x[k] : box.hi[k];
+        const uint32_t m = md_abs_bits(c);
+        top = m > top ? m : top;
+        box.count += 1;
+    }
+    box.slack = md_slack(top);
+    return box;
+}
+
+// ---- one (point, tile) of the query launch ----------------------------------------------------------------------------------------------
+NPCD_SIMP_HD float md_bound(const float* p, float point_slack, const MdBox& box) {
+    const float slack = box.slack > point_slack ? box.slack : point_slack;
+    float g[3];
+    for (int k = 0; k < 3; ++k) {
+        const float below = box.lo[k] - p[k], above = p[k] - box.hi[k];
+        const float out = ((below > above ? below : above) - slack) * kMdShrink;
+        g[k] = out > 0.f ? out : 0.f;          // a NaN gives 0
+    }
+    return md_dot(g[0], g[1], g[2], g[0], g[1], g[2]);
+}
+NPCD_SIMP_HD bool md_needs(float bound, float best) { return !(bound > best) & (bound < simp_float(kMdInfBits)); }
+
+}  // namespace npcd

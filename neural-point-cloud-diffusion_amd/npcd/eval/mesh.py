@@ -9,9 +9,11 @@ same way: `face_weights_reference` and `surface_sample_referenc
 (DESIGN.md 5.16): `simplify_reference` restates npcd.hip.simplify, exact vertex clustering, and extract_mesh(simplify=k) applies it.
 What a mesh's connectivity is and Taubin smoothing likewise: `mesh_edges_reference` and `smooth_reference` restate
 npcd.hip.smooth, `mesh_topology` reports edges, boundary and non-manifold edges and the Euler characteristic, and
-extract_mesh(smooth=n, topology=True) applies both.
+extract_mesh(smooth=n, topology=True) applies both.  How far two surfaces lie apart likewise:
+`point_mesh_distance_reference` restates npcd.hip.mesh_distance, `mesh_deviation` and `cloud_mesh_distance` report mean, rms and
+maximum distances, and extract_mesh(deviation=n) says what simplifying and smoothing cost.
 
-This module imports without a GPU; only extract_mesh and sample_mesh_clouds need one."""
+This module imports without a GPU; only extract_mesh, sample_mesh_clouds, mesh_deviation and cloud_mesh_distance need one."""
 import itertools
 import math
 from typing import Dict, List, Optional, Sequence
@@ -582,11 +584,150 @@ def smooth_reference(vertices, faces, iterations: int = 10, lam: float = 0.5, mu
     return out, state.astype(np.int32), e
 
 
+MAX_DISTANCE_FACES = 2 ** 28          # what npcd.hip.mesh_distance takes (kMdMaxFaces of csrc/mesh_distance.h)
+
+
+def closest_on_triangles(p, a, b, c):
+    """The region form of Ericson's closest point on a triangle, every operation rounded in the arrays' own dtype, in the order of
+    DESIGN.md 5.18.  p, a, b, c broadcast to [..., 3] -> (dist2 [...], q [..., 3]).  With float32 arrays this is the specification of a
+    pair; with float64 arrays the same algorithm is what the tests measure its error against."""
+    dt = np.result_type(p, a, b, c)
+    zero, one = dt.type(0), dt.type(1)
+
+    def dot(u, v):
+        return (u[..., 0] * v[..., 0] + u[..., 1] * v[..., 1]) + u[..., 2] * v[..., 2]
+    with np.errstate(all="ignore"):
+        ab, ac, ap, bp, cp = b - a, c - a, p - a, p - b, p - c
+        d1, d2, d3, d4, d5, d6 = dot(ab, ap), dot(ac, ap), dot(ab, bp), dot(ac, bp), dot(ab, cp), dot(ac, cp)
+        vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+        d43, d56 = d4 - d3, d5 - d6
+        holds = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+                 (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (d43 >= 0) & (d56 >= 0)]
+        region = np.full(d1.shape, 6, dtype=np.int8)          # the first region that holds
+        for k in range(5, -1, -1):
+            region = np.where(holds[k], np.int8(k), region)
+        t = d43 / (d43 + d56)
+        den = one / ((va + vb) + vc)
+        v = np.select([region == 1, region == 2, region == 5, region == 6], [one, d1 / (d1 - d3), one - t, vb * den], zero).astype(dt)
+        w = np.select([region == 3, region == 4, region == 5, region == 6], [one, d2 / (d2 - d6), t, vc * den], zero).astype(dt)
+        q = a + (v[..., None] * ab + w[..., None] * ac)
+        e = p - q
+        return dot(e, e), q
+
+
+def point_mesh_distance_reference(points, vertices, faces, chunk: int = 256) -> Dict[str, np.ndarray]:
+    """The specification of npcd.hip.mesh_distance.closest_on_mesh in numpy: brute force, fp32 as written, `chunk`
+    faces at a time.  points [S, 3], vertices [V, 3], faces [F, 3] -> {"sqdist" [S] float32, "face" [S] int32, "closest" [S, 3]
+    float32}.
+
+    A face takes part if its three indices lie in [0, V).  In ascending face order a face replaces the best if its dist2 is below it,
+    from best = +inf and face = -1: a NaN never wins and among equal bits the lowest face index stays.  closest is that face's q; a
+    point that no face wins keeps (+inf, -1, (+0, +0, +0))."""
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32))
+    f = np.asarray(faces)
+    if p.ndim != 2 or p.shape[1] != 3 or v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"point_mesh_distance_reference: points, vertices and faces must be [N, 3]; got {p.shape}, {v.shape} and {f.shape}")
+    if f.size and not np.issubdtype(f.dtype, np.integer):
+        raise ValueError("point_mesh_distance_reference: faces must hold integers")
+    f = f.astype(np.int64)
+    S, V, F = len(p), len(v), len(f)
+    if F >= MAX_DISTANCE_FACES:
+        raise ValueError(f"point_mesh_distance_reference: {F} faces; they must stay below 2^28 = {MAX_DISTANCE_FACES}")
+    best = np.full(S, np.inf, dtype=np.float32)
+    face = np.full(S, -1, dtype=np.int32)
+    closest = np.zeros((S, 3), dtype=np.float32)
+    rows = np.arange(S)
+    for first in range(0, F if S else 0, chunk):
+        part = f[first:first + chunk]
+        valid = ((part >= 0) & (part < V)).all(axis=1)
+        if not valid.any():
+            continue
+        index = first + np.nonzero(valid)[0]
+        corner = v[part[valid]]          # [n, 3 corners, 3]
+        d, q = closest_on_triangles(p[:, None, :], corner[None, :, 0], corner[None, :, 1], corner[None, :, 2])
+        d = np.where(np.isnan(d), np.float32(np.inf), d)
+        at = np.argmin(d, axis=1)          # the first of equal minima: the lowest index
+        least = d[rows, at]
+        wins = least < best
+        best[wins], face[wins], closest[wins] = least[wins], index[at[wins]].astype(np.int32), q[rows, at][wins]
+    return {"sqdist": best, "face": face, "closest": closest}
+
+
 def _mesh_parts(mesh):
     """(vertices, faces, normals or None) of a mesh as isosurface (a tuple) or extract_mesh (a dict) returns it."""
     if isinstance(mesh, dict):
         return mesh["vertices"], mesh["faces"], mesh.get("normals")
     return mesh[0], mesh[1], (mesh[2] if len(mesh) > 2 else None)
+
+
+def _distance_stats(sqdist: torch.Tensor, usable: torch.Tensor) -> torch.Tensor:
+    """sqdist [S] and usable [S] bool -> [mean, rms, max] of sqrt(float64(sqdist)) over the usable samples as a float64 tensor on
+    their device; NaN without any."""
+    d = torch.sqrt(sqdist.to(torch.float64))
+    if d.numel() == 0:
+        return torch.full((3,), float("nan"), dtype=torch.float64, device=sqdist.device)
+    n = usable.sum().to(torch.float64)
+    kept = torch.where(usable, d, torch.zeros_like(d))
+    top = torch.where(usable, d, torch.full_like(d, -float("inf"))).max()
+    return torch.stack([kept.sum() / n, torch.sqrt((kept * kept).sum() / n), torch.where(n > 0, top, torch.full_like(top, float("nan")))])
+
+
+def _closest_operator(closest):
+    if closest is None:
+        from ..hip.mesh_distance import closest_on_mesh as closest
+    return closest
+
+
+_STAT_NAMES = ("mean", "rms", "max")
+
+
+@torch.no_grad()
+def mesh_deviation(a, b, num_samples: int = 100_000, generator: Optional[torch.Generator] = None, sampler=None, closest=None) -> Dict[str, object]:
+    """How far two surfaces lie apart.  a, b: meshes on the GPU as isosurface (a tuple) or extract_mesh (a dict) return them.
+
+    num_samples points are drawn by area on each (npcd.hip.surface.sample_surface) and each takes its distance to the
+    other mesh (npcd.hip.mesh_distance.closest_on_mesh).  -> {"a_to_b", "b_to_a": {"mean", "rms", "max"} of
+    sqrt(float64(sqdist)) over the samples that have a face on both sides, "hausdorff": the larger max, "mean": the mean of the two
+    means, "diagonal": the bounding-box diagonal of a's finite vertices, "samples": num_samples}, Python floats.  A direction without
+    a usable sample gives NaN.  The reductions are float64 on the device; one host read.  `sampler` and `closest` stand in for
+    sample_surface and closest_on_mesh (tests of the host logic)."""
+    n = int(num_samples)
+    if n < 1:
+        raise ValueError(f"mesh_deviation: num_samples must be at least 1; got {num_samples}")
+    if sampler is None:
+        from ..hip.surface import sample_surface as sampler
+    closest = _closest_operator(closest)
+    (va, fa, _), (vb, fb, _) = _mesh_parts(a), _mesh_parts(b)
+    stats = []
+    for (v_from, f_from), (v_to, f_to) in (((va, fa), (vb, fb)), ((vb, fb), (va, fa))):
+        points, _, own = sampler((v_from, f_from), n, generator=generator, return_faces=True)
+        got = closest(points, v_to, f_to)
+        stats.append(_distance_stats(got["sqdist"], (own >= 0) & (got["face"] >= 0)))
+    finite = torch.isfinite(va).all(dim=1)
+    if va.shape[0]:
+        v64 = va.to(torch.float64)
+        lo = torch.where(finite[:, None], v64, torch.full_like(v64, float("inf"))).amin(dim=0)
+        hi = torch.where(finite[:, None], v64, torch.full_like(v64, -float("inf"))).amax(dim=0)
+        diagonal = torch.where(finite.any(), torch.sqrt(((hi - lo) ** 2).sum()), torch.full((), float("nan"), dtype=torch.float64, device=va.device))
+    else:
+        diagonal = torch.full((), float("nan"), dtype=torch.float64, device=va.device)
+    flat = torch.cat([stats[0], stats[1], diagonal.reshape(1)]).cpu().tolist()          # the one host read
+    a_to_b, b_to_a = dict(zip(_STAT_NAMES, flat[0:3])), dict(zip(_STAT_NAMES, flat[3:6]))
+    both = (a_to_b["max"], b_to_a["max"])
+    return {"a_to_b": a_to_b, "b_to_a": b_to_a, "hausdorff": float("nan") if any(math.isnan(x) for x in both) else max(both),
+            "mean": 0.5 * (a_to_b["mean"] + b_to_a["mean"]), "diagonal": flat[6], "samples": n}
+
+
+@torch.no_grad()
+def cloud_mesh_distance(points: torch.Tensor, mesh, closest=None) -> Dict[str, float]:
+    """How far the points [S, 3] of a generated cloud lie from an extracted surface: {"mean", "rms", "max"} of sqrt(float64(sqdist))
+    over the points that a face wins (npcd.hip.mesh_distance.closest_on_mesh), Python floats; NaN without any.  One host read.
+    `closest` stands in for closest_on_mesh."""
+    closest = _closest_operator(closest)
+    vertices, faces, _ = _mesh_parts(mesh)
+    got = closest(points, vertices, faces)
+    return dict(zip(_STAT_NAMES, _distance_stats(got["sqdist"], got["face"] >= 0).cpu().tolist()))
 
 
 @torch.no_grad()
@@ -609,6 +750,9 @@ def sample_mesh_clouds(meshes, num_points: int, generator: Optional[torch.Genera
     return (got[0], got[2]) if normals else got[0]
 
 
+DEVIATION_SEED = 20260518          # of the samples of extract_mesh(deviation=n)
+
+
 def default_level(pointnerf) -> float:
     """ln 2 / (2 cube_scale / (depth_resolution - 1)): the density at which one depth step of an axis-parallel ray through the box
     is half opaque."""
@@ -621,7 +765,7 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
                  bound: Optional[float] = None, mlp_dtype=None, view_dir: Optional[torch.Tensor] = None, components: Optional[int] = None,
                  min_component_nodes: Optional[int] = None, normals: bool = False, simplify: Optional[float] = None,
                  simplifier=None, smooth: Optional[int] = None, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
-                 topology: bool = False, smoother=None) -> List[Dict[str, torch.Tensor]]:
+                 topology: bool = False, smoother=None, deviation: Optional[int] = None, deviator=None) -> List[Dict[str, torch.Tensor]]:
     """coords [B, N, 3], feats [B, N, F] on the GPU -> per cloud {"vertices" [V, 3] fp32, "faces" [F, 3] int32, "colors" [V, 3] fp32
     in [0, 1] (with colors=True)}, all on the GPU.
 
@@ -644,8 +788,18 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
     (npcd.hip.smooth.smooth_mesh): boundary vertices stay where they are.  Only "vertices" changes: normals and
     colours are NOT recomputed -- the normals stay the gradient normals of the unsmoothed surface.  topology=True adds "topology", the
     dict of mesh_topology for the final mesh (one more host read per mesh).  `smoother` stands in for smooth_mesh (tests of the host
-    logic); with it, topology=True takes the counts of mesh_edges_reference.  smooth=None, topology=False: the mesh as before."""
+    logic); with it, topology=True takes the counts of mesh_edges_reference.  smooth=None, topology=False: the mesh as before.
+
+    deviation=n, with simplify or smooth given, adds "deviation": mesh_deviation(the final mesh, the raw isosurface of the same cloud,
+    n), what simplifying and smoothing cost in distance (one more host read per mesh).  Its samples come from a
+    generator seeded with DEVIATION_SEED, so two calls agree.  `deviator` stands in for mesh_deviation (tests of the host logic).
+    deviation=None: the mesh as before."""
     from ..hip.isosurface import isosurface
+    if deviation is not None:
+        if isinstance(deviation, bool) or not isinstance(deviation, int) or deviation < 1:
+            raise ValueError(f"extract_mesh: deviation must be a positive number of samples; got {deviation!r}")
+        if simplify is None and smooth is None:
+            raise ValueError("extract_mesh: deviation compares the final mesh with the raw isosurface; without simplify or smooth there is nothing to compare")
     if smooth is not None and not (isinstance(smooth, int) and not isinstance(smooth, bool) and 0 <= smooth <= 1000):
         raise ValueError(f"extract_mesh: smooth must be a number of iterations in [0, 1000]; got {smooth!r}")
     if smooth is not None and not (0.0 < float(smooth_lambda) <= 1.0 and -1.0 <= float(smooth_mu) <= 0.0):
@@ -676,6 +830,9 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
             mesh = _simplified(mesh, float(simplify), origin, spacing, sigma.shape[1:], simplifier)
         if smooth is not None or topology:
             mesh = _smoothed(mesh, smooth, float(smooth_lambda), float(smooth_mu), topology, smoother)
+        if deviation is not None:
+            seeded = torch.Generator(device=vertices.device).manual_seed(DEVIATION_SEED)
+            mesh["deviation"] = (mesh_deviation if deviator is None else deviator)(mesh, (vertices, faces), deviation, generator=seeded)
         out.append(mesh)
     return out
 

@@ -177,6 +177,9 @@ SIGNATURES = {
     "npcd_mesh_edges_emit": (c_int, [_P, c_int64, c_int64, _P, c_int64] + [_P] * 7 + [_P]),
     "npcd_smooth_ws_bytes": (c_int64, [c_int64]),
     "npcd_smooth_mesh": (c_int, [_P, c_int64, _P, _P, c_int64, _P, _P, c_int, c_double, c_double, _P, _P, _P]),
+    "npcd_mesh_distance_ws_bytes": (c_int64, [c_int64, c_int64]),
+    "npcd_mesh_distance_boxes": (c_int, [_P, c_int64, _P, c_int64, _P, _P]),
+    "npcd_mesh_distance_query": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int] + [_P] * 4 + [_P]),
 }
 
 _lib = None
@@ -245,3 +248,4 @@ def stream_ptr():
 
 from .simplify import simplify_mesh  # noqa: E402,F401  (after the binding it is written on)
 from .smooth import mesh_edges, smooth_mesh  # noqa: E402,F401
+from .mesh_distance import closest_on_mesh  # noqa: E402,F401
