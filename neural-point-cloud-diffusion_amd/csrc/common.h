@@ -111,6 +111,9 @@ __device__ __forceinline__ int tile_swz(int row) { return (((row >> 1) & 1) << 2
 __device__ __forceinline__ int tile_off(int row, int chunk) { return row * 128 + (((chunk ^ tile_swz(row)) & 7) << 4); }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// host: workgroups of `threads` lanes for one lane per entry; does p break an alignment of `bytes` (a power of two)?  Null does not.
+static inline unsigned blocks_for(int64_t lanes, int threads) { return (unsigned)((lanes + threads - 1) / threads); }
+static inline bool misaligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0; }
 
 // host-side error latch
 void set_hip_error(hipError_t e);

@@ -25,11 +25,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define NPCD_CC_HD __host__ __device__ __forceinline__
-#else
-#define NPCD_CC_HD inline
-#endif
+#include "bits.h"          // NPCD_HD
 
 namespace npcd {
 
@@ -43,7 +39,7 @@ struct CcGrid {
     int gx, gy, gz, n;                  // nodes per axis and per volume
     int bricks_x, bricks_y, bricks;          // bricks per row, per slab of bricks, per volume
 };
-NPCD_CC_HD CcGrid cc_grid(int gz, int gy, int gx) {
+NPCD_HD CcGrid cc_grid(int gz, int gy, int gx) {
     CcGrid g;
     g.gx = gx, g.gy = gy, g.gz = gz, g.n = gz * gy * gx;
     g.bricks_x = (gx + kCcBrickX - 1) / kCcBrickX;
@@ -58,7 +54,7 @@ struct CcNode {
     int lx, ly, lz, x, y, z, node;
     bool valid;
 };
-NPCD_CC_HD CcNode cc_node(const CcGrid& g, int brick, int l) {
+NPCD_HD CcNode cc_node(const CcGrid& g, int brick, int l) {
     CcNode p;
     const int by = brick / g.bricks_x, bx = brick - by * g.bricks_x, bz = by / g.bricks_y;
     p.lx = l % kCcBrickX, p.ly = l / kCcBrickX % kCcBrickY, p.lz = l / (kCcBrickX * kCcBrickY);
@@ -70,17 +66,17 @@ NPCD_CC_HD CcNode cc_node(const CcGrid& g, int brick, int l) {
 
 // plain memory operations: the host's, and the device's where a launch has no concurrent writer
 struct CcPlain {
-    static NPCD_CC_HD int load(const int32_t* p) { return *p; }
-    static NPCD_CC_HD int fetch_min(int32_t* p, int v) {
+    static NPCD_HD int load(const int32_t* p) { return *p; }
+    static NPCD_HD int fetch_min(int32_t* p, int v) {
         const int old = *p;
         if (v < old) *p = v;
         return old;
     }
-    static NPCD_CC_HD void add(int32_t* p, int v) { *p += v; }
+    static NPCD_HD void add(int32_t* p, int v) { *p += v; }
 };
 
 template <class Ops>
-NPCD_CC_HD int cc_root(const int32_t* parent, int i) {
+NPCD_HD int cc_root(const int32_t* parent, int i) {
     for (;;) {          // (I): the index falls strictly
         const int p = Ops::load(parent + i);
         if (p == i) return i;
@@ -89,7 +85,7 @@ NPCD_CC_HD int cc_root(const int32_t* parent, int i) {
 }
 // the root, halving the path on the way: an entry is lowered to its grandparent, a node of the component below it
 template <class Ops>
-NPCD_CC_HD int cc_find(int32_t* parent, int i) {
+NPCD_HD int cc_find(int32_t* parent, int i) {
     for (;;) {
         const int p = Ops::load(parent + i);
         if (p == i) return i;
@@ -99,7 +95,7 @@ NPCD_CC_HD int cc_find(int32_t* parent, int i) {
     }
 }
 template <class Ops>
-NPCD_CC_HD void cc_union(int32_t* parent, int a, int b) {
+NPCD_HD void cc_union(int32_t* parent, int a, int b) {
     for (;;) {          // max(a, b) falls strictly with every retry
         a = cc_find<Ops>(parent, a), b = cc_find<Ops>(parent, b);
         if (a == b) return;
@@ -113,13 +109,13 @@ NPCD_CC_HD void cc_union(int32_t* parent, int a, int b) {
 // ---- tile phase: union-find over the edges inside a brick, on the brick's label array `local` [kCcBrickNodes] in local indices, and
 // the number of nodes of every piece -- the part of a component inside the brick -- at the piece's root, in `count`
 // [kCcBrickNodes].  Four steps with a workgroup barrier between them; every lane runs each step for its kCcNodesPerLane nodes.
-NPCD_CC_HD void cc_tile_load(const CcGrid& g, const float* vol, float level, int brick, int l, int32_t* local, int32_t* count) {
+NPCD_HD void cc_tile_load(const CcGrid& g, const float* vol, float level, int brick, int l, int32_t* local, int32_t* count) {
     const CcNode p = cc_node(g, brick, l);
     local[l] = p.valid && vol[p.node] > level ? l : -1;
     count[l] = 0;
 }
 template <class Ops>
-NPCD_CC_HD void cc_tile_link(int l, int32_t* local) {
+NPCD_HD void cc_tile_link(int l, int32_t* local) {
     if (local[l] < 0) return;
     const int lx = l % kCcBrickX, ly = l / kCcBrickX % kCcBrickY, lz = l / (kCcBrickX * kCcBrickY);
     for (int c = 1; c < 8; ++c) {          // the upper end at (dx, dy, dz) = (c & 1, c >> 1 & 1, c >> 2)
@@ -130,11 +126,11 @@ NPCD_CC_HD void cc_tile_link(int l, int32_t* local) {
     }
 }
 template <class Ops>
-NPCD_CC_HD void cc_tile_count(int l, const int32_t* local, int32_t* count) {          // the forest is complete: plain loads
+NPCD_HD void cc_tile_count(int l, const int32_t* local, int32_t* count) {          // the forest is complete: plain loads
     if (local[l] >= 0) Ops::add(count + cc_root<CcPlain>(local, l), 1);
 }
 // the forest of the pieces goes to `parent` in node indices of the volume; sizes = the piece's nodes at its root, 0 elsewhere
-NPCD_CC_HD void cc_tile_store(const CcGrid& g, int brick, int l, const int32_t* local, const int32_t* count, int32_t* parent, int32_t* sizes) {
+NPCD_HD void cc_tile_store(const CcGrid& g, int brick, int l, const int32_t* local, const int32_t* count, int32_t* parent, int32_t* sizes) {
     const CcNode p = cc_node(g, brick, l);
     if (!p.valid) return;
     sizes[p.node] = count[l];
@@ -146,7 +142,7 @@ NPCD_CC_HD void cc_tile_store(const CcGrid& g, int brick, int l, const int32_t* 
 // components -- and an upper end whose entry equals the one just joined is skipped: the up to four edges from a node into one
 // neighbouring brick mostly end in one piece.
 template <class Ops>
-NPCD_CC_HD void cc_merge_node(const CcGrid& g, int brick, int l, int32_t* parent) {
+NPCD_HD void cc_merge_node(const CcGrid& g, int brick, int l, int32_t* parent) {
     const CcNode p = cc_node(g, brick, l);
     if (!p.valid || (p.lx + 1 < kCcBrickX && p.ly + 1 < kCcBrickY && p.lz + 1 < kCcBrickZ)) return;          // no edge leaves the brick
     const int mine = parent[p.node];
@@ -167,7 +163,7 @@ NPCD_CC_HD void cc_merge_node(const CcGrid& g, int brick, int l, int32_t* parent
 // piece's nodes on to the component's root -- one integer addition per piece, not per node.  Only a component's root receives
 // additions and only a piece's root that is not one clears its own entry: no entry is both.
 template <class Ops>
-NPCD_CC_HD void cc_final_node(const int32_t* parent, int node, int32_t* labels, int32_t* sizes) {
+NPCD_HD void cc_final_node(const int32_t* parent, int node, int32_t* labels, int32_t* sizes) {
     const int label = parent[node] < 0 ? -1 : cc_root<CcPlain>(parent, node);
     labels[node] = label;
     if (label < 0 || label == node) return;

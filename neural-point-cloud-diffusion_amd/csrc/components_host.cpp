@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "components.h"
+#include "host_lanes.h"
 
 using namespace npcd;
 
@@ -30,7 +31,7 @@ int main(int argc, char** argv) {
     std::fclose(in);
     // poisoned: the phases write every entry they promise
     std::vector<int32_t> parent(vol.size(), -7), labels(vol.size(), -7), sizes(vol.size(), -7);
-    const auto order = [reverse](int i, int count) { return reverse ? count - 1 - i : i; };
+    const LaneOrder order{reverse};
     for (int b = 0; b < B; ++b) {
         const size_t base = (size_t)b * g.n;
         for (int w = 0; w < g.bricks; ++w) {          // tile phase: one workgroup per brick, a barrier between the steps

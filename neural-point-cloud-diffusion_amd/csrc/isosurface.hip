@@ -19,8 +19,8 @@
 // order, so a strip's output is one contiguous range.
 //   count: a node reads its own sample and the seven at the upper ends of its edges (the other seven corners of its cell), and
 //          writes one word: bits 0-6 the crossed edge types, bit 7 "inside", bits 8.. the vertices of its strip before it
-//          (an exclusive scan: wave_scan_incl of wave.h, then the 16 wave totals through LDS).  The strip's vertex and triangle
-//          totals go to two small arrays.
+//          (the exclusive form of block_scan, block_scan.h).  The strip's vertex and triangle totals go to two small
+//          arrays.
 //   scan:  one workgroup per volume turns the strips' totals into exclusive bases, in place, and writes counts[b] = (V, F).
 //   emit:  the owner writes its vertices; a cell reads the eight words of its corners -- "inside" bits and vertex bases, the volume is
 //          not read again for the faces -- scans the triangle counts over the strip as before and writes its triangles.  The index
@@ -37,6 +37,7 @@
 // Bounds.  A neighbour is read only where the node has one on that axis; a lane past the volume's last node reads and writes
 // nothing and scans zeros.  7 gz gy gx < 2^31 (checked), so node, vertex and strip indices are ints; byte offsets and the
 // triangle bases are 64 bits.
+#include "block_scan.h"
 #include "common.h"
 
 namespace npcd {
@@ -155,24 +156,6 @@ __device__ __forceinline__ IsoNode iso_node(const IsoArgs& a, int wg, int tid) {
     return p;
 }
 
-// exclusive scan over the workgroup in lane order, and the total; every lane calls it
-__device__ __forceinline__ uint64_t iso_block_scan(uint64_t v, uint64_t* wave_total, uint64_t* total) {
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
-    const uint64_t incl = wave_scan_incl(v, (uint64_t)0, [](uint64_t x, uint64_t y) { return x + y; });
-    if (lane == kWave - 1) wave_total[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kIsoWaves; ++w) {
-        const uint64_t t = wave_total[w];
-        before += w < wave ? t : 0;
-        all += t;
-    }
-    __syncthreads();          // the totals may be written again
-    *total = all;
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(kIsoThreads) void iso_count_kernel(IsoArgs a) {
     __shared__ uint64_t wave_total[kIsoWaves];
     const int b = blockIdx.x / a.W, wg = blockIdx.x - b * a.W;
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(kIsoThreads) void iso_count_kernel(IsoArgs a) {
     }
     const uint32_t nv = __builtin_popcount(mask), nt = p.cell() ? iso_cell_tris(in8) : 0;
     uint64_t total;
-    const uint64_t before = iso_block_scan((uint64_t)nt << 32 | nv, wave_total, &total);
+    const uint64_t before = block_scan<kIsoThreads, false>((uint64_t)nt << 32 | nv, wave_total, &total);
     if (p.valid) a.words[(int64_t)b * a.n + p.node] = mask | (in8 & 1) << 7 | (uint32_t)before << 8;
     if (threadIdx.x == 0) {
         a.wg_verts[blockIdx.x] = (int32_t)(uint32_t)total;
@@ -208,8 +191,8 @@ __global__ __launch_bounds__(kIsoThreads) void iso_scan_kernel(IsoArgs a) {
         const bool live = i < a.W;
         const uint64_t v = live ? (uint64_t)verts[i] : 0, t = live ? (uint64_t)tris[i] : 0;
         uint64_t total_v, total_t;
-        const uint64_t before_v = iso_block_scan(v, wave_total, &total_v);
-        const uint64_t before_t = iso_block_scan(t, wave_total, &total_t);
+        const uint64_t before_v = block_scan<kIsoThreads, false>(v, wave_total, &total_v);
+        const uint64_t before_t = block_scan<kIsoThreads, false>(t, wave_total, &total_t);
         if (live) {
             verts[i] = (int32_t)(carry_v + before_v);
             tris[i] = (int64_t)(carry_t + before_t);
@@ -285,7 +268,7 @@ __global__ __launch_bounds__(kIsoThreads) void iso_emit_kernel(IsoArgs a) {
     }
     const int nt = iso_cell_tris(in8);          // 0 off the cells: in8 is 0 there
     uint64_t total;
-    const uint64_t before = iso_block_scan((uint64_t)nt, wave_total, &total);
+    const uint64_t before = block_scan<kIsoThreads, false>((uint64_t)nt, wave_total, &total);
     if (nt) {
         int32_t* f = a.faces + (a.face_off[b] + a.wg_tris[blockIdx.x] + (int64_t)before) * 3;
         f = iso_emit_tet<0>(in8, w, vb, f);

@@ -19,9 +19,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
-#include "smooth.h"          // simp_bits, simp_float, sm_finite, sm_lost
+#include "bits.h"
 
 namespace npcd {
 
@@ -43,12 +42,12 @@ struct alignas(16) MdBox {          // one tile
     int32_t count;          // the corners inside: 0 for a tile that is always skipped
 };
 
-NPCD_SIMP_HD int64_t md_tiles(int64_t F) { return (F + kMdTile - 1) / kMdTile; }
-NPCD_SIMP_HD float md_dot(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
+NPCD_HD int64_t md_tiles(int64_t F) { return (F + kMdTile - 1) / kMdTile; }
+NPCD_HD float md_dot(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
 
 // ---- one pair -------------------------------------------------------------------------------------------------------------------------
 // -> dist2; q [3] the closest point
-NPCD_SIMP_HD float md_pair(const float* p, const float* a, const float* b, const float* c, float* q) {
+NPCD_HD float md_pair(const float* p, const float* a, const float* b, const float* c, float* q) {
     const float abx = b[0] - a[0], aby = b[1] - a[1], abz = b[2] - a[2];
     const float acx = c[0] - a[0], acy = c[1] - a[1], acz = c[2] - a[2];
     const float apx = p[0] - a[0], apy = p[1] - a[1], apz = p[2] - a[2];
@@ -91,18 +90,18 @@ NPCD_SIMP_HD float md_pair(const float* p, const float* a, const float* b, const
 
 // ---- the winner -----------------------------------------------------------------------------------------------------------------------
 // (dist2, face) replaces (best, best_face) if it is below it lexicographically; a NaN and +inf never do
-NPCD_SIMP_HD bool md_better(float dist2, int32_t face, float best, int32_t best_face) {
+NPCD_HD bool md_better(float dist2, int32_t face, float best, int32_t best_face) {
     return (dist2 < best) | ((dist2 == best) & (face < best_face));
 }
 // the same order on one word: a dist2 that cannot win (NaN, +inf) gives kMdNoKey
-NPCD_SIMP_HD uint64_t md_key(float dist2, int32_t face) {
-    return dist2 < simp_float(kMdInfBits) ? ((uint64_t)simp_bits(dist2) << 32) | (uint32_t)face : kMdNoKey;
+NPCD_HD uint64_t md_key(float dist2, int32_t face) {
+    return dist2 < bits_float(kMdInfBits) ? ((uint64_t)float_bits(dist2) << 32) | (uint32_t)face : kMdNoKey;
 }
 
 // ---- one face of the corners launch -----------------------------------------------------------------------------------------------------
 // out [3]: the corners of face f, NaN where the face does not take part (or f >= F).  -> true if it takes part
-NPCD_SIMP_HD bool md_corners_lane(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int64_t f, MdCorner* out) {
-    const float nan = simp_float(0x7fc00000u);
+NPCD_HD bool md_corners_lane(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int64_t f, MdCorner* out) {
+    const float nan = bits_float(0x7fc00000u);
     bool valid = f < F;
     int64_t idx[3] = {0, 0, 0};
     if (valid)
@@ -121,24 +120,24 @@ NPCD_SIMP_HD bool md_corners_lane(const float* vertices, int64_t V, const int32_
     return valid;
 }
 // a corner joins a box if its three coordinates are finite
-NPCD_SIMP_HD bool md_corner_counts(const MdCorner& c) { return sm_finite(c.x) && sm_finite(c.y) && sm_finite(c.z); }
-NPCD_SIMP_HD uint32_t md_abs_bits(const MdCorner& c) {
-    const uint32_t x = simp_bits(c.x) & 0x7fffffffu, y = simp_bits(c.y) & 0x7fffffffu, z = simp_bits(c.z) & 0x7fffffffu;
+NPCD_HD bool md_corner_counts(const MdCorner& c) { return is_finite(c.x) && is_finite(c.y) && is_finite(c.z); }
+NPCD_HD uint32_t md_abs_bits(const MdCorner& c) {
+    const uint32_t x = float_bits(c.x) & 0x7fffffffu, y = float_bits(c.y) & 0x7fffffffu, z = float_bits(c.z) & 0x7fffffffu;
     return x > y ? (x > z ? x : z) : (y > z ? y : z);
 }
 // 8 ulp of a finite |coordinate| given by its bits: 2^-20 of the power of two at or below it, at least 8 times the smallest float
-NPCD_SIMP_HD float md_slack(uint32_t abs_bits) {
-    const float unit = simp_float(abs_bits & kMdInfBits) * 9.5367431640625e-07f;          // 2^-20, exact or a denormal power of two
-    const float least = simp_float(8u);
+NPCD_HD float md_slack(uint32_t abs_bits) {
+    const float unit = bits_float(abs_bits & kMdInfBits) * 9.5367431640625e-07f;          // 2^-20, exact or a denormal power of two
+    const float least = bits_float(8u);
     return unit > least ? unit : least;
 }
-NPCD_SIMP_HD float md_point_slack(const float* p) {
+NPCD_HD float md_point_slack(const float* p) {
     const MdCorner c = {p[0], p[1], p[2], 0.f};
-    return md_corner_counts(c) ? md_slack(md_abs_bits(c)) : simp_float(8u);
+    return md_corner_counts(c) ? md_slack(md_abs_bits(c)) : bits_float(8u);
 }
 // the box of `n` corners (n a multiple of three, NaN corners do not count)
-NPCD_SIMP_HD MdBox md_box_of(const MdCorner* corners, int64_t n) {
-    const float inf = simp_float(kMdInfBits);
+NPCD_HD MdBox md_box_of(const MdCorner* corners, int64_t n) {
+    const float inf = bits_float(kMdInfBits);
     MdBox box = {{inf, inf, inf}, 0.f, {-inf, -inf, -inf}, 0};
     uint32_t top = 0;
     for (int64_t j = 0; j < n; ++j) {
@@ -155,7 +154,7 @@ NPCD_SIMP_HD MdBox md_box_of(const MdCorner* corners, int64_t n) {
 }
 
 // ---- one (point, tile) of the query launch ----------------------------------------------------------------------------------------------
-NPCD_SIMP_HD float md_bound(const float* p, float point_slack, const MdBox& box) {
+NPCD_HD float md_bound(const float* p, float point_slack, const MdBox& box) {
     const float slack = box.slack > point_slack ? box.slack : point_slack;
     float g[3];
     for (int k = 0; k < 3; ++k) {
@@ -165,6 +164,6 @@ NPCD_SIMP_HD float md_bound(const float* p, float point_slack, const MdBox& box)
     }
     return md_dot(g[0], g[1], g[2], g[0], g[1], g[2]);
 }
-NPCD_SIMP_HD bool md_needs(float bound, float best) { return !(bound > best) & (bound < simp_float(kMdInfBits)); }
+NPCD_HD bool md_needs(float bound, float best) { return !(bound > best) & (bound < bits_float(kMdInfBits)); }
 
 }  // namespace npcd

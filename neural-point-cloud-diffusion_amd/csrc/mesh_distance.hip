@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kMdTile) void md_boxes_kernel(const float* __restri
     const MdBox own = md_box_of(c, 3);
     float v[8] = {own.lo[0], own.lo[1], own.lo[2], own.hi[0], own.hi[1], own.hi[2], 0.f, (float)own.count};
     for (int k = 0; k < 3; ++k)
-        if (md_corner_counts(c[k])) v[6] = fmaxf(v[6], simp_float(md_abs_bits(c[k])));
+        if (md_corner_counts(c[k])) v[6] = fmaxf(v[6], bits_float(md_abs_bits(c[k])));
     for (int k = 0; k < 3; ++k) v[k] = wave_reduce64(v[k], [](float a, float b) { return fminf(a, b); });
     for (int k = 3; k < 7; ++k) v[k] = wave_max64(v[k]);
     v[7] = wave_sum64(v[7]);          // at most 768: exact
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kMdTile) void md_boxes_kernel(const float* __restri
             for (int k = 3; k < 7; ++k) v[k] = fmaxf(v[k], part[w][k]);
             v[7] += part[w][7];
         }
-        MdBox box = {{v[0], v[1], v[2]}, md_slack(simp_bits(v[6])), {v[3], v[4], v[5]}, (int32_t)v[7]};
+        MdBox box = {{v[0], v[1], v[2]}, md_slack(float_bits(v[6])), {v[3], v[4], v[5]}, (int32_t)v[7]};
         ws.boxes[blockIdx.x] = box;
     }
 }
@@ -102,10 +102,10 @@ __global__ __launch_bounds__(kMdThreads) void md_query_kernel(MdArgs a) {
     __shared__ MdCorner tile[kMdTile * 3];
     const int64_t i = (int64_t)blockIdx.x * kMdThreads + threadIdx.x;
     const bool own = i < a.S;
-    const float nan = simp_float(0x7fc00000u);
+    const float nan = bits_float(0x7fc00000u);
     const float p[3] = {own ? a.points[i * 3] : nan, own ? a.points[i * 3 + 1] : nan, own ? a.points[i * 3 + 2] : nan};
     const int tiles = (int)md_tiles(a.F);
-    float best = simp_float(kMdInfBits);
+    float best = bits_float(kMdInfBits);
     int32_t best_face = -1;
     unsigned evaluated = 0;
     const float point_slack = md_point_slack(p);
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kMdThreads) void md_query_kernel(MdArgs a) {
     if (CULL) {
         // every lane's tile with the smallest bound, the lowest such, is evaluated first: the lane would need it anyway, and the walk
         // then starts with a best that is near the final one
-        float least = simp_float(kMdInfBits);
+        float least = bits_float(kMdInfBits);
         for (int t0 = 0; t0 < tiles; t0 += kMdScan) {
             float bound[kMdScan];
 #pragma unroll
@@ -170,7 +170,6 @@ static int md_check(int64_t V, int64_t F) {
     if (V >= kMdMaxVertices || F >= kMdMaxFaces) return NPCD_ERR_UNSUPPORTED;
     return NPCD_OK;
 }
-static inline bool md_misaligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0; }
 
 }  // namespace npcd
 
@@ -187,7 +186,7 @@ extern "C" int npcd_mesh_distance_boxes(const float* vertices, int64_t V, const 
     const int rc = md_check(V, F);
     if (rc != NPCD_OK) return rc;
     if (F < 1 || !faces || !ws || (V > 0 && !vertices)) return NPCD_ERR_ARG;
-    if (md_misaligned(vertices, 4) || md_misaligned(faces, 4) || md_misaligned(ws, 16)) return NPCD_ERR_ARG;
+    if (misaligned(vertices, 4) || misaligned(faces, 4) || misaligned(ws, 16)) return NPCD_ERR_ARG;
     MdWs w;
     md_ws_layout(ws, F, &w);
     hipLaunchKernelGGL(md_boxes_kernel, dim3((unsigned)md_tiles(F)), dim3(kMdTile), 0, static_cast<hipStream_t>(stream), vertices, V, faces,
@@ -204,14 +203,14 @@ extern "C" int npcd_mesh_distance_query(const float* points, int64_t S, const fl
     if (S < 0) return NPCD_ERR_ARG;
     if (S >= kMdMaxPoints) return NPCD_ERR_UNSUPPORTED;
     if (S < 1 || F < 1 || !points || !ws || !sqdist || !face || !closest || (cull != 0 && cull != 1)) return NPCD_ERR_ARG;
-    if (md_misaligned(points, 4) || md_misaligned(sqdist, 4) || md_misaligned(face, 4) || md_misaligned(closest, 4) ||
-        md_misaligned(ws, 16) || md_misaligned(evaluated, 8))
+    if (misaligned(points, 4) || misaligned(sqdist, 4) || misaligned(face, 4) || misaligned(closest, 4) ||
+        misaligned(ws, 16) || misaligned(evaluated, 8))
         return NPCD_ERR_ARG;
     (void)vertices, (void)faces;          // the corners in the workspace are what the query reads
     MdWs w;
     md_ws_layout(const_cast<void*>(ws), F, &w);
     const MdArgs a{points, w.boxes, w.corners, sqdist, closest, face, reinterpret_cast<unsigned long long*>(evaluated), S, F};
-    const dim3 grid((unsigned)((S + kMdThreads - 1) / kMdThreads)), block(kMdThreads);
+    const dim3 grid(blocks_for(S, kMdThreads)), block(kMdThreads);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (cull)
         hipLaunchKernelGGL(md_query_kernel<true>, grid, block, 0, s, a);

@@ -14,14 +14,10 @@
 #include <cstring>
 #include <vector>
 
+#include "host_lanes.h"
 #include "mesh_distance.h"
 
 using namespace npcd;
-
-template <class T>
-static bool read_all(FILE* f, std::vector<T>& v) { return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size(); }
-template <class T>
-static bool write_all(FILE* f, const std::vector<T>& v) { return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
 
 struct Result {
     std::vector<float> sqdist, closest;
@@ -57,12 +53,13 @@ int main(int argc, char** argv) {
     if (!read_all(in, points) || !read_all(in, vertices) || !read_all(in, faces)) return 2;
     std::fclose(in);
     const int64_t tiles = md_tiles(F);
+    const LaneOrder order{reverse};
     // ---- the boxes launch ----------------------------------------------------------------------------------------------------------------
     const MdCorner poison = {-7.f, -7.f, -7.f, -7.f};
     std::vector<MdCorner> corners((size_t)tiles * kMdTile * 3, poison);
     std::vector<MdBox> boxes(tiles);
     for (int64_t l = 0; l < tiles * kMdTile; ++l) {
-        const int64_t f = reverse ? tiles * kMdTile - 1 - l : l;
+        const int64_t f = order(l, tiles * kMdTile);
         md_corners_lane(vertices.data(), V, faces.data(), F, f, corners.data() + f * 3);
     }
     for (int64_t t = 0; t < tiles; ++t) boxes[t] = md_box_of(corners.data() + t * kMdTile * 3, kMdTile * 3);
@@ -76,7 +73,7 @@ int main(int argc, char** argv) {
         for (int64_t t = 0; t < tiles; ++t) bound[t] = md_bound(p, point_slack, boxes[t]);
         uint64_t best = kMdNoKey;
         for (int64_t l = 0; l < F; ++l) {
-            const int64_t f = reverse ? F - 1 - l : l;
+            const int64_t f = order(l, F);
             float q[3];
             const float d = pair_of(p, corners, f, q);
             const uint64_t key = md_key(d, (int32_t)f);
@@ -84,13 +81,13 @@ int main(int argc, char** argv) {
             const float b = bound[f / kMdTile];
             if (key != kMdNoKey && !md_needs(b, d)) violations += 1;          // a face that can win, in a tile that a lane with this best skips
         }
-        finish(p, corners, simp_float((uint32_t)(best >> 32)), (int32_t)(uint32_t)best, i, all);
+        finish(p, corners, bits_float((uint32_t)(best >> 32)), (int32_t)(uint32_t)best, i, all);
     }
     // ---- the culled walk of the kernel, a wave of one lane ---------------------------------------------------------------------------------
     for (int64_t i = 0; i < S; ++i) {
         const float* p = points.data() + i * 3;
         const float point_slack = md_point_slack(p);
-        float best = simp_float(kMdInfBits), least = best;
+        float best = bits_float(kMdInfBits), least = best;
         int32_t best_face = -1;
         int64_t nearest = -1;
         const auto evaluate = [&](int64_t t) {
@@ -107,7 +104,7 @@ int main(int argc, char** argv) {
         }
         if (nearest >= 0) evaluate(nearest);
         for (int64_t l = 0; l < tiles; ++l) {
-            const int64_t t = reverse ? tiles - 1 - l : l;
+            const int64_t t = order(l, tiles);
             if (t == nearest) continue;
             if (md_needs(md_bound(p, point_slack, boxes[t]), best)) evaluate(t);
         }

@@ -17,13 +17,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
-#if defined(__HIPCC__)
-#define NPCD_SIMP_HD __host__ __device__ __forceinline__
-#else
-#define NPCD_SIMP_HD inline
-#endif
+#include "bits.h"
 
 namespace npcd {
 
@@ -41,35 +36,13 @@ struct SimpGrid {
     int dims[3];
 };
 
-NPCD_SIMP_HD uint32_t simp_bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-NPCD_SIMP_HD float simp_float(uint32_t u) {
-    float x;
-    memcpy(&x, &u, 4);
-    return x;
-}
-// 2^k as a float64, k in [-1022, 1023]
-NPCD_SIMP_HD double simp_pow2(int k) {
-    const uint64_t u = (uint64_t)(k + 1023) << 52;
-    double x;
-    memcpy(&x, &u, 8);
-    return x;
-}
-NPCD_SIMP_HD int simp_popcount(uint32_t w) {
-    w = w - ((w >> 1) & 0x55555555u);
-    w = (w & 0x33333333u) + ((w >> 2) & 0x33333333u);
-    return (int)((((w + (w >> 4)) & 0x0f0f0f0fu) * 0x01010101u) >> 24);
-}
-NPCD_SIMP_HD int64_t simp_cells(const int* dims) { return (int64_t)dims[0] * dims[1] * dims[2]; }
-NPCD_SIMP_HD int64_t simp_words(int64_t cells) { return (cells + 31) / 32; }
-NPCD_SIMP_HD int64_t simp_strips(int64_t entries) { return (entries + kSimpStrip - 1) / kSimpStrip; }
+NPCD_HD int64_t simp_cells(const int* dims) { return (int64_t)dims[0] * dims[1] * dims[2]; }
+NPCD_HD int64_t simp_words(int64_t cells) { return (cells + 31) / 32; }
+NPCD_HD int64_t simp_strips(int64_t entries) { return (entries + kSimpStrip - 1) / kSimpStrip; }
 
 // ---- one vertex of the mark launch ---------------------------------------------------------------------------------------------------
 // -> the key of the vertex's cell, -1 for a lost vertex (r is then 0); r [3] the place inside the cell
-NPCD_SIMP_HD int32_t simp_mark_lane(const float* v, const SimpGrid& g, uint32_t* r) {
+NPCD_HD int32_t simp_mark_lane(const float* v, const SimpGrid& g, uint32_t* r) {
     int c[3];
     bool lost = false;
     for (int a = 0; a < 3; ++a) {
@@ -90,38 +63,28 @@ NPCD_SIMP_HD int32_t simp_mark_lane(const float* v, const SimpGrid& g, uint32_t*
     }
     return (int32_t)(((int64_t)c[2] * g.dims[1] + c[1]) * g.dims[0] + c[0]);
 }
-// the bits of |a| for the integer maximum; 0 for a value that is not finite
-NPCD_SIMP_HD uint32_t simp_attr_bits(float a) {
-    const uint32_t m = simp_bits(a) & 0x7fffffffu;
-    return m < 0x7f800000u ? m : 0u;
-}
 
 // ---- attributes ------------------------------------------------------------------------------------------------------------------------
-// 30 - floor(log2 A) for A > 0 (denormals included: float64 holds every float as a normal number)
-NPCD_SIMP_HD int simp_attr_shift(uint32_t a_max_bits) {
-    const double x = (double)simp_float(a_max_bits);
-    uint64_t u;
-    memcpy(&u, &x, 8);
-    return 30 - ((int)((u >> 52) & 0x7ff) - 1023);
+// 30 - floor(log2 A) for A > 0: A maps into [2^30, 2^31), |q| <= 2^31
+NPCD_HD int simp_attr_shift(uint32_t a_max_bits) { return 30 - floor_log2(bits_float(a_max_bits)); }
+NPCD_HD int64_t simp_quantise(float a, uint32_t a_max_bits) {
+    if (a_max_bits == 0 || finite_abs_bits(a) == 0) return 0;
+    return (int64_t)rint((double)a * pow2(simp_attr_shift(a_max_bits)));
 }
-NPCD_SIMP_HD int64_t simp_quantise(float a, uint32_t a_max_bits) {
-    if (a_max_bits == 0 || simp_attr_bits(a) == 0) return 0;
-    return (int64_t)rint((double)a * simp_pow2(simp_attr_shift(a_max_bits)));
-}
-NPCD_SIMP_HD float simp_attr_mean(int64_t sum, uint32_t n, uint32_t a_max_bits) {
+NPCD_HD float simp_attr_mean(int64_t sum, uint32_t n, uint32_t a_max_bits) {
     if (a_max_bits == 0) return 0.f;
-    return (float)(((double)sum / (double)n) * simp_pow2(-simp_attr_shift(a_max_bits)));
+    return (float)(((double)sum / (double)n) * pow2(-simp_attr_shift(a_max_bits)));
 }
 
 // ---- the rank of a cell ---------------------------------------------------------------------------------------------------------------
 // word_before: per bitmap word the set bits of its strip before it; strip_before: per strip the set bits before it
-NPCD_SIMP_HD int32_t simp_cluster_of(int32_t key, const uint32_t* bitmap, const uint32_t* word_before, const uint32_t* strip_before) {
+NPCD_HD int32_t simp_cluster_of(int32_t key, const uint32_t* bitmap, const uint32_t* word_before, const uint32_t* strip_before) {
     const int32_t w = key >> 5;
-    return (int32_t)(strip_before[w / kSimpStrip] + word_before[w] + (uint32_t)simp_popcount(bitmap[w] & ((1u << (key & 31)) - 1u)));
+    return (int32_t)(strip_before[w / kSimpStrip] + word_before[w] + (uint32_t)popcount32(bitmap[w] & ((1u << (key & 31)) - 1u)));
 }
 
 // ---- one cluster of the finish launch -------------------------------------------------------------------------------------------------
-NPCD_SIMP_HD void simp_position(int32_t key, const uint64_t* S, uint32_t n, const SimpGrid& g, float* out) {
+NPCD_HD void simp_position(int32_t key, const uint64_t* S, uint32_t n, const SimpGrid& g, float* out) {
     const int c[3] = {key % g.dims[0], (key / g.dims[0]) % g.dims[1], key / g.dims[0] / g.dims[1]};
     for (int a = 0; a < 3; ++a) out[a] = (float)(g.origin[a] + g.cell[a] * ((double)c[a] + ((double)S[a] / (double)n) * 0x1p-32));
 }
@@ -129,7 +92,7 @@ NPCD_SIMP_HD void simp_position(int32_t key, const uint64_t* S, uint32_t n, cons
 // ---- one face --------------------------------------------------------------------------------------------------------------------------
 // the clusters of the corners to m [3], corner order kept; false (and m = -1, -1, -1) for a face that goes: an index outside [0, V) --
 // nothing is read through it --, a lost corner or two corners in one cluster
-NPCD_SIMP_HD bool simp_face_lane(const int32_t* face, const int32_t* vertex_cluster, int V, int32_t* m) {
+NPCD_HD bool simp_face_lane(const int32_t* face, const int32_t* vertex_cluster, int V, int32_t* m) {
     bool ok = true;
     for (int k = 0; k < 3; ++k) {
         const int i = face[k];
@@ -140,7 +103,7 @@ NPCD_SIMP_HD bool simp_face_lane(const int32_t* face, const int32_t* vertex_clus
     if (!ok) m[0] = m[1] = m[2] = -1;
     return ok;
 }
-NPCD_SIMP_HD void simp_sorted(const int32_t* m, int32_t* s) {
+NPCD_HD void simp_sorted(const int32_t* m, int32_t* s) {
     int32_t a = m[0], b = m[1], c = m[2], t;
     if (a > b) t = a, a = b, b = t;
     if (b > c) t = b, b = c, c = t;
@@ -148,7 +111,7 @@ NPCD_SIMP_HD void simp_sorted(const int32_t* m, int32_t* s) {
     s[0] = a, s[1] = b, s[2] = c;
 }
 // the sort keys of a mapped face (m[0] < 0: not valid): one packed key (key_hi null; every id below 2^21) or two
-NPCD_SIMP_HD void simp_face_keys(const int32_t* m, int64_t* key_hi, int64_t* key_lo) {
+NPCD_HD void simp_face_keys(const int32_t* m, int64_t* key_hi, int64_t* key_lo) {
     if (m[0] < 0) {
         *key_lo = kSimpNoKey;
         if (key_hi) *key_hi = kSimpNoKey;
@@ -161,7 +124,7 @@ NPCD_SIMP_HD void simp_face_keys(const int32_t* m, int64_t* key_hi, int64_t* key
 }
 // position i of the sorted order: does face order[i] stay?  It is valid and the face before it in the order is not one of the same
 // sorted triple (the sort is stable: the first of a run is its lowest index).  An entry of `order` outside [0, F) is not followed.
-NPCD_SIMP_HD bool simp_keeps(const int64_t* order, int64_t i, const int32_t* mapped, int64_t F, int64_t* face) {
+NPCD_HD bool simp_keeps(const int64_t* order, int64_t i, const int32_t* mapped, int64_t F, int64_t* face) {
     *face = order[i];
     if (*face < 0 || *face >= F) return false;
     const int32_t* m = mapped + *face * 3;

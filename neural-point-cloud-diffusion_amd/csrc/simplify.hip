@@ -4,10 +4,10 @@
 //   npcd_simplify_cluster, one memset and four launches:
 //     mark        one lane per vertex: the key of its cell into vertex_cluster (-1: lost), the place inside the cell to the workspace,
 //                 the cell's bit into the occupancy bitmap by an integer OR, and the integer maximum of the bits of the finite |a| of its
-//                 attributes over the wave, then one atomicMax per wave, read first and skipped when not larger.
-//     rank        one lane per bitmap word: the exclusive sums of the popcounts inside a strip of kSimpStrip words (wave_scan_incl of
-//                 csrc/wave.h, then the four wave totals through LDS), the strip's total to its slot;
-//     totals      one workgroup: the exclusive sums of the strip totals in place, 256 at a time with a carry; V' to counts[0].
+//                 attributes (wave_publish_max of csrc/wave.h).
+//     rank        one lane per bitmap word: the exclusive sums of the popcounts inside a strip of kSimpStrip words (block_scan of
+//                 csrc/block_scan.h), the strip's total to its slot;
+//     totals      one workgroup: the exclusive sums of the strip totals in place (block_scan_totals); V' to counts[0].
 //     accumulate  one lane per vertex: its cluster = strip + word + the set bits below its own, into vertex_cluster; r, the quantised
 //                 attributes and 1 into the cluster's integer sums by 64-bit and 32-bit integer atomics at agent scope.
 //   npcd_simplify_faces, one launch: one lane per face, the mapped triple to the workspace and the sort keys of its sorted triple.
@@ -23,6 +23,7 @@
 // clamp; a cluster id is below U = min(V, cells), the rows of the sums -- an id that is not (cannot be: a workspace that is not this
 // mesh's) is dropped.  A face index outside [0, V) and an entry of `order` outside [0, F) are not followed; a kept face is written
 // only below F', the rows of the outputs.
+#include "block_scan.h"
 #include "common.h"
 #include "simplify.h"
 
@@ -70,20 +71,6 @@ struct SimpArgs {
     int64_t words;
 };
 
-struct SimpAdd {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-// inclusive sums over the kSimpThreads lanes of a workgroup; wave_total: LDS [kSimpThreads / 64].  Every lane of the workgroup calls it.
-__device__ __forceinline__ uint32_t simp_block_scan(uint32_t v, uint64_t* wave_total) {
-    uint64_t incl = wave_scan_incl((uint64_t)v, (uint64_t)0, SimpAdd());
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) incl += wave_total[w];
-    __syncthreads();          // the totals may be written again
-    return (uint32_t)incl;
-}
-
 __global__ __launch_bounds__(kSimpThreads) void simp_mark_kernel(SimpArgs a) {
     const int64_t i = (int64_t)blockIdx.x * kSimpThreads + threadIdx.x;
     uint32_t bits = 0;
@@ -94,40 +81,28 @@ __global__ __launch_bounds__(kSimpThreads) void simp_mark_kernel(SimpArgs a) {
         a.ws.r[i * 3] = r[0], a.ws.r[i * 3 + 1] = r[1], a.ws.r[i * 3 + 2] = r[2];
         if (key >= 0) __hip_atomic_fetch_or(a.ws.bitmap + (key >> 5), 1u << (key & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         for (int c = 0; c < a.C; ++c) {
-            const uint32_t m = simp_attr_bits(a.attrs[i * a.C + c]);
+            const uint32_t m = finite_abs_bits(a.attrs[i * a.C + c]);
             bits = m > bits ? m : bits;
         }
     }
-    const uint32_t top = (uint32_t)wave_max_u64(bits);          // every lane of the wave is here
-    if ((threadIdx.x & 63) == 0 && top > __hip_atomic_load(a.ws.a_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        __hip_atomic_fetch_max(a.ws.a_max, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    wave_publish_max(bits, a.ws.a_max);          // every lane of the wave is here
 }
 
 __global__ __launch_bounds__(kSimpThreads) void simp_rank_kernel(SimpArgs a) {
     __shared__ uint64_t wave_total[kSimpThreads / 64];
     const int64_t w = (int64_t)blockIdx.x * kSimpStrip + threadIdx.x;
-    const uint32_t own = w < a.words ? (uint32_t)simp_popcount(a.ws.bitmap[w]) : 0u;
-    const uint32_t incl = simp_block_scan(own, wave_total);
-    if (w < a.words) a.ws.word_before[w] = incl - own;
-    if (threadIdx.x == kSimpThreads - 1) a.ws.strip_before[blockIdx.x] = incl;
+    const uint32_t own = w < a.words ? (uint32_t)popcount32(a.ws.bitmap[w]) : 0u;
+    uint64_t total;
+    const uint32_t before = (uint32_t)block_scan<kSimpThreads, false>(own, wave_total, &total);
+    if (w < a.words) a.ws.word_before[w] = before;
+    if (threadIdx.x == 0) a.ws.strip_before[blockIdx.x] = (uint32_t)total;
 }
 
 // one workgroup: totals [n] to their exclusive sums in place, the sum of all to *out
 __global__ __launch_bounds__(kSimpThreads) void simp_totals_kernel(uint32_t* totals, int64_t n, int64_t* out) {
     __shared__ uint64_t wave_total[kSimpThreads / 64];
-    __shared__ uint32_t last;
-    uint32_t carry = 0;
-    for (int64_t first = 0; first < n; first += kSimpThreads) {          // the same trips for every lane
-        const int64_t t = first + threadIdx.x;
-        const uint32_t own = t < n ? totals[t] : 0u;
-        const uint32_t incl = carry + simp_block_scan(own, wave_total);
-        if (t < n) totals[t] = incl - own;
-        if (threadIdx.x == kSimpThreads - 1) last = incl;
-        __syncthreads();
-        carry = last;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = (int64_t)carry;
+    const uint64_t sum = block_scan_totals<kSimpThreads, false>(totals, n, wave_total);
+    if (threadIdx.x == 0) *out = (int64_t)sum;
 }
 
 __global__ __launch_bounds__(kSimpThreads) void simp_accumulate_kernel(SimpArgs a) {
@@ -172,9 +147,10 @@ __global__ __launch_bounds__(kSimpThreads) void simp_flags_kernel(SimpArgs a) {
     __shared__ uint64_t wave_total[kSimpThreads / 64];
     const int64_t f = (int64_t)blockIdx.x * kSimpStrip + threadIdx.x;
     const uint32_t own = f < a.F ? a.ws.fword[f] & 1u : 0u;
-    const uint32_t incl = simp_block_scan(own, wave_total);
+    uint64_t total;
+    const uint32_t incl = (uint32_t)block_scan<kSimpThreads, true>(own, wave_total, &total);
     if (f < a.F) a.ws.fword[f] = incl << 1 | own;
-    if (threadIdx.x == kSimpThreads - 1) a.ws.fstrip[blockIdx.x] = incl;
+    if (threadIdx.x == 0) a.ws.fstrip[blockIdx.x] = (uint32_t)total;
 }
 
 __global__ __launch_bounds__(kSimpThreads) void simp_finish_kernel(SimpArgs a) {
@@ -215,8 +191,6 @@ static int simp_check(int64_t V, int64_t F, int C, const double* origin, const d
 static void simp_grid(SimpArgs* a, const double* origin, const double* cell, const int* dims) {
     for (int k = 0; k < 3; ++k) a->g.origin[k] = origin[k], a->g.cell[k] = cell[k], a->g.dims[k] = dims[k];
 }
-static inline unsigned simp_blocks(int64_t lanes) { return (unsigned)((lanes + kSimpThreads - 1) / kSimpThreads); }
-static inline bool simp_misaligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0; }
 
 }  // namespace npcd
 
@@ -238,8 +212,8 @@ extern "C" int npcd_simplify_cluster(const float* vertices, int64_t V, int64_t F
     const int rc = simp_check(V, F, C, origin_host, cell_host, dims_host, &cells);
     if (rc != NPCD_OK) return rc;
     if (V < 1 || !vertices || !ws || !vertex_cluster || !counts || (C > 0) != (attributes != nullptr)) return NPCD_ERR_ARG;
-    if (simp_misaligned(ws, 8) || simp_misaligned(counts, 8) || simp_misaligned(vertices, 4) || simp_misaligned(vertex_cluster, 4) ||
-        simp_misaligned(attributes, 4))
+    if (misaligned(ws, 8) || misaligned(counts, 8) || misaligned(vertices, 4) || misaligned(vertex_cluster, 4) ||
+        misaligned(attributes, 4))
         return NPCD_ERR_ARG;
     SimpArgs a{};
     a.vertices = vertices, a.attrs = attributes, a.vertex_cluster = vertex_cluster;
@@ -249,13 +223,13 @@ extern "C" int npcd_simplify_cluster(const float* vertices, int64_t V, int64_t F
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t strips = simp_strips(a.words);
     NPCD_HIP_CHECK(hipMemsetAsync(ws, 0, (size_t)a.ws.zeroed, s));
-    hipLaunchKernelGGL(simp_mark_kernel, dim3(simp_blocks(V)), dim3(kSimpThreads), 0, s, a);
+    hipLaunchKernelGGL(simp_mark_kernel, dim3(blocks_for(V, kSimpThreads)), dim3(kSimpThreads), 0, s, a);
     NPCD_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(simp_rank_kernel, dim3((unsigned)strips), dim3(kSimpThreads), 0, s, a);
     NPCD_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(simp_totals_kernel, dim3(1), dim3(kSimpThreads), 0, s, a.ws.strip_before, strips, counts);
     NPCD_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(simp_accumulate_kernel, dim3(simp_blocks(V)), dim3(kSimpThreads), 0, s, a);
+    hipLaunchKernelGGL(simp_accumulate_kernel, dim3(blocks_for(V, kSimpThreads)), dim3(kSimpThreads), 0, s, a);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
@@ -266,8 +240,8 @@ extern "C" int npcd_simplify_faces(const int32_t* faces, int64_t V, int64_t F, i
     const int rc = simp_check(V, F, C, nullptr, nullptr, dims_host, &cells);
     if (rc != NPCD_OK) return rc;
     if (V < 1 || F < 1 || !faces || !vertex_cluster || !ws || !key_lo) return NPCD_ERR_ARG;
-    if (simp_misaligned(ws, 8) || simp_misaligned(key_hi, 8) || simp_misaligned(key_lo, 8) || simp_misaligned(faces, 4) ||
-        simp_misaligned(vertex_cluster, 4))
+    if (misaligned(ws, 8) || misaligned(key_hi, 8) || misaligned(key_lo, 8) || misaligned(faces, 4) ||
+        misaligned(vertex_cluster, 4))
         return NPCD_ERR_ARG;
     // one packed key holds cluster ids below 2^21 only: with more rows than that the caller sorts by two keys
     if (!key_hi && simp_rows(V, cells) > kSimpPackedIds) return NPCD_ERR_ARG;
@@ -275,7 +249,8 @@ extern "C" int npcd_simplify_faces(const int32_t* faces, int64_t V, int64_t F, i
     a.faces = faces, a.vertex_cluster = const_cast<int32_t*>(vertex_cluster), a.key_hi = key_hi, a.key_lo = key_lo;
     a.V = (int)V, a.F = (int)F, a.C = C;
     simp_ws_layout(ws, V, F, C, cells, &a.ws);
-    hipLaunchKernelGGL(simp_faces_kernel, dim3(simp_blocks(F)), dim3(kSimpThreads), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(simp_faces_kernel, dim3(blocks_for(F, kSimpThreads)), dim3(kSimpThreads), 0, static_cast<hipStream_t>(stream),
+                       a);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
@@ -286,14 +261,14 @@ extern "C" int npcd_simplify_unique(const int64_t* order, int64_t V, int64_t F, 
     const int rc = simp_check(V, F, C, nullptr, nullptr, dims_host, &cells);
     if (rc != NPCD_OK) return rc;
     if (V < 1 || F < 1 || !order || !ws || !counts) return NPCD_ERR_ARG;
-    if (simp_misaligned(ws, 8) || simp_misaligned(order, 8) || simp_misaligned(counts, 8)) return NPCD_ERR_ARG;
+    if (misaligned(ws, 8) || misaligned(order, 8) || misaligned(counts, 8)) return NPCD_ERR_ARG;
     SimpArgs a{};
     a.order = order, a.V = (int)V, a.F = (int)F, a.C = C;
     simp_ws_layout(ws, V, F, C, cells, &a.ws);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t strips = simp_strips(F);
     NPCD_HIP_CHECK(hipMemsetAsync(a.ws.fword, 0, (size_t)F * 4, s));
-    hipLaunchKernelGGL(simp_unique_kernel, dim3(simp_blocks(F)), dim3(kSimpThreads), 0, s, a);
+    hipLaunchKernelGGL(simp_unique_kernel, dim3(blocks_for(F, kSimpThreads)), dim3(kSimpThreads), 0, s, a);
     NPCD_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(simp_flags_kernel, dim3((unsigned)strips), dim3(kSimpThreads), 0, s, a);
     NPCD_HIP_CHECK(hipGetLastError());
@@ -309,13 +284,13 @@ extern "C" int npcd_simplify_emit(int64_t V, int64_t F, int C, const double* ori
     int64_t cells;
     const int rc = simp_check(V, F, C, origin_host, cell_host, dims_host, &cells);
     if (rc != NPCD_OK) return rc;
-    if (V < 1 || !ws || simp_misaligned(ws, 8)) return NPCD_ERR_ARG;
+    if (V < 1 || !ws || misaligned(ws, 8)) return NPCD_ERR_ARG;
     if (V_out < 1 || V_out > simp_rows(V, cells) || F_out < 0 || F_out > F) return NPCD_ERR_ARG;
     if (!vertices_out || (C > 0) != (attributes_out != nullptr) || (F_out > 0) != (faces_out != nullptr) ||
         (F_out > 0) != (face_source != nullptr))
         return NPCD_ERR_ARG;
-    if (simp_misaligned(vertices_out, 4) || simp_misaligned(attributes_out, 4) || simp_misaligned(faces_out, 4) ||
-        simp_misaligned(face_source, 4))
+    if (misaligned(vertices_out, 4) || misaligned(attributes_out, 4) || misaligned(faces_out, 4) ||
+        misaligned(face_source, 4))
         return NPCD_ERR_ARG;
     SimpArgs a{};
     a.V = (int)V, a.F = (int)F, a.C = C, a.U = (int)simp_rows(V, cells), a.Vp = (int)V_out, a.Fp = (int)F_out;
@@ -323,10 +298,10 @@ extern "C" int npcd_simplify_emit(int64_t V, int64_t F, int C, const double* ori
     simp_grid(&a, origin_host, cell_host, dims_host);
     simp_ws_layout(const_cast<void*>(ws), V, F, C, cells, &a.ws);
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(simp_finish_kernel, dim3(simp_blocks(V_out)), dim3(kSimpThreads), 0, s, a);
+    hipLaunchKernelGGL(simp_finish_kernel, dim3(blocks_for(V_out, kSimpThreads)), dim3(kSimpThreads), 0, s, a);
     NPCD_HIP_CHECK(hipGetLastError());
     if (F_out > 0) {
-        hipLaunchKernelGGL(simp_compact_kernel, dim3(simp_blocks(F)), dim3(kSimpThreads), 0, s, a);
+        hipLaunchKernelGGL(simp_compact_kernel, dim3(blocks_for(F, kSimpThreads)), dim3(kSimpThreads), 0, s, a);
         NPCD_HIP_CHECK(hipGetLastError());
     }
     return NPCD_OK;

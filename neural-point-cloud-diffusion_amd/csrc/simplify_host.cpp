@@ -16,34 +16,10 @@
 #include <numeric>
 #include <vector>
 
+#include "host_lanes.h"
 #include "simplify.h"
 
 using namespace npcd;
-
-template <class T>
-static bool read_all(FILE* f, std::vector<T>& v) { return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size(); }
-template <class T>
-static bool write_all(FILE* f, const std::vector<T>& v) { return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-
-// x [n] to its exclusive sums in place, forward or from the far end; returns the total
-static uint32_t scan_exclusive(uint32_t* x, int64_t n, bool reverse) {
-    uint32_t total = 0;
-    if (!reverse) {
-        for (int64_t i = 0; i < n; ++i) {
-            const uint32_t own = x[i];
-            x[i] = total;
-            total += own;
-        }
-        return total;
-    }
-    for (int64_t i = n - 1; i >= 0; --i) total += x[i];
-    uint32_t after = 0;
-    for (int64_t i = n - 1; i >= 0; --i) {
-        after += x[i];
-        x[i] = total - after;
-    }
-    return total;
-}
 
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
@@ -65,7 +41,7 @@ int main(int argc, char** argv) {
     std::vector<int32_t> faces((size_t)F * 3);
     if (!read_all(in, vertices) || !read_all(in, faces) || !read_all(in, attrs)) return 2;
     std::fclose(in);
-    const auto order_of = [reverse](int64_t i, int64_t count) { return reverse ? count - 1 - i : i; };
+    const LaneOrder order_of{reverse};
     const int64_t U = V < cells ? V : cells, words = simp_words(cells), strips = simp_strips(words);
     // what the cluster call zeroes is zero; everything else is poisoned: the steps write every entry they promise
     std::vector<uint64_t> sums((size_t)U * (3 + C), 0);
@@ -77,14 +53,14 @@ int main(int argc, char** argv) {
         const int32_t key = simp_mark_lane(vertices.data() + i * 3, g, r.data() + i * 3);
         vertex_cluster[i] = key;
         if (key >= 0) bitmap[key >> 5] |= 1u << (key & 31);
-        for (int c = 0; c < C; ++c) a_max = std::max(a_max, simp_attr_bits(attrs[i * C + c]));
+        for (int c = 0; c < C; ++c) a_max = std::max(a_max, finite_abs_bits(attrs[i * C + c]));
     }
     for (int64_t l = 0; l < strips; ++l) {          // the rank launch
         const int64_t s = order_of(l, strips), first = s * kSimpStrip, count = std::min<int64_t>(kSimpStrip, words - first);
-        for (int64_t w = 0; w < count; ++w) word_before[first + w] = (uint32_t)simp_popcount(bitmap[first + w]);
-        strip_before[s] = scan_exclusive(word_before.data() + first, count, reverse);
+        for (int64_t w = 0; w < count; ++w) word_before[first + w] = (uint32_t)popcount32(bitmap[first + w]);
+        strip_before[s] = scan_in_place<false>(word_before.data() + first, count, reverse);
     }
-    int64_t counts[2] = {scan_exclusive(strip_before.data(), strips, reverse), 0};          // the totals launch
+    int64_t counts[2] = {scan_in_place<false>(strip_before.data(), strips, reverse), 0};          // the totals launch
     for (int64_t l = 0; l < V; ++l) {          // the accumulate launch
         const int64_t i = order_of(l, V);
         const int32_t key = vertex_cluster[i];
@@ -117,10 +93,10 @@ int main(int argc, char** argv) {
         const int64_t s = order_of(l, simp_strips(F)), first = s * kSimpStrip, count = std::min<int64_t>(kSimpStrip, F - first);
         uint32_t marks[kSimpStrip];
         for (int64_t k = 0; k < count; ++k) marks[k] = fword[first + k] & 1u;
-        fstrip[s] = scan_exclusive(marks, count, reverse);
-        for (int64_t k = 0; k < count; ++k) fword[first + k] = (marks[k] + (fword[first + k] & 1u)) << 1 | (fword[first + k] & 1u);
+        fstrip[s] = scan_in_place<true>(marks, count, reverse);
+        for (int64_t k = 0; k < count; ++k) fword[first + k] = marks[k] << 1 | (fword[first + k] & 1u);
     }
-    counts[1] = scan_exclusive(fstrip.data(), simp_strips(F), reverse);          // the totals launch
+    counts[1] = scan_in_place<false>(fstrip.data(), simp_strips(F), reverse);          // the totals launch
     const int64_t Vp = counts[0], Fp = counts[1];
     if (Vp > U || Fp > F) return 3;
     std::vector<float> vertices_out((size_t)Vp * 3, -7.f), attrs_out((size_t)Vp * C, -7.f);

@@ -20,9 +20,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
-#include "simplify.h"          // simp_bits, simp_float, simp_pow2, simp_attr_bits, simp_attr_shift
+#include "bits.h"
 
 namespace npcd {
 
@@ -44,17 +43,17 @@ struct alignas(16) SmRecord {
     uint32_t flag;
 };
 
-NPCD_SIMP_HD int64_t sm_strips(int64_t entries) { return (entries + kSmStrip - 1) / kSmStrip; }
+NPCD_HD int64_t sm_strips(int64_t entries) { return (entries + kSmStrip - 1) / kSmStrip; }
 
 // ---- one face of the keys launch ------------------------------------------------------------------------------------------------------
-NPCD_SIMP_HD bool sm_face_valid(const int32_t* f, int64_t V) {
+NPCD_HD bool sm_face_valid(const int32_t* f, int64_t V) {
     for (int k = 0; k < 3; ++k)
         if (f[k] < 0 || f[k] >= V) return false;
     return f[0] != f[1] && f[1] != f[2] && f[0] != f[2];
 }
-NPCD_SIMP_HD int64_t sm_sort_key(int32_t a, int32_t b, int backward) { return (((((int64_t)a) << 31) | (int64_t)b) << 1) | (int64_t)backward; }
+NPCD_HD int64_t sm_sort_key(int32_t a, int32_t b, int backward) { return (((((int64_t)a) << 31) | (int64_t)b) << 1) | (int64_t)backward; }
 // keys [6]: the three forward pairs, then the three backward ones
-NPCD_SIMP_HD void sm_face_keys(const int32_t* f, int64_t V, int64_t* keys) {
+NPCD_HD void sm_face_keys(const int32_t* f, int64_t V, int64_t* keys) {
     if (!sm_face_valid(f, V)) {
         for (int k = 0; k < 6; ++k) keys[k] = kSmNoKey;
         return;
@@ -64,21 +63,21 @@ NPCD_SIMP_HD void sm_face_keys(const int32_t* f, int64_t V, int64_t* keys) {
         keys[k] = sm_sort_key(a, b, 0), keys[3 + k] = sm_sort_key(b, a, 1);
     }
 }
-NPCD_SIMP_HD int64_t sm_pair(int64_t sort_key) { return sort_key >> 1; }
-NPCD_SIMP_HD int64_t sm_source(int64_t sort_key) { return sort_key >> 32; }
-NPCD_SIMP_HD int64_t sm_target(int64_t sort_key) { return (sort_key >> 1) & 0x7fffffff; }
+NPCD_HD int64_t sm_pair(int64_t sort_key) { return sort_key >> 1; }
+NPCD_HD int64_t sm_source(int64_t sort_key) { return sort_key >> 32; }
+NPCD_HD int64_t sm_target(int64_t sort_key) { return (sort_key >> 1) & 0x7fffffff; }
 
 // ---- one position of the sorted keys -------------------------------------------------------------------------------------------------
-NPCD_SIMP_HD bool sm_is_head(const int64_t* keys, int64_t p) {
+NPCD_HD bool sm_is_head(const int64_t* keys, int64_t p) {
     return keys[p] != kSmNoKey && (p == 0 || sm_pair(keys[p - 1]) != sm_pair(keys[p]));
 }
 // 1 for a head, 2^32 more for a head with a < b: both prefix sums in one
-NPCD_SIMP_HD uint64_t sm_marks(const int64_t* keys, int64_t p) {
+NPCD_HD uint64_t sm_marks(const int64_t* keys, int64_t p) {
     if (!sm_is_head(keys, p)) return 0;
     return 1u + (sm_source(keys[p]) < sm_target(keys[p]) ? (uint64_t)1 << 32 : 0);
 }
 // the last valid position holds 6 F_v - 1
-NPCD_SIMP_HD bool sm_is_last(const int64_t* keys, int64_t n, int64_t p) { return keys[p] != kSmNoKey && (p == n - 1 || keys[p + 1] == kSmNoKey); }
+NPCD_HD bool sm_is_last(const int64_t* keys, int64_t n, int64_t p) { return keys[p] != kSmNoKey && (p == n - 1 || keys[p + 1] == kSmNoKey); }
 
 struct SmEdges {          // the outputs of the emit launch
     int32_t *row_start, *neighbours, *edges, *edge_faces, *edge_forward;          // [V + 1], [D], [E, 2], [E], [E]
@@ -87,7 +86,7 @@ struct SmEdges {          // the outputs of the emit launch
 };
 // position p of n sorted keys; heads, edges: the inclusive counts of sm_marks up to and including p.  -> used | boundary 2^16 |
 // non-manifold 2^32 | misoriented 2^48, each 0 or 1.  Every index is held to its array: a key that is not this mesh's writes nothing.
-NPCD_SIMP_HD uint64_t sm_emit_lane(const int64_t* keys, int64_t n, int64_t p, int64_t heads, int64_t edges, const SmEdges& o) {
+NPCD_HD uint64_t sm_emit_lane(const int64_t* keys, int64_t n, int64_t p, int64_t heads, int64_t edges, const SmEdges& o) {
     const int64_t key = keys[p];
     if (key == kSmNoKey) return 0;
     const int64_t a = sm_source(key), b = sm_target(key);
@@ -124,18 +123,17 @@ NPCD_SIMP_HD uint64_t sm_emit_lane(const int64_t* keys, int64_t n, int64_t p, in
 }
 
 // ---- the lattice ---------------------------------------------------------------------------------------------------------------------
-NPCD_SIMP_HD bool sm_finite(float x) { return (simp_bits(x) & 0x7fffffffu) < 0x7f800000u; }
-NPCD_SIMP_HD bool sm_lost(const float* v) { return !(sm_finite(v[0]) && sm_finite(v[1]) && sm_finite(v[2])); }
-// 29 - floor(log2 A) for A > 0
-NPCD_SIMP_HD int sm_shift(uint32_t a_max_bits) { return simp_attr_shift(a_max_bits) - 1; }
+NPCD_HD bool sm_lost(const float* v) { return !(is_finite(v[0]) && is_finite(v[1]) && is_finite(v[2])); }
+// 29 - floor(log2 A) for A > 0: A maps into [2^29, 2^30), |q| <= 2^30
+NPCD_HD int sm_shift(uint32_t a_max_bits) { return 29 - floor_log2(bits_float(a_max_bits)); }
 // the row of vertex i in the adjacency, held to [0, D]
-NPCD_SIMP_HD void sm_row(const int32_t* row_start, int64_t i, int64_t D, int64_t* begin, int64_t* end) {
+NPCD_HD void sm_row(const int32_t* row_start, int64_t i, int64_t D, int64_t* begin, int64_t* end) {
     const int64_t lo = row_start[i], hi = row_start[i + 1];
     *begin = lo < 0 ? 0 : lo > D ? D : lo;
     *end = hi < *begin ? *begin : hi > D ? D : hi;
 }
 // one vertex of the quantise launch: its place on the lattice, lost or not, and whether it moves.  boundary and fixed may be null.
-NPCD_SIMP_HD SmRecord sm_quantise_lane(const float* vertices, int64_t i, int64_t V, const int32_t* row_start, const int32_t* neighbours,
+NPCD_HD SmRecord sm_quantise_lane(const float* vertices, int64_t i, int64_t V, const int32_t* row_start, const int32_t* neighbours,
                                        int64_t D, const uint8_t* boundary, const uint8_t* fixed, uint32_t a_max_bits) {
     SmRecord r = {{0, 0, 0}, 0u};
     const float* v = vertices + i * 3;
@@ -144,7 +142,7 @@ NPCD_SIMP_HD SmRecord sm_quantise_lane(const float* vertices, int64_t i, int64_t
         return r;
     }
     if (a_max_bits) {
-        const double scale = simp_pow2(sm_shift(a_max_bits));
+        const double scale = pow2(sm_shift(a_max_bits));
         for (int k = 0; k < 3; ++k) r.q[k] = (int32_t)rint((double)v[k] * scale);
     }
     if ((fixed && fixed[i]) || (boundary && boundary[i])) return r;
@@ -160,7 +158,7 @@ NPCD_SIMP_HD SmRecord sm_quantise_lane(const float* vertices, int64_t i, int64_t
     return r;
 }
 // one vertex of a step launch: the old state in `state`, -> its new record
-NPCD_SIMP_HD SmRecord sm_step_lane(const SmRecord* state, int64_t i, int64_t V, const int32_t* row_start, const int32_t* neighbours, int64_t D,
+NPCD_HD SmRecord sm_step_lane(const SmRecord* state, int64_t i, int64_t V, const int32_t* row_start, const int32_t* neighbours, int64_t D,
                                    double factor, bool from_the_end = false) {
     SmRecord own = state[i];
     if (!(own.flag & kSmMoves)) return own;
@@ -183,12 +181,12 @@ NPCD_SIMP_HD SmRecord sm_step_lane(const SmRecord* state, int64_t i, int64_t V, 
     return own;
 }
 // one vertex of the finish launch
-NPCD_SIMP_HD void sm_finish_lane(const float* in, const SmRecord& r, uint32_t a_max_bits, float* out) {
+NPCD_HD void sm_finish_lane(const float* in, const SmRecord& r, uint32_t a_max_bits, float* out) {
     if (!(r.flag & kSmMoves) || a_max_bits == 0) {
-        for (int k = 0; k < 3; ++k) out[k] = simp_float(simp_bits(in[k]));
+        for (int k = 0; k < 3; ++k) out[k] = bits_float(float_bits(in[k]));
         return;
     }
-    const double quantum = simp_pow2(-sm_shift(a_max_bits));
+    const double quantum = pow2(-sm_shift(a_max_bits));
     for (int k = 0; k < 3; ++k) out[k] = (float)((double)r.q[k] * quantum);
 }
 

@@ -4,17 +4,16 @@
 //   npcd_mesh_edges_keys, one launch: one lane per face writes its six sort keys.
 //   npcd_mesh_edges_unique, one memset and two launches over the caller's ascending order of those keys:
 //     marks       one lane per position: 1 for a head, 2^32 more for a head with a < b; the inclusive sums of both inside a strip of
-//                 kSmStrip positions (wave_scan_incl of csrc/wave.h, then the four wave totals through LDS) to the workspace, the
-//                 strip's total to its slot; the last valid position writes F_v to counts[1].
-//     totals      one workgroup: the exclusive sums of the strip totals in place, 256 at a time with a carry; D to counts[0].
+//                 kSmStrip positions (block_scan of csrc/block_scan.h) to the workspace, the strip's total to its slot; the
+//                 last valid position writes F_v to counts[1].
+//     totals      one workgroup: the exclusive sums of the strip totals in place (block_scan_totals); D to counts[0].
 //   npcd_mesh_edges_emit, one memset and two launches:
-//     emit        one lane per position, sm_emit_lane; the four counts of a strip are summed in one 64-bit word (over the wave, then
-//                 the four wave totals through LDS) and stored to the strip's slot.
+//     emit        one lane per position, sm_emit_lane; the four counts of a strip are summed in one 64-bit word (the scan's total)
+//                 and stored to the strip's slot.
 //     counts      one workgroup sums the slots and writes the four sums to counts[2..5].  No atomics: ~100,000 waves adding to one
 //                 address took 1.1 ms of a 1.9-ms call on a mesh of a million faces (docs/experiments.md R34.1).
 //   npcd_smooth_mesh, one memset and 3 + steps launches:
-//     measure     the integer maximum of the bits of the finite |coordinates| over the wave, then one atomicMax per wave, read first
-//                 and skipped when not larger.
+//     measure     the integer maximum of the bits of the finite |coordinates| (wave_publish_max of csrc/wave.h).
 //     quantise    one lane per vertex: its record (place on the lattice, lost, moves).
 //     step        one lane per vertex gathers the records of its row and writes its new record to the other buffer: no atomics.
 //     finish      one lane per vertex: fp32 of its place, or its input bits.
@@ -24,6 +23,7 @@
 // Bounds.  A lane past the last face, position or vertex reads and writes nothing (it scans 0).  An index of a face outside [0, V)
 // makes no key; a key's ends are below V and a rank below D before anything is written through them (sm_emit_lane); a row's ends are
 // held to [0, D] and a neighbour to [0, V) before the state is read through them (sm_row, sm_step_lane).
+#include "block_scan.h"
 #include "common.h"
 #include "smooth.h"
 
@@ -42,20 +42,6 @@ static inline int64_t sm_ws_layout(void* ws, int64_t F, SmWs* out) {
     return 16 * strips + 4 * n;
 }
 
-struct SmAdd {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-// inclusive sums over the kSmThreads lanes of a workgroup; wave_total: LDS [kSmThreads / 64].  Every lane of the workgroup calls it.
-__device__ __forceinline__ uint64_t sm_block_scan(uint64_t v, uint64_t* wave_total) {
-    uint64_t incl = wave_scan_incl(v, (uint64_t)0, SmAdd());
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) incl += wave_total[w];
-    __syncthreads();          // the totals may be written again
-    return incl;
-}
-
 __global__ __launch_bounds__(kSmThreads) void sm_keys_kernel(const int32_t* faces, int64_t V, int64_t F, int64_t* keys) {
     const int64_t f = (int64_t)blockIdx.x * kSmThreads + threadIdx.x;
     if (f >= F) return;
@@ -69,30 +55,20 @@ __global__ __launch_bounds__(kSmThreads) void sm_marks_kernel(const int64_t* key
     __shared__ uint64_t wave_total[kSmThreads / 64];
     const int64_t p = (int64_t)blockIdx.x * kSmStrip + threadIdx.x;
     const uint64_t own = p < n ? sm_marks(keys, p) : 0;
-    const uint64_t incl = sm_block_scan(own, wave_total);
+    uint64_t total;
+    const uint64_t incl = block_scan<kSmThreads, true>(own, wave_total, &total);
     if (p < n) {
         ws.incl[p] = (uint32_t)incl | (uint32_t)(incl >> 32) << 16;
         if (sm_is_last(keys, n, p)) counts[kSmCountFaces] = (p + 1) / 6;
     }
-    if (threadIdx.x == kSmThreads - 1) ws.strip_before[blockIdx.x] = incl;
+    if (threadIdx.x == 0) ws.strip_before[blockIdx.x] = total;
 }
 
 // one workgroup: totals [n] (two 32-bit counts in a word) to their exclusive sums in place; the low count of all to *out
 __global__ __launch_bounds__(kSmThreads) void sm_totals_kernel(uint64_t* totals, int64_t n, int64_t* out) {
     __shared__ uint64_t wave_total[kSmThreads / 64];
-    __shared__ uint64_t last;
-    uint64_t carry = 0;
-    for (int64_t first = 0; first < n; first += kSmThreads) {          // the same trips for every lane
-        const int64_t t = first + threadIdx.x;
-        const uint64_t own = t < n ? totals[t] : 0;
-        const uint64_t incl = carry + sm_block_scan(own, wave_total);
-        if (t < n) totals[t] = incl - own;
-        if (threadIdx.x == kSmThreads - 1) last = incl;
-        __syncthreads();
-        carry = last;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = (int64_t)(carry & 0xffffffffu);
+    const uint64_t sum = block_scan_totals<kSmThreads, false>(totals, n, wave_total);
+    if (threadIdx.x == 0) *out = (int64_t)(sum & 0xffffffffu);
 }
 
 __global__ __launch_bounds__(kSmThreads) void sm_emit_kernel(const int64_t* keys, int64_t n, SmWs ws, SmEdges o) {
@@ -105,8 +81,9 @@ __global__ __launch_bounds__(kSmThreads) void sm_emit_kernel(const int64_t* keys
         const uint32_t incl = ws.incl[p];
         found = sm_emit_lane(keys, n, p, (int64_t)(before & 0xffffffffu) + (incl & 0xffffu), (int64_t)(before >> 32) + (incl >> 16), o);
     }
-    const uint64_t sum = sm_block_scan(found, wave_total);          // every lane of the workgroup is here; at most 256 to a field
-    if (threadIdx.x == kSmThreads - 1) ws.strip_counts[blockIdx.x] = sum;
+    uint64_t sum;
+    block_scan<kSmThreads, true>(found, wave_total, &sum);          // every lane of the workgroup is here; at most 256 to a field
+    if (threadIdx.x == 0) ws.strip_counts[blockIdx.x] = sum;
 }
 
 // one workgroup: the four 16-bit counts of every strip summed to counts [4]
@@ -118,8 +95,9 @@ __global__ __launch_bounds__(kSmThreads) void sm_counts_kernel(const uint64_t* s
         for (int k = 0; k < 4; ++k) own[k] += (c >> (16 * k)) & 0xffffu;
     }
     for (int k = 0; k < 4; ++k) {
-        const uint64_t sum = sm_block_scan(own[k], wave_total);
-        if (threadIdx.x == kSmThreads - 1) counts[k] = (int64_t)sum;
+        uint64_t sum;
+        block_scan<kSmThreads, true>(own[k], wave_total, &sum);
+        if (threadIdx.x == 0) counts[k] = (int64_t)sum;
     }
 }
 
@@ -137,12 +115,10 @@ __global__ __launch_bounds__(kSmThreads) void sm_measure_kernel(SmArgs a) {
     uint32_t bits = 0;
     if (i < a.V)
         for (int k = 0; k < 3; ++k) {
-            const uint32_t m = simp_attr_bits(a.vertices[i * 3 + k]);
+            const uint32_t m = finite_abs_bits(a.vertices[i * 3 + k]);
             bits = m > bits ? m : bits;
         }
-    const uint32_t top = (uint32_t)wave_max_u64(bits);          // every lane of the wave is here
-    if ((threadIdx.x & 63) == 0 && top > __hip_atomic_load(a.a_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        __hip_atomic_fetch_max(a.a_max, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    wave_publish_max(bits, a.a_max);          // every lane of the wave is here
 }
 
 __global__ __launch_bounds__(kSmThreads) void sm_quantise_kernel(SmArgs a, SmRecord* state) {
@@ -171,8 +147,6 @@ static int sm_check(int64_t V, int64_t F) {
     if (V >= kSmMaxVertices || F >= kSmMaxFaces) return NPCD_ERR_UNSUPPORTED;
     return NPCD_OK;
 }
-static inline unsigned sm_blocks(int64_t lanes) { return (unsigned)((lanes + kSmThreads - 1) / kSmThreads); }
-static inline bool sm_misaligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0; }
 // the smoothing's workspace: the maximum in the first 16 bytes, then two buffers of records
 static inline int64_t sm_state_bytes(int64_t V) { return 16 + 2 * V * (int64_t)sizeof(SmRecord); }
 
@@ -190,8 +164,9 @@ extern "C" int64_t npcd_mesh_edges_ws_bytes(int64_t V, int64_t F) {
 extern "C" int npcd_mesh_edges_keys(const int32_t* faces, int64_t V, int64_t F, int64_t* keys, void* stream) {
     const int rc = sm_check(V, F);
     if (rc != NPCD_OK) return rc;
-    if (F < 1 || !faces || !keys || sm_misaligned(faces, 4) || sm_misaligned(keys, 8)) return NPCD_ERR_ARG;
-    hipLaunchKernelGGL(sm_keys_kernel, dim3(sm_blocks(F)), dim3(kSmThreads), 0, static_cast<hipStream_t>(stream), faces, V, F, keys);
+    if (F < 1 || !faces || !keys || misaligned(faces, 4) || misaligned(keys, 8)) return NPCD_ERR_ARG;
+    hipLaunchKernelGGL(sm_keys_kernel, dim3(blocks_for(F, kSmThreads)), dim3(kSmThreads), 0, static_cast<hipStream_t>(stream), faces, V, F,
+                       keys);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;
 }
@@ -200,7 +175,7 @@ extern "C" int npcd_mesh_edges_unique(const int64_t* sorted_keys, int64_t V, int
     const int rc = sm_check(V, F);
     if (rc != NPCD_OK) return rc;
     if (F < 1 || !sorted_keys || !ws || !counts) return NPCD_ERR_ARG;
-    if (sm_misaligned(sorted_keys, 8) || sm_misaligned(ws, 8) || sm_misaligned(counts, 8)) return NPCD_ERR_ARG;
+    if (misaligned(sorted_keys, 8) || misaligned(ws, 8) || misaligned(counts, 8)) return NPCD_ERR_ARG;
     SmWs w;
     sm_ws_layout(ws, F, &w);
     const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -221,8 +196,8 @@ extern "C" int npcd_mesh_edges_emit(const int64_t* sorted_keys, int64_t V, int64
     if (F < 1 || V < 1 || D < 2 || D > 6 * F || (D & 1)) return NPCD_ERR_ARG;
     if (!sorted_keys || !ws || !row_start || !neighbours || !edges || !edge_faces || !edge_forward || !boundary_vertex || !counts)
         return NPCD_ERR_ARG;
-    if (sm_misaligned(sorted_keys, 8) || sm_misaligned(ws, 8) || sm_misaligned(counts, 8) || sm_misaligned(row_start, 4) ||
-        sm_misaligned(neighbours, 4) || sm_misaligned(edges, 4) || sm_misaligned(edge_faces, 4) || sm_misaligned(edge_forward, 4))
+    if (misaligned(sorted_keys, 8) || misaligned(ws, 8) || misaligned(counts, 8) || misaligned(row_start, 4) ||
+        misaligned(neighbours, 4) || misaligned(edges, 4) || misaligned(edge_faces, 4) || misaligned(edge_forward, 4))
         return NPCD_ERR_ARG;
     SmWs w;
     sm_ws_layout(ws, F, &w);
@@ -251,8 +226,8 @@ extern "C" int npcd_smooth_mesh(const float* vertices, int64_t V, const int32_t*
     if (V < 1 || D < 0 || D >= 6 * kSmMaxFaces || iterations < 0 || iterations > kSmMaxIterations) return NPCD_ERR_ARG;
     if (!(lam > 0.0 && lam <= 1.0) || !(mu >= -1.0 && mu <= 0.0)) return NPCD_ERR_ARG;
     if (!vertices || !vertices_out || !row_start || !ws || (D > 0 && !neighbours)) return NPCD_ERR_ARG;
-    if (sm_misaligned(vertices, 4) || sm_misaligned(vertices_out, 4) || sm_misaligned(row_start, 4) || sm_misaligned(neighbours, 4) ||
-        sm_misaligned(ws, 16))
+    if (misaligned(vertices, 4) || misaligned(vertices_out, 4) || misaligned(row_start, 4) || misaligned(neighbours, 4) ||
+        misaligned(ws, 16))
         return NPCD_ERR_ARG;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (iterations == 0 || D == 0) {          // nothing moves: the input bits
@@ -262,7 +237,7 @@ extern "C" int npcd_smooth_mesh(const float* vertices, int64_t V, const int32_t*
     SmArgs a{vertices, row_start, neighbours, boundary_vertex, fixed, static_cast<uint32_t*>(ws), vertices_out, V, D};
     SmRecord* state[2] = {reinterpret_cast<SmRecord*>(static_cast<char*>(ws) + 16), nullptr};
     state[1] = state[0] + V;
-    const dim3 grid(sm_blocks(V)), block(kSmThreads);
+    const dim3 grid(blocks_for(V, kSmThreads)), block(kSmThreads);
     NPCD_HIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
     hipLaunchKernelGGL(sm_measure_kernel, grid, block, 0, s, a);
     NPCD_HIP_CHECK(hipGetLastError());

@@ -14,31 +14,10 @@
 #include <cstring>
 #include <vector>
 
+#include "host_lanes.h"
 #include "smooth.h"
 
 using namespace npcd;
-
-template <class T>
-static bool read_all(FILE* f, std::vector<T>& v) { return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size(); }
-template <class T>
-static bool write_all(FILE* f, const std::vector<T>& v) { return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-
-// x [n] (two 32-bit counts in a word) to its inclusive sums in place, forward or from the far end; returns the total
-static uint64_t scan_inclusive(uint64_t* x, int64_t n, bool reverse) {
-    uint64_t total = 0;
-    if (!reverse) {
-        for (int64_t i = 0; i < n; ++i) x[i] = total += x[i];
-        return total;
-    }
-    for (int64_t i = n - 1; i >= 0; --i) total += x[i];
-    uint64_t after = 0;
-    for (int64_t i = n - 1; i >= 0; --i) {
-        const uint64_t own = x[i];
-        x[i] = total - after;
-        after += own;
-    }
-    return total;
-}
 
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
@@ -59,7 +38,7 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> fixed(has_fixed ? V : 0);
     if (!read_all(in, vertices) || !read_all(in, faces) || !read_all(in, fixed)) return 2;
     std::fclose(in);
-    const auto order_of = [reverse](int64_t i, int64_t count) { return reverse ? count - 1 - i : i; };
+    const LaneOrder order_of{reverse};
     // ---- the edges --------------------------------------------------------------------------------------------------------------------
     const int64_t n = 6 * F, strips = sm_strips(n);
     std::vector<int64_t> keys(n, -7);
@@ -75,18 +54,13 @@ int main(int argc, char** argv) {
         const int64_t s = order_of(l, strips), first = s * kSmStrip, count = std::min<int64_t>(kSmStrip, n - first);
         uint64_t marks[kSmStrip];
         for (int64_t k = 0; k < count; ++k) marks[k] = sm_marks(keys.data(), first + k);
-        strip_before[s] = scan_inclusive(marks, count, reverse);
+        strip_before[s] = scan_in_place<true>(marks, count, reverse);
         for (int64_t k = 0; k < count; ++k) {
             incl[first + k] = (uint32_t)marks[k] | (uint32_t)(marks[k] >> 32) << 16;
             if (sm_is_last(keys.data(), n, first + k)) counts[kSmCountFaces] = (first + k + 1) / 6;
         }
     }
-    {          // the totals launch: exclusive sums in place
-        std::vector<uint64_t> own(strip_before);
-        const uint64_t total = scan_inclusive(strip_before.data(), strips, reverse);
-        for (int64_t s = 0; s < strips; ++s) strip_before[s] -= own[s];
-        counts[kSmCountD] = (int64_t)(total & 0xffffffffu);
-    }
+    counts[kSmCountD] = (int64_t)(scan_in_place<false>(strip_before.data(), strips, reverse) & 0xffffffffu);          // the totals launch
     const int64_t D = counts[kSmCountD], E = D / 2;
     if (D < 0 || D > n || (D & 1)) return 3;
     std::vector<int32_t> row_start(V + 1, D ? -7 : 0), neighbours(D, -7), edges((size_t)E * 2, -7), edge_faces(E, -7), edge_forward(E, -7);
@@ -103,7 +77,7 @@ int main(int argc, char** argv) {
     }
     // ---- the smoothing ----------------------------------------------------------------------------------------------------------------
     uint32_t a_max = 0;
-    for (int64_t l = 0; l < V * 3; ++l) a_max = std::max(a_max, simp_attr_bits(vertices[order_of(l, V * 3)]));          // the measure launch
+    for (int64_t l = 0; l < V * 3; ++l) a_max = std::max(a_max, finite_abs_bits(vertices[order_of(l, V * 3)]));          // the measure launch
     const SmRecord poison = {{-7, -7, -7}, 0xdeadbeefu};
     std::vector<SmRecord> state[2] = {std::vector<SmRecord>(V, poison), std::vector<SmRecord>(V, poison)};
     for (int64_t l = 0; l < V; ++l) {          // the quantise launch

@@ -17,13 +17,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
-#if defined(__HIPCC__)
-#define NPCD_SURF_HD __host__ __device__ __forceinline__
-#else
-#define NPCD_SURF_HD inline
-#endif
+#include "bits.h"
 
 namespace npcd {
 
@@ -37,29 +32,18 @@ constexpr int kSurfLdsTiles = 4096;
 constexpr int kSurfMaxChannels = 16;
 enum { kSurfNormalsNone = 0, kSurfNormalsFace = 1, kSurfNormalsVertex = 2 };
 
-NPCD_SURF_HD uint32_t surf_bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-NPCD_SURF_HD float surf_float(uint32_t u) {
-    float x;
-    memcpy(&x, &u, 4);
-    return x;
-}
-
 // the first tile slot of mesh b: the meshes before it fill at most floor(face_offset / kSurfTile) + b slots, and the slots of
 // consecutive meshes do not overlap; floor(F_total / kSurfTile) + B slots hold a batch
-NPCD_SURF_HD int64_t surf_tile_base(int face_offset, int b) { return (int64_t)(face_offset / kSurfTile) + b; }
-NPCD_SURF_HD int surf_tiles(int faces) { return faces / kSurfTile + (faces % kSurfTile != 0); }
-NPCD_SURF_HD int64_t surf_slots(int B, int F_total) { return (int64_t)(F_total / kSurfTile) + B; }
+NPCD_HD int64_t surf_tile_base(int face_offset, int b) { return (int64_t)(face_offset / kSurfTile) + b; }
+NPCD_HD int surf_tiles(int faces) { return faces / kSurfTile + (faces % kSurfTile != 0); }
+NPCD_HD int64_t surf_slots(int B, int F_total) { return (int64_t)(F_total / kSurfTile) + B; }
 
 // rows [first, first + count) of member b in a packed array of `total` rows; offsets [B + 1] that do not ascend inside
 // [0, total] give an empty member: nothing is read or written through them
 struct SurfSpan {
     int first, count;
 };
-NPCD_SURF_HD SurfSpan surf_span(const int32_t* offsets, int b, int total) {
+NPCD_HD SurfSpan surf_span(const int32_t* offsets, int b, int total) {
     const int lo = offsets[b], hi = offsets[b + 1];
     SurfSpan s;
     s.first = 0, s.count = 0;
@@ -68,7 +52,7 @@ NPCD_SURF_HD SurfSpan surf_span(const int32_t* offsets, int b, int total) {
 }
 // the member that owns tile slot `slot`: the largest b whose first slot is not above it (the bases ascend strictly with b); the slot
 // is one of its tiles iff slot - base < surf_tiles(F_b)
-NPCD_SURF_HD int surf_slot_member(const int32_t* face_offsets, int B, int64_t slot) {
+NPCD_HD int surf_slot_member(const int32_t* face_offsets, int B, int64_t slot) {
     int lo = 0, hi = B - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -82,7 +66,7 @@ struct SurfFace {
     float n[3], d;          // e1 x e2 and its length
 };
 // the corners, normal and measure of a face; false (and d = +0, nothing read) if an index lies outside [0, V)
-NPCD_SURF_HD bool surf_face(const float* vertices, const int32_t* face, int V, SurfFace* f) {
+NPCD_HD bool surf_face(const float* vertices, const int32_t* face, int V, SurfFace* f) {
     const int i0 = face[0], i1 = face[1], i2 = face[2];
     f->d = 0.f;
     if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) return false;
@@ -94,50 +78,38 @@ NPCD_SURF_HD bool surf_face(const float* vertices, const int32_t* face, int V, S
     f->d = d < INFINITY ? d : 0.f;          // NaN and +inf: no measure
     return true;
 }
-NPCD_SURF_HD float surf_face_measure(const float* vertices, const int32_t* face, int V) {
+NPCD_HD float surf_face_measure(const float* vertices, const int32_t* face, int V) {
     SurfFace f;
     surf_face(vertices, face, V, &f);
     return f.d;
 }
 
-// k = 31 - floor(log2 d_max) for d_max > 0 (denormals included: float64 holds every float as a normal number): -96 .. 180
-NPCD_SURF_HD int surf_shift(float d_max) {
-    const double x = (double)d_max;
-    uint64_t u;
-    memcpy(&u, &x, 8);
-    return 31 - ((int)((u >> 52) & 0x7ff) - 1023);
-}
-// 2^k as a float64, k in [-1022, 1023]
-NPCD_SURF_HD double surf_pow2(int k) {
-    const uint64_t u = (uint64_t)(k + 1023) << 52;
-    double x;
-    memcpy(&x, &u, 8);
-    return x;
-}
+// k = 31 - floor(log2 d_max) for d_max > 0: d_max maps into [2^31, 2^32); -96 .. 180
+NPCD_HD int surf_shift(float d_max) { return 31 - floor_log2(d_max); }
 // w = floor(float64(d) 2^k): the product is exact, d_max maps into [2^31, 2^32); a mesh without measure (d_max = 0) has w = 0
-NPCD_SURF_HD uint64_t surf_quantise(float d, uint32_t d_max_bits) {
+NPCD_HD uint64_t surf_quantise(float d, uint32_t d_max_bits) {
     if (d_max_bits == 0) return 0;
-    return (uint64_t)((double)d * surf_pow2(surf_shift(surf_float(d_max_bits))));
+    return (uint64_t)((double)d * pow2(surf_shift(bits_float(d_max_bits))));
 }
 // area = 0.5 float64(W) 2^-k
-NPCD_SURF_HD double surf_area(uint64_t W, uint32_t d_max_bits) {
+NPCD_HD double surf_area(uint64_t W, uint32_t d_max_bits) {
     if (d_max_bits == 0) return 0.0;
-    return 0.5 * (double)W * surf_pow2(-surf_shift(surf_float(d_max_bits)));
+    return 0.5 * (double)W * pow2(-surf_shift(bits_float(d_max_bits)));
 }
 
-NPCD_SURF_HD uint32_t surf_k0(float u0) {
+NPCD_HD uint32_t surf_k0(float u0) {
     const float t = floorf(u0 * 16777216.f);
     return !(t > 0.f) ? 0u : t >= 16777215.f ? 16777215u : (uint32_t)t;
 }
 // floor(k0 W / 2^24) for k0 < 2^24 and W < 2^63, exactly.  The product has up to 87 bits; with W = Whi 2^32 + Wlo it is
 // (k0 Whi) 2^32 + k0 Wlo, both products below 2^56, and the first term is a multiple of 2^24: floor((k0 Whi) 2^8 + k0 Wlo / 2^24)
 // = (k0 Whi) 2^8 + floor(k0 Wlo / 2^24) -- the high and the low half of the 128-bit product, without the 128-bit multiply
-NPCD_SURF_HD uint64_t surf_mul_shift(uint32_t k0, uint64_t W) {
+NPCD_HD uint64_t surf_mul_shift(uint32_t k0, uint64_t W) {
     const uint64_t hi = (uint64_t)k0 * (W >> 32), lo = (uint64_t)k0 * (W & 0xffffffffu);
     return (hi << 8) + (lo >> 24);
 }
 // the smallest i in [0, n) with a[i] > r, n if there is none; a ascending
-NPCD_SURF_HD int surf_upper_bound(const uint64_t* a, int n, uint64_t r) {
+NPCD_HD int surf_upper_bound(const uint64_t* a, int n, uint64_t r) {
     int lo = 0, hi = n;
     while (lo < hi) {          // a[i] <= r for i < lo, a[i] > r for i >= hi
         const int mid = lo + ((hi - lo) >> 1);
@@ -146,18 +118,18 @@ NPCD_SURF_HD int surf_upper_bound(const uint64_t* a, int n, uint64_t r) {
     return lo;
 }
 
-NPCD_SURF_HD void surf_barycentric(float u1, float u2, float* b) {
+NPCD_HD void surf_barycentric(float u1, float u2, float* b) {
     const float s = sqrtf(u1);
     b[0] = 1.f - s, b[1] = s * (1.f - u2), b[2] = s * u2;
 }
-NPCD_SURF_HD float surf_mix(const float* b, float x0, float x1, float x2) { return (b[0] * x0 + b[1] * x1) + b[2] * x2; }
+NPCD_HD float surf_mix(const float* b, float x0, float x1, float x2) { return (b[0] * x0 + b[1] * x1) + b[2] * x2; }
 
 // ---- one face of the measure launch -------------------------------------------------------------------------------------------------
 // -> the bits of d, for the mesh's integer maximum; d goes to d_out
-NPCD_SURF_HD uint32_t surf_measure_lane(const float* vertices, const int32_t* faces, int V, int face, float* d_out) {
+NPCD_HD uint32_t surf_measure_lane(const float* vertices, const int32_t* faces, int V, int face, float* d_out) {
     const float d = surf_face_measure(vertices, faces + (int64_t)face * 3, V);
     d_out[face] = d;
-    return surf_bits(d);
+    return float_bits(d);
 }
 
 // ---- one sample --------------------------------------------------------------------------------------------------------------------
@@ -177,13 +149,13 @@ struct SurfRow {          // where a sample's outputs go; null where an output i
     float* normal;         // [3]
     float* attr;           // [C]
 };
-NPCD_SURF_HD void surf_row_empty(const SurfMesh& m, const SurfRow& o) {
+NPCD_HD void surf_row_empty(const SurfMesh& m, const SurfRow& o) {
     o.point[0] = o.point[1] = o.point[2] = 0.f;
     if (o.face) *o.face = -1;
     if (o.normal) o.normal[0] = o.normal[1] = o.normal[2] = 0.f;
     if (o.attr) for (int c = 0; c < m.C; ++c) o.attr[c] = 0.f;
 }
-NPCD_SURF_HD void surf_sample_row(const SurfMesh& m, const float* u, const SurfRow& o) {
+NPCD_HD void surf_sample_row(const SurfMesh& m, const float* u, const SurfRow& o) {
     if (m.W == 0) return surf_row_empty(m, o);
     const uint64_t r = surf_mul_shift(surf_k0(u[0]), m.W);          // r < W: a tile's sum exceeds it
     int tile = surf_upper_bound(m.tiles, surf_tiles(m.F), r);

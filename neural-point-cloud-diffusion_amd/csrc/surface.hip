@@ -4,11 +4,11 @@
 //
 //   npcd_surface_prepare, three launches:
 //     measure   one workgroup per tile slot (surf_tile_base: kSurfTile consecutive faces of one mesh), one lane per face: d = |e1 x e2|
-//               to the workspace, and the integer maximum of its bits over the wave, then one atomicMax per wave into the mesh's word
-//               (d >= +0, so the bits order as the values do; a maximum does not depend on the order of its operands).
-//     quantise  the same grid: w = floor(float64(d) 2^k), the inclusive sums of w inside the tile (wave_scan_incl of csrc/wave.h, then
-//               the four wave totals through LDS) to the workspace, the tile's total to its slot.
-//     tiles     one workgroup per mesh: the inclusive sums of its tile totals in place, 256 at a time with a carry; W and the area.
+//               to the workspace, and the integer maximum of its bits into the mesh's word (wave_publish_max of csrc/wave.h; d >= +0,
+//               so the bits order as the values do).
+//     quantise  the same grid: w = floor(float64(d) 2^k), the inclusive sums of w inside the tile (block_scan of
+//               csrc/block_scan.h) to the workspace, the tile's total to its slot.
+//     tiles     one workgroup per mesh: the inclusive sums of its tile totals in place (block_scan_totals); W and the area.
 //   npcd_surface_sample, one launch: one lane per sample (surf_sample_row).  The mesh's tile sums are staged in LDS where they fit
 //               (kSurfLdsTiles), the second search reads the tile's local sums from global memory.
 //   Integer sums throughout: the order of the additions does not matter, and no workgroup waits on another -- the launches are the
@@ -17,6 +17,7 @@
 // Bounds.  A member's rows are taken through surf_span: offsets that do not ascend inside [0, total] give an empty member.  A lane past
 // the mesh's last face, tile or sample reads and writes nothing (its weight in a scan is 0).  A face index outside [0, V) is not
 // followed (surf_face).  Tile slots: blockIdx.x < floor(F_total / kSurfTile) + B, the size of the slot arrays.
+#include "block_scan.h"
 #include "common.h"
 #include "surface.h"
 
@@ -51,20 +52,6 @@ struct SurfArgs {
     int S, C, normals_mode;
 };
 
-struct AddU64 {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-// inclusive sums over the kSurfThreads lanes of a workgroup; wave_total: LDS [kSurfThreads / 64].  Every lane of the workgroup calls it.
-__device__ __forceinline__ uint64_t surf_block_scan(uint64_t v, uint64_t* wave_total) {
-    uint64_t incl = wave_scan_incl(v, (uint64_t)0, AddU64());
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) incl += wave_total[w];
-    __syncthreads();          // the totals may be written again
-    return incl;
-}
-
 // the mesh and the tile of this workgroup's slot; false for a slot no mesh uses
 __device__ __forceinline__ bool surf_slot(const SurfArgs& a, int* b, SurfSpan* fs, int* tile) {
     *b = surf_slot_member(a.face_off, a.B, blockIdx.x);
@@ -82,8 +69,7 @@ __global__ __launch_bounds__(kSurfThreads) void surf_measure_kernel(SurfArgs a) 
     const int64_t i = (int64_t)tile * kSurfTile + threadIdx.x;
     uint32_t bits = 0;
     if (i < fs.count) bits = surf_measure_lane(a.vertices + (int64_t)vs.first * 3, a.faces + (int64_t)fs.first * 3, vs.count, (int)i, a.ws.d + fs.first);
-    const uint32_t top = (uint32_t)wave_max_u64(bits);
-    if ((threadIdx.x & 63) == 0 && top) atomicMax(a.ws.d_max + b, top);
+    wave_publish_max(bits, a.ws.d_max + b);          // every lane of the wave is here
 }
 
 __global__ __launch_bounds__(kSurfThreads) void surf_quantise_kernel(SurfArgs a) {
@@ -94,9 +80,10 @@ __global__ __launch_bounds__(kSurfThreads) void surf_quantise_kernel(SurfArgs a)
     const int64_t i = (int64_t)tile * kSurfTile + threadIdx.x;
     const uint32_t d_max = a.ws.d_max[b];
     const uint64_t w = i < fs.count ? surf_quantise(a.ws.d[fs.first + i], d_max) : 0;
-    const uint64_t incl = surf_block_scan(w, wave_total);
+    uint64_t total;
+    const uint64_t incl = block_scan<kSurfThreads, true>(w, wave_total, &total);
     if (i < fs.count) a.ws.local[fs.first + i] = incl;
-    if (threadIdx.x == kSurfThreads - 1) a.ws.tiles[blockIdx.x] = incl;
+    if (threadIdx.x == 0) a.ws.tiles[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kSurfThreads) void surf_tiles_kernel(SurfArgs a) {
@@ -105,19 +92,10 @@ __global__ __launch_bounds__(kSurfThreads) void surf_tiles_kernel(SurfArgs a) {
     const SurfSpan fs = surf_span(a.face_off, b, a.F_total);
     const int n = surf_tiles(fs.count);
     uint64_t* tiles = a.ws.tiles + surf_tile_base(fs.first, b);          // (n = 0 for a span that is not one: not followed)
-    uint64_t carry = 0;
-    for (int first = 0; first < n; first += kSurfThreads) {          // the same trips for every lane
-        const int t = first + threadIdx.x;
-        const uint64_t incl = carry + surf_block_scan(t < n ? tiles[t] : 0, wave_total);
-        if (t < n) tiles[t] = incl;
-        if (threadIdx.x == kSurfThreads - 1) wave_total[0] = incl;
-        __syncthreads();
-        carry = wave_total[0];
-        __syncthreads();
-    }
+    const uint64_t W = block_scan_totals<kSurfThreads, true>(tiles, n, wave_total);
     if (threadIdx.x == 0) {
-        a.ws.mesh_W[b] = carry;
-        a.area[b] = surf_area(carry, a.ws.d_max[b]);
+        a.ws.mesh_W[b] = W;
+        a.area[b] = surf_area(W, a.ws.d_max[b]);
     }
 }
 
@@ -172,9 +150,8 @@ extern "C" int npcd_surface_prepare(const float* vertices, const int32_t* faces,
     const int rc = surf_check(B, V_total, F_total);
     if (rc != NPCD_OK) return rc;
     if (!vertices || !faces || !vert_offsets || !face_offsets || !ws || !area) return NPCD_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(area)) & 7) return NPCD_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(vertices) | reinterpret_cast<uintptr_t>(faces) | reinterpret_cast<uintptr_t>(vert_offsets) |
-         reinterpret_cast<uintptr_t>(face_offsets)) & 3)
+    if (misaligned(ws, 8) || misaligned(area, 8) || misaligned(vertices, 4) || misaligned(faces, 4) || misaligned(vert_offsets, 4) ||
+        misaligned(face_offsets, 4))
         return NPCD_ERR_ARG;
     SurfArgs a{};
     a.vertices = vertices, a.faces = faces, a.vert_off = vert_offsets, a.face_off = face_offsets, a.area = area;
@@ -206,14 +183,14 @@ extern "C" int npcd_surface_sample(const float* vertices, const int32_t* faces, 
     if ((normals_mode != kSurfNormalsNone) != (normals_out != nullptr) || (normals_mode == kSurfNormalsVertex) != (vertex_normals != nullptr))
         return NPCD_ERR_ARG;
     if ((C > 0) != (attributes != nullptr) || (C > 0) != (attributes_out != nullptr)) return NPCD_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(ws) & 7) return NPCD_ERR_ARG;
+    if (misaligned(ws, 8)) return NPCD_ERR_ARG;
     SurfArgs a{};
     a.vertices = vertices, a.faces = faces, a.vert_off = vert_offsets, a.face_off = face_offsets;
     a.B = B, a.V_total = (int)V_total, a.F_total = (int)F_total;
     surf_ws_layout(const_cast<void*>(ws), B, a.F_total, &a.ws);
     a.u = u, a.S = S, a.points = points, a.faces_out = faces_out, a.normals_mode = normals_mode, a.vnormals = vertex_normals;
     a.normals_out = normals_out, a.attrs = attributes, a.C = C, a.attrs_out = attributes_out;
-    hipLaunchKernelGGL(surf_sample_kernel, dim3((unsigned)((S + kSurfThreads - 1) / kSurfThreads), (unsigned)B), dim3(kSurfThreads), 0,
+    hipLaunchKernelGGL(surf_sample_kernel, dim3(blocks_for(S, kSurfThreads), (unsigned)B), dim3(kSurfThreads), 0,
                        static_cast<hipStream_t>(stream), a);
     NPCD_HIP_CHECK(hipGetLastError());
     return NPCD_OK;

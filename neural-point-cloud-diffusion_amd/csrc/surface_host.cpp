@@ -14,31 +14,10 @@
 #include <cstring>
 #include <vector>
 
+#include "host_lanes.h"
 #include "surface.h"
 
 using namespace npcd;
-
-template <class T>
-static bool read_all(FILE* f, std::vector<T>& v) { return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size(); }
-template <class T>
-static bool write_all(FILE* f, const std::vector<T>& v) { return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-
-// inclusive sums of x [n] in place, forward or from the far end
-static uint64_t scan_in_place(uint64_t* x, int n, bool reverse) {
-    uint64_t total = 0;
-    if (!reverse) {
-        for (int i = 0; i < n; ++i) x[i] = total += x[i];
-        return total;
-    }
-    for (int i = n - 1; i >= 0; --i) total += x[i];
-    uint64_t after = 0;
-    for (int i = n - 1; i >= 0; --i) {
-        const uint64_t own = x[i];
-        x[i] = total - after;
-        after += own;
-    }
-    return total;
-}
 
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
@@ -56,7 +35,7 @@ int main(int argc, char** argv) {
         return 2;
     std::fclose(in);
     const int slots = (int)surf_slots(B, F_total);
-    const auto order = [reverse](int i, int count) { return reverse ? count - 1 - i : i; };
+    const LaneOrder order{reverse};
     // poisoned: the steps write every entry they promise
     std::vector<float> d(F_total, -7.f);
     std::vector<uint32_t> d_max(B, 0);
@@ -83,14 +62,14 @@ int main(int argc, char** argv) {
                 }
             }
             if (pass == 0) continue;
-            tiles[slot] = scan_in_place(w_tile, kSurfTile, reverse);
+            tiles[slot] = scan_in_place<true>(w_tile, kSurfTile, reverse);
             for (int l = 0; l < kSurfTile; ++l)
                 if (tile * kSurfTile + l < fs.count) local[fs.first + tile * kSurfTile + l] = w_tile[l];
         }
     for (int w = 0; w < B; ++w) {          // the tiles launch
         const int b = order(w, B);
         const SurfSpan fs = surf_span(face_off.data(), b, F_total);
-        mesh_W[b] = scan_in_place(tiles.data() + surf_tile_base(fs.first, b), surf_tiles(fs.count), reverse);
+        mesh_W[b] = scan_in_place<true>(tiles.data() + surf_tile_base(fs.first, b), surf_tiles(fs.count), reverse);
         area[b] = surf_area(mesh_W[b], d_max[b]);
     }
     std::vector<float> points((size_t)B * S * 3, -7.f), normals(mode ? (size_t)B * S * 3 : 0, -7.f), attrs_out((size_t)B * S * C, -7.f);

@@ -87,5 +87,18 @@ struct MaxU64 {
 };
 __device__ __forceinline__ uint64_t row_max_u64(uint64_t v) { return row_scan_incl(v, (uint64_t)0, MaxU64()); }
 __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) { return read_lane(wave_scan_incl(v, (uint64_t)0, MaxU64()), 63); }
+// integer sums: the prefix sums of csrc/block_scan.h
+struct AddU64 {
+    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
+};
+
+// the maximum of `bits` over the wave into *target, a word that only grows: lane 0 reads it first and issues the one atomic only if
+// the wave's maximum is larger.  A maximum does not depend on how often or in what order it is applied.  Every lane of the wave
+// calls it (workgroups of one dimension).
+__device__ __forceinline__ void wave_publish_max(uint32_t bits, uint32_t* target) {
+    const uint32_t top = (uint32_t)wave_max_u64(bits);
+    if ((threadIdx.x & 63) == 0 && top > __hip_atomic_load(target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        __hip_atomic_fetch_max(target, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 }  // namespace npcd

@@ -352,6 +352,8 @@ def test_kernels_use_no_scratch(tmp_path):
         assert k["scratch"] == 0 and k["vgpr"] <= 128, (name, k)
         # the staged tile sums of the sample launch; the four wave totals of a workgroup's scan
         assert k["lds"] == (8 * LDS_TILES if "surf_sample" in name else 0 if "surf_measure" in name else 32), (name, k)
+    text = open(tmp_path / "surface.s").read()
+    assert "global_atomic_umax" in text and "cmpswap" not in text          # the one atomic is one instruction, not a compare-and-swap loop
 
 
 def test_header_exports_and_signatures():
