@@ -1021,6 +1021,23 @@ int npcd_mesh_distance_boxes(const float* vertices, int64_t V, const int32_t* fa
 int npcd_mesh_distance_query(const float* points, int64_t S, const float* vertices, int64_t V, const int32_t* faces, int64_t F,
                              const void* ws, int cull, float* sqdist, int32_t* face, float* closest, int64_t* evaluated, void* stream);
 
+/* ---- the first hit of every ray on one mesh (added within ABI 10; csrc/raycast.hip, csrc/raycast.h).  origins and
+ * directions [R, 3], vertices [V, 3] fp32 and faces [F, 3] int32 on the device, V < 2^31, 1 <= F < 2^28, 1 <= R < 2^31.  The
+ * specification is restated by ray_mesh_reference of npcd/eval/mesh.py, and the kernel is held to it bit for bit.
+ *   npcd_raycast_query: ws as npcd_mesh_distance_boxes of the same (vertices, V, faces, F) left it.  Per ray the lexicographic
+ *       minimum of (t, face) over the hits with t_min <= t <= t_max and t < +inf -- t ordered as a signed float with -0 == +0, so
+ *       t_min may be negative -- of the watertight ray / triangle test with fp32 sheared corners and float64 edge functions: t [R]
+ *       fp32, face [R] int32, bary [R, 3] fp32 (the weights of the face's three corners), front [R] int8 (1: the face's normal
+ *       (B - A) x (C - A) points against the ray); (+inf, -1, zeros, 0) for a ray that hits nothing.  cull = 1 skips a tile whose
+ *       enlarged box no ray segment of a wave reaches; cull = 0 evaluates every tile.  The outputs are the same bits.  evaluated
+ *       (int64 on the device, may be NULL, not zeroed here) takes the (wave, tile) evaluations, one integer add per wave.  One launch.
+ * No float atomics, no host synchronisation, no allocation, no workgroup that waits on another.  NPCD_ERR_UNSUPPORTED for V >= 2^31,
+ * F >= 2^28 or R >= 2^31; NPCD_ERR_ARG for a negative size, F < 1 or R < 1, a cull that is not 0 or 1, a NULL pointer that the call
+ * takes or a misaligned one (ws: 16 bytes, evaluated: 8).  Nothing is launched in either case. */
+int npcd_raycast_query(const float* origins, const float* directions, int64_t R, const float* vertices, int64_t V, const int32_t* faces,
+                       int64_t F, const void* ws, float t_min, float t_max, int cull, float* t, int32_t* face, float* bary, int8_t* front,
+                       int64_t* evaluated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,9 @@ SOURCES = {
     # products, the three cross terms and q = a + (v ab + w ac) are rounded as written.  Its pair loop is nothing
     # but fp32 VALU: single operations rather than packed ones, as for chamfer.hip (docs/experiments.md R15.1)
     "mesh_distance.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # the first hit of a ray is picked by comparing t = float(T / det) bit for bit with its numpy restatement: the fp32 shear of the
+    # corners and the float64 edge functions, T and det are rounded as written.  Single operations, as above
+    "raycast.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

@@ -11,9 +11,12 @@ What a mesh's connectivity is and Taubin smoothing likewise: `m
 npcd.hip.smooth, `mesh_topology` reports edges, boundary and non-manifold edges and the Euler characteristic, and
 extract_mesh(smooth=n, topology=True) applies both.  How far two surfaces lie apart likewise:
 `point_mesh_distance_reference` restates npcd.hip.mesh_distance, `mesh_deviation` and `cloud_mesh_distance` report mean, rms and
-maximum distances, and extract_mesh(deviation=n) says what simplifying and smoothing cost.
+maximum distances, and extract_mesh(deviation=n) says what simplifying and smoothing cost.  Looking at a mesh likewise (DESIGN.md
+5.19): `ray_mesh_reference` restates npcd.hip.raycast, `render_mesh` gives mask, depth, face, normal and colour at the renderer's own
+rays, `mesh_render_agreement` compares them with the field's render, and extract_mesh(agreement=cameras) reports it.
 
-This module imports without a GPU; only extract_mesh, sample_mesh_clouds, mesh_deviation and cloud_mesh_distance need one."""
+This module imports without a GPU; only extract_mesh, sample_mesh_clouds, mesh_deviation, cloud_mesh_distance, render_mesh and
+mesh_render_agreement need one."""
 import itertools
 import math
 from typing import Dict, List, Optional, Sequence
@@ -654,6 +657,95 @@ def point_mesh_distance_reference(points, vertices, faces, chunk: int = 256) -> 
     return {"sqdist": best, "face": face, "closest": closest}
 
 
+def ray_axes(directions: np.ndarray):
+    """directions [R, 3] float32 -> (kx, ky, kz [R] int64, usable [R] bool): step 1 of DESIGN.md 5.19.  kz is the axis of the largest
+    |d|, the lowest among equal ones; kx = (kz + 1) % 3 and ky = (kx + 1) % 3, swapped where d[kz] < 0; usable: d finite and
+    d[kz] != 0."""
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    size = np.abs(d)
+    kz = np.zeros(len(d), dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        top = size[:, 0].copy()
+        for k in (1, 2):
+            larger = size[:, k] > top
+            kz[larger], top[larger] = k, size[larger, k]
+        kx = (kz + 1) % 3
+        ky = (kx + 1) % 3
+        dz = d[np.arange(len(d)), kz]
+        turned = dz < 0
+        kx, ky = np.where(turned, ky, kx), np.where(turned, kx, ky)
+        usable = np.isfinite(d).all(axis=1) & (dz != 0)
+    return kx, ky, kz, usable
+
+
+def ray_mesh_reference(origins, directions, vertices, faces, t_min: float = 0.0, t_max: float = float("inf"), chunk: int = 256) -> Dict[str, np.ndarray]:
+    """The specification of npcd.hip.raycast.cast_rays in numpy: brute force, `chunk` faces at a time.  origins,
+    directions [R, 3], vertices [V, 3], faces [F, 3] -> {"t" [R] float32, "face" [R] int32, "bary" [R, 3] float32, "front" [R] int8}.
+
+    A face takes part if its three indices lie in [0, V).  With the axes of ray_axes, Sx = d[kx] / d[kz], Sy = d[ky] / d[kz] and Sz =
+    1 / d[kz] in fp32; per corner p = P - o, px = p[kx] - Sx p[kz], py = p[ky] - Sy p[kz], pz = Sz p[kz] in fp32.  In float64 from those:
+    U = cx by - cy bx, V = ax cy - ay cx, W = bx ay - by ax, det = (U + V) + W; a pair misses if one of U, V, W is below 0 and another
+    above, if det == 0 or anything is NaN; T = (U az + V bz) + W cz, t = float32(T / det), a hit iff t_min <= t <= t_max and t < +inf.
+    The winner is the lexicographic minimum of (t, face), t as a signed float (-0 == +0); bary = float32(U / det, V / det, W / det),
+    front = det > 0.  A ray that is not usable (a component of o or d not finite, d[kz] == 0) or hits nothing keeps (+inf, -1, zeros,
+    0)."""
+    o = np.ascontiguousarray(np.asarray(origins, dtype=np.float32))
+    d = np.ascontiguousarray(np.asarray(directions, dtype=np.float32))
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32))
+    f = np.asarray(faces)
+    if any(a.ndim != 2 or a.shape[1] != 3 for a in (o, d, v, f)) or len(o) != len(d):
+        raise ValueError(f"ray_mesh_reference: origins and directions must be [R, 3], vertices and faces [N, 3]; got {o.shape}, {d.shape}, "
+                         f"{v.shape} and {f.shape}")
+    if f.size and not np.issubdtype(f.dtype, np.integer):
+        raise ValueError("ray_mesh_reference: faces must hold integers")
+    f = f.astype(np.int64)
+    R, V, F = len(o), len(v), len(f)
+    if F >= MAX_DISTANCE_FACES:
+        raise ValueError(f"ray_mesh_reference: {F} faces; they must stay below 2^28 = {MAX_DISTANCE_FACES}")
+    t_min, t_max = np.float32(t_min), np.float32(t_max)
+    out = {"t": np.full(R, np.inf, dtype=np.float32), "face": np.full(R, -1, dtype=np.int32), "bary": np.zeros((R, 3), dtype=np.float32),
+           "front": np.zeros(R, dtype=np.int8)}
+    rows = np.arange(R)
+    kx, ky, kz, usable = ray_axes(d)
+    usable &= np.isfinite(o).all(axis=1)
+    with np.errstate(all="ignore"):
+        dz = d[rows, kz]
+        Sx, Sy, Sz = d[rows, kx] / dz, d[rows, ky] / dz, np.float32(1.0) / dz
+
+        def pick(p, k):          # p [R, n, 3 corners, 3] -> [R, n, 3 corners]: the component k [R] of every corner
+            return np.take_along_axis(p, k[:, None, None, None], axis=3)[..., 0]
+        for first in range(0, F if R else 0, chunk):
+            part = f[first:first + chunk]
+            valid = ((part >= 0) & (part < V)).all(axis=1)
+            if not valid.any():
+                continue
+            index = first + np.nonzero(valid)[0]
+            p = v[part[valid]][None] - o[:, None, None, :]          # [R, n, 3 corners, 3] float32
+            pz = pick(p, kz)
+            x = (pick(p, kx) - Sx[:, None, None] * pz).astype(np.float64)
+            y = (pick(p, ky) - Sy[:, None, None] * pz).astype(np.float64)
+            z = (Sz[:, None, None] * pz).astype(np.float64)
+            assert p.dtype == np.float32 and pz.dtype == np.float32
+            U = x[..., 2] * y[..., 1] - y[..., 2] * x[..., 1]
+            Vf = x[..., 0] * y[..., 2] - y[..., 0] * x[..., 2]
+            W = x[..., 1] * y[..., 0] - y[..., 1] * x[..., 0]
+            det = (U + Vf) + W
+            below, above = (U < 0) | (Vf < 0) | (W < 0), (U > 0) | (Vf > 0) | (W > 0)
+            inside = usable[:, None] & ~(below & above) & (det != 0) & ~(np.isnan(U) | np.isnan(Vf) | np.isnan(W) | np.isnan(det))
+            T = (U * z[..., 0] + Vf * z[..., 1]) + W * z[..., 2]
+            t = (T / det).astype(np.float32)
+            hit = inside & (t >= t_min) & (t <= t_max) & (t < np.float32(np.inf))
+            key = np.where(hit, t, np.float32(np.inf))
+            at = np.argmin(key, axis=1)          # the first of equal minima: the lowest index
+            least = key[rows, at]
+            wins = least < out["t"]
+            w, a = rows[wins], at[wins]
+            out["t"][w], out["face"][w] = least[wins], index[a].astype(np.int32)
+            out["bary"][w] = np.stack([U[w, a] / det[w, a], Vf[w, a] / det[w, a], W[w, a] / det[w, a]], axis=1).astype(np.float32)
+            out["front"][w] = (det[w, a] > 0).astype(np.int8)
+    return out
+
+
 def _mesh_parts(mesh):
     """(vertices, faces, normals or None) of a mesh as isosurface (a tuple) or extract_mesh (a dict) returns it."""
     if isinstance(mesh, dict):
@@ -730,6 +822,133 @@ def cloud_mesh_distance(points: torch.Tensor, mesh, closest=None) -> Dict[str, f
     return dict(zip(_STAT_NAMES, _distance_stats(got["sqdist"], got["face"] >= 0).cpu().tolist()))
 
 
+def _mix(bary: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """bary [..., 3] and rows [..., 3 corners, C] -> (b0 r0 + b1 r1) + b2 r2, in that order."""
+    return (bary[..., 0:1] * rows[..., 0, :] + bary[..., 1:2] * rows[..., 1, :]) + bary[..., 2:3] * rows[..., 2, :]
+
+
+def _unit(g: torch.Tensor) -> torch.Tensor:
+    """g [..., 3] -> g / sqrt((gx gx + gy gy) + gz gz); (+0, +0, +0) where a component is not finite."""
+    unit = g / torch.sqrt((g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1]) + g[..., 2] * g[..., 2])[..., None]
+    return torch.where(torch.isfinite(unit).all(dim=-1, keepdim=True), unit, torch.zeros_like(unit))
+
+
+def block_order(resolution: int, device, block: int = 8) -> torch.Tensor:
+    """The row-major pixel numbers of a resolution^2 image in the order of its block x block pixel blocks, row-major within a block and
+    among the blocks: 64 consecutive entries are neighbours in the image, which is what a wave of cast_rays wants.  int64 [R]."""
+    row, col = torch.meshgrid(torch.arange(resolution, device=device), torch.arange(resolution, device=device), indexing="ij")
+    across = (resolution + block - 1) // block
+    key = ((row // block * across + col // block) * block + row % block) * block + col % block
+    return torch.sort(key.reshape(-1))[1]
+
+
+MESH_GREY = 0.75          # the albedo of a mesh without colours in render_mesh
+
+
+@torch.no_grad()
+def render_mesh(mesh, extrinsics: torch.Tensor, intrinsics: torch.Tensor, resolution: int, cube_scale: float, white_back: bool = True,
+                light: str = "head", caster=None, raygen=None) -> Dict[str, torch.Tensor]:
+    """A mesh on the GPU, as isosurface or extract_mesh return it, seen from the cameras extrinsics [T, 4, 4] (world to camera) and
+    intrinsics [T, 3, 3] -> {"mask" [T, R, 1], "depth" [T, R, 1], "face" [T, R] int32, "normal" [T, R, 3], "channels" [T, R, 3]}, R =
+    resolution^2 in row-major pixel order.
+
+    The rays are those of npcd.hip.render.ray_gen(extrinsics, intrinsics, resolution, cube_scale), the very rays the volume renderer
+    marches, and each takes its first hit on the mesh (npcd.hip.raycast.cast_rays) with t >= 0; they are cast in 8 x 8 pixel blocks
+    and scattered back, a permutation that changes no bit.  mask is 1 on a hit; depth is the ray parameter t along ray_gen's
+    direction -- the volume renderer's convention, the point is o + t d; ray_gen's d is unit, so t is also a distance -- and a ray that misses gets its own end
+    t1, what the volume renderer gives a sample slot without a point.  normal is the unit normal of the face, (B - A) x (C - A)
+    normalised, or with mesh["normals"] the barycentric mix of the vertex normals, normalised again; zeros on a miss.  channels is
+    the barycentric mix of mesh["colors"], or without colours MESH_GREY |normal . d / |d||: a light at the camera, both sides lit;
+    a miss gets the background, 1 with white_back and 0 without.  Torch on the device in a fixed order of operations: two calls give
+    the same bits.  No host read.  `caster` and `raygen` stand in for cast_rays and ray_gen (tests of the host logic)."""
+    if light != "head":
+        raise ValueError(f"render_mesh: light must be \"head\" (a light at the camera); got {light!r}")
+    if caster is None:
+        from ..hip.raycast import cast_rays as caster
+    if raygen is None:
+        from ..hip.render import ray_gen as raygen
+    vertices, faces, normals = _mesh_parts(mesh)
+    colors = mesh.get("colors") if isinstance(mesh, dict) else None
+    resolution = int(resolution)
+    o, d, _, t1 = raygen(extrinsics, intrinsics, resolution, float(cube_scale))
+    T, R = o.shape[0], o.shape[1]
+    order = block_order(resolution, o.device)
+    got = caster(o[:, order].reshape(-1, 3), d[:, order].reshape(-1, 3), vertices, faces)
+    back = {k: torch.empty_like(got[k].reshape((T, R) + got[k].shape[1:])) for k in ("t", "face", "bary")}
+    for k in back:
+        back[k][:, order] = got[k].reshape(back[k].shape)
+    face, bary = back["face"], back["bary"]
+    hit = face >= 0
+    depth = torch.where(hit, back["t"], t1)
+    background = torch.full((T, R, 3), 1.0 if white_back else 0.0, dtype=torch.float32, device=o.device)
+    if faces.shape[0] == 0:
+        return {"mask": hit.to(torch.float32)[..., None], "depth": depth[..., None], "face": face, "normal": torch.zeros_like(background),
+                "channels": background}
+    corners = faces[face.clamp(min=0).long()].long()          # [T, R, 3]: a winner's indices lie in [0, V)
+    if normals is None:
+        c = vertices[corners]
+        e1, e2 = c[..., 1, :] - c[..., 0, :], c[..., 2, :] - c[..., 0, :]
+        n = torch.stack([e1[..., 1] * e2[..., 2] - e1[..., 2] * e2[..., 1], e1[..., 2] * e2[..., 0] - e1[..., 0] * e2[..., 2],
+                         e1[..., 0] * e2[..., 1] - e1[..., 1] * e2[..., 0]], dim=-1)
+    else:
+        n = _mix(bary, normals[corners])
+    normal = torch.where(hit[..., None], _unit(n), torch.zeros_like(n))
+    if colors is None:
+        toward = _unit(d)
+        lit = torch.abs((normal[..., 0] * toward[..., 0] + normal[..., 1] * toward[..., 1]) + normal[..., 2] * toward[..., 2])
+        shade = (MESH_GREY * lit)[..., None].expand(-1, -1, 3)
+    else:
+        shade = _mix(bary, colors[corners])
+    return {"mask": hit.to(torch.float32)[..., None], "depth": depth[..., None], "face": face, "normal": normal,
+            "channels": torch.where(hit[..., None], shade, background)}
+
+
+_AGREEMENT_NAMES = ("iou", "depth_mean", "depth_max", "psnr", "ssim")
+
+
+@torch.no_grad()
+def mesh_render_agreement(pointnerf, coords, feats, mesh, extrinsics: torch.Tensor, intrinsics: torch.Tensor, resolution: int = 128,
+                          caster=None, raygen=None, renderer=None, metrics=None) -> Dict[str, object]:
+    """Does a mesh look like the field it came from?  The field of one cloud (coords [N, 3] or [1, N, 3], feats likewise) through
+    PointNeRF.render and the mesh through render_mesh, at the same cameras extrinsics [T, 4, 4] and intrinsics [T, 3, 3], the same
+    rays, the renderer's cube_scale and background.
+
+    -> {"views": per view {"iou", "depth_mean", "depth_max", "psnr", "ssim"}, and the same five over the views}, Python floats.  iou:
+    the silhouettes, the field's mask above 0.5 against the mesh's, intersection over union (1 where both are empty).  depth_mean,
+    depth_max: |depth difference| over the pixels inside both silhouettes, the ray parameter of either; NaN without such a pixel.
+    psnr = 10 log10(1 / mse) and ssim of the two colour images through npcd.hip.image_metrics.  Over the views: the mean of the
+    views that have a value, the maximum for depth_max.  float64 on the device; one host read, at the end.  `caster`, `raygen`,
+    `renderer` (for pointnerf.render) and `metrics` (for image_metrics) stand in (tests of the host logic)."""
+    if metrics is None:
+        from ..hip.image_metrics import image_metrics as metrics
+    resolution = int(resolution)
+    batch = lambda x: x if x is None or x.dim() == 3 else x[None]
+    seen = (pointnerf.render if renderer is None else renderer)(batch(coords), batch(feats), extrinsics[None], intrinsics[None], resolution=resolution)
+    settings = pointnerf.renderer
+    view = render_mesh(mesh, extrinsics, intrinsics, resolution, float(settings.cube_scale), white_back=bool(settings.white_back),
+                       caster=caster, raygen=raygen)
+    T = extrinsics.shape[0]
+    f64 = torch.float64
+    of_field, of_mesh = seen["mask"][0, :, :, 0] > 0.5, view["mask"][:, :, 0] > 0.5
+    both, either = (of_field & of_mesh), (of_field | of_mesh)
+    n_both, n_either = both.sum(dim=1).to(f64), either.sum(dim=1).to(f64)
+    iou = torch.where(n_either > 0, n_both / n_either, torch.ones_like(n_either))
+    gap = torch.abs(seen["depth"][0, :, :, 0].to(f64) - view["depth"][:, :, 0].to(f64))
+    gap_mean = torch.where(both, gap, torch.zeros_like(gap)).sum(dim=1) / n_both          # 0 / 0: NaN without a common pixel
+    gap_max = torch.where(both, gap, torch.full_like(gap, -float("inf"))).amax(dim=1)
+    gap_max = torch.where(n_both > 0, gap_max, torch.full_like(gap_max, float("nan")))
+    image = lambda c: c.reshape(T, resolution, resolution, 3).to(torch.float32).contiguous()
+    measured = metrics(image(view["channels"]), image(seen["channels"][0]), layout="hwc")
+    psnr = 10.0 * torch.log10(1.0 / measured.mse.to(f64))
+    rows = torch.stack([iou, gap_mean, gap_max, psnr, measured.ssim.to(f64)], dim=1).cpu().tolist()          # the one host read
+    views = [dict(zip(_AGREEMENT_NAMES, row)) for row in rows]
+    out: Dict[str, object] = {"views": views}
+    for name in _AGREEMENT_NAMES:
+        values = [v[name] for v in views if not math.isnan(v[name])]
+        out[name] = float("nan") if not values else (max(values) if name == "depth_max" else sum(values) / len(values))
+    return out
+
+
 @torch.no_grad()
 def sample_mesh_clouds(meshes, num_points: int, generator: Optional[torch.Generator] = None, normals: bool = False, sampler=None):
     """Meshes on the GPU, as isosurface or extract_mesh return them -> clouds [B, num_points, 3] fp32 drawn uniformly by area from
@@ -765,7 +984,8 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
                  bound: Optional[float] = None, mlp_dtype=None, view_dir: Optional[torch.Tensor] = None, components: Optional[int] = None,
                  min_component_nodes: Optional[int] = None, normals: bool = False, simplify: Optional[float] = None,
                  simplifier=None, smooth: Optional[int] = None, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
-                 topology: bool = False, smoother=None, deviation: Optional[int] = None, deviator=None) -> List[Dict[str, torch.Tensor]]:
+                 topology: bool = False, smoother=None, deviation: Optional[int] = None, deviator=None, agreement=None,
+                 agreer=None) -> List[Dict[str, torch.Tensor]]:
     """coords [B, N, 3], feats [B, N, F] on the GPU -> per cloud {"vertices" [V, 3] fp32, "faces" [F, 3] int32, "colors" [V, 3] fp32
     in [0, 1] (with colors=True)}, all on the GPU.
 
@@ -793,8 +1013,17 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
     deviation=n, with simplify or smooth given, adds "deviation": mesh_deviation(the final mesh, the raw isosurface of the same cloud,
     n), what simplifying and smoothing cost in distance (one more host read per mesh).  Its samples come from a
     generator seeded with DEVIATION_SEED, so two calls agree.  `deviator` stands in for mesh_deviation (tests of the host logic).
-    deviation=None: the mesh as before."""
+    deviation=None: the mesh as before.
+
+    agreement=(extrinsics [T, 4, 4], intrinsics [T, 3, 3]) or (extrinsics, intrinsics, image resolution) adds "agreement":
+    mesh_render_agreement(pointnerf, the cloud, the final mesh, the cameras), whether the mesh looks like the field from those cameras
+    (one more host read per mesh; the image resolution defaults to mesh_render_agreement's).  `agreer` stands in for
+    mesh_render_agreement (tests of the host logic).  agreement=None: the mesh as before."""
     from ..hip.isosurface import isosurface
+    if agreement is not None:
+        if not (isinstance(agreement, (tuple, list)) and len(agreement) in (2, 3) and all(isinstance(t, torch.Tensor) for t in agreement[:2])
+                and (len(agreement) == 2 or (isinstance(agreement[2], int) and not isinstance(agreement[2], bool) and agreement[2] > 0))):
+            raise ValueError(f"extract_mesh: agreement must be (extrinsics, intrinsics) or (extrinsics, intrinsics, image resolution); got {agreement!r}")
     if deviation is not None:
         if isinstance(deviation, bool) or not isinstance(deviation, int) or deviation < 1:
             raise ValueError(f"extract_mesh: deviation must be a positive number of samples; got {deviation!r}")
@@ -833,6 +1062,10 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
         if deviation is not None:
             seeded = torch.Generator(device=vertices.device).manual_seed(DEVIATION_SEED)
             mesh["deviation"] = (mesh_deviation if deviator is None else deviator)(mesh, (vertices, faces), deviation, generator=seeded)
+        if agreement is not None:
+            size = {} if len(agreement) == 2 else {"resolution": agreement[2]}
+            mesh["agreement"] = (mesh_render_agreement if agreer is None else agreer)(pointnerf, coords[b:b + 1], feats[b:b + 1], dict(mesh),
+                                                                                       agreement[0], agreement[1], **size)
         out.append(mesh)
     return out
 

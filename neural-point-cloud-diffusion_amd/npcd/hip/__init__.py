@@ -180,6 +180,7 @@ SIGNATURES = {
     "npcd_mesh_distance_ws_bytes": (c_int64, [c_int64, c_int64]),
     "npcd_mesh_distance_boxes": (c_int, [_P, c_int64, _P, c_int64, _P, _P]),
     "npcd_mesh_distance_query": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int] + [_P] * 4 + [_P]),
+    "npcd_raycast_query": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_float, c_int] + [_P] * 5 + [_P]),
 }
 
 _lib = None
@@ -248,4 +249,5 @@ def stream_ptr():
 
 from .simplify import simplify_mesh  # noqa: E402,F401  (after the binding it is written on)
 from .smooth import mesh_edges, smooth_mesh  # noqa: E402,F401
-from .mesh_distance import closest_on_mesh  # noqa: E402,F401
+from .mesh_distance import closest_on_mesh, mesh_boxes  # noqa: E402,F401
+from .raycast import cast_rays  # noqa: E402,F401

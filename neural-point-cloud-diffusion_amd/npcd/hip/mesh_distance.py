@@ -42,6 +42,34 @@ def sort_order(points: torch.Tensor, vertices: torch.Tensor) -> torch.Tensor:
     return torch.sort(key)[1]
 
 
+def mesh_boxes(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """vertices [V, 3] fp32 and faces [F, 3] int32 on the GPU, F >= 1 -> the workspace that npcd_mesh_distance_boxes leaves (the
+    corners of every face and the box of every tile of TILE_FACES faces) as an int64 tensor: what npcd.hip.raycast.cast_rays takes as
+    boxes=, so that many calls on one mesh build it once.  It belongs to these vertices and faces.  One launch, no host read."""
+    who = "mesh_boxes"
+    for name, t in (("vertices", vertices), ("faces", faces)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a tensor")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{who}: {name} must be [N, 3]; got {tuple(t.shape)}")
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if V >= MAX_VERTICES or not 1 <= F < MAX_FACES:
+        raise ValueError(f"{who}: {V} vertices and {F} faces; vertices must stay below 2^31 and faces in [1, 2^28 = {MAX_FACES})")
+    require_gpu(vertices, faces)
+    if vertices.dtype != torch.float32 or faces.dtype != torch.int32:
+        raise RuntimeError(f"{who}: vertices must be fp32 and faces int32; got {vertices.dtype} and {faces.dtype}")
+    if faces.device != vertices.device:
+        raise RuntimeError(f"{who}: vertices on {vertices.device}, faces on {faces.device}")
+    vertices, faces = vertices.detach().contiguous(), faces.contiguous()
+    L = lib()
+    with torch.cuda.device(vertices.device):
+        got = L.npcd_mesh_distance_ws_bytes(V, F)
+        check(min(got, 0), "npcd_mesh_distance_ws_bytes")
+        ws = torch.empty(got // 8 + 2, dtype=torch.int64, device=vertices.device)          # a fresh allocation: aligned well beyond 16 bytes
+        check(L.npcd_mesh_distance_boxes(ptr(vertices), V, ptr(faces), F, ptr(ws), stream_ptr()), "npcd_mesh_distance_boxes")
+    return ws
+
+
 def closest_on_mesh(points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, cull: bool = True, sort_points: bool = True,
                     stats: bool = False) -> Dict[str, torch.Tensor]:
     """points [S, 3], vertices [V, 3] fp32 and faces [F, 3] int32 on the GPU -> {"sqdist" [S] fp32, "face" [S] int32, "closest"
