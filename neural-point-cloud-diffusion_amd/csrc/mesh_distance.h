@@ -1,48 +1,33 @@
 // The closest point of a triangle mesh to a query point: the per-lane arithmetic of csrc/mesh_distance.hip, written
-// once for the device and the host.  The kernels run these functions one lane per face (the corners launch) or per query point; the
-// stand-alone program csrc/mesh_distance_host.cpp runs them as plain loops (tests/test_mesh_distance_cpu.py): this header includes
-// nothing of HIP.  All fp32 arithmetic is as written -- the file is compiled without FMA contraction (build.py) -- and the division
+// once for the device and the host.  The kernels run these functions and those of mesh_tiles.h one lane per face (the corners launch) or per query
+// point; the stand-alone program csrc/mesh_distance_host.cpp runs them as plain loops (tests/test_mesh_distance_cpu.py): this header
+// includes nothing of HIP.  All fp32 arithmetic is as written -- the file is compiled without FMA contraction (build.py) -- and the division
 // is the correctly rounded one.
 //
 //   Pair      (p; a, b, c): the region form of Ericson's closest point on a triangle, md_pair below; dot(u, v) = (ux vx + uy vy) +
 //             uz vz.  The first region that holds gives (v, w); q = a + (v ab + w ac), dist2 = dot(p - q, p - q).  One division: the
 //             regions differ in which quotient they take, not in how it is rounded.
-//   Corners   a face takes part if its three indices lie in [0, V); the corners launch writes its nine coordinates as three 16-byte
-//             words.  Every other face, and the padding of the last tile, is written as NaN: its dist2 is NaN and never wins.
 //   Winner    the lexicographic minimum of (dist2, face) over the faces with dist2 < +inf; a NaN never wins.  dist2 >= +0, so its
 //             bits order as unsigned integers: md_key packs (bits << 32) | face.
-//   Box       per tile of kMdTile consecutive faces the axis-aligned box of the corners that are finite, of the faces that take part,
-//             and slack = 2^-20 the largest power of two at or below the largest |coordinate| among them: 8 ulp.
 //   Bound     md_bound: g = (max(lo - p, p - hi) - max(slack, the point's own)) (1 - 2^-11), clamped at 0 per axis; (gx gx + gy gy) +
 //             gz gz.  A tile is evaluated if bound <= best and bound < +inf (md_needs); the box of a tile without a finite corner
 //             is (+inf, -inf), whose bound is +inf for every finite point.
+//   Query     MdQuery: a lane's point and slack, and the answers of these functions to the tile walk (tile_walk.h).
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "bits.h"
+#include "mesh_tiles.h"
 
 namespace npcd {
 
 constexpr int kMdThreads = 64;                                // lanes per workgroup of the query launch: one wave, one point per lane
-constexpr int kMdTile = 256;                                  // faces per tile; the corners launch runs one workgroup of kMdTile lanes per tile
 constexpr int kMdScan = 4;                                    // boxes a wave takes bounds to at a time: their loads are in flight together
-constexpr int64_t kMdMaxVertices = (int64_t)1 << 31;
-constexpr int64_t kMdMaxFaces = (int64_t)1 << 28;
 constexpr int64_t kMdMaxPoints = (int64_t)1 << 31;
-constexpr uint32_t kMdInfBits = 0x7f800000u;
 constexpr uint64_t kMdNoKey = ((uint64_t)kMdInfBits << 32) | 0xffffffffu;          // (+inf, -1): what a point without a face keeps
 constexpr float kMdShrink = 0.99951171875f;                   // 1 - 2^-11, per axis: 2^-10 of the bound
 
-struct alignas(16) MdCorner {          // one corner of a face: a 16-byte word, the fourth float is not read
-    float x, y, z, pad;
-};
-struct alignas(16) MdBox {          // one tile
-    float lo[3], slack, hi[3];
-    int32_t count;          // the corners inside: 0 for a tile that is always skipped
-};
-
-NPCD_HD int64_t md_tiles(int64_t F) { return (F + kMdTile - 1) / kMdTile; }
 NPCD_HD float md_dot(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
 
 // ---- one pair -------------------------------------------------------------------------------------------------------------------------
@@ -98,61 +83,6 @@ NPCD_HD uint64_t md_key(float dist2, int32_t face) {
     return dist2 < bits_float(kMdInfBits) ? ((uint64_t)float_bits(dist2) << 32) | (uint32_t)face : kMdNoKey;
 }
 
-// ---- one face of the corners launch -----------------------------------------------------------------------------------------------------
-// out [3]: the corners of face f, NaN where the face does not take part (or f >= F).  -> true if it takes part
-NPCD_HD bool md_corners_lane(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int64_t f, MdCorner* out) {
-    const float nan = bits_float(0x7fc00000u);
-    bool valid = f < F;
-    int64_t idx[3] = {0, 0, 0};
-    if (valid)
-        for (int k = 0; k < 3; ++k) {
-            idx[k] = faces[f * 3 + k];
-            valid = valid && idx[k] >= 0 && idx[k] < V;
-        }
-    for (int k = 0; k < 3; ++k) {
-        out[k].pad = 0.f;
-        if (valid) {
-            out[k].x = vertices[idx[k] * 3], out[k].y = vertices[idx[k] * 3 + 1], out[k].z = vertices[idx[k] * 3 + 2];
-        } else {
-            out[k].x = out[k].y = out[k].z = nan;
-        }
-    }
-    return valid;
-}
-// a corner joins a box if its three coordinates are finite
-NPCD_HD bool md_corner_counts(const MdCorner& c) { return is_finite(c.x) && is_finite(c.y) && is_finite(c.z); }
-NPCD_HD uint32_t md_abs_bits(const MdCorner& c) {
-    const uint32_t x = float_bits(c.x) & 0x7fffffffu, y = float_bits(c.y) & 0x7fffffffu, z = float_bits(c.z) & 0x7fffffffu;
-    return x > y ? (x > z ? x : z) : (y > z ? y : z);
-}
-// 8 ulp of a finite |coordinate| given by its bits: 2^-20 of the power of two at or below it, at least 8 times the smallest float
-NPCD_HD float md_slack(uint32_t abs_bits) {
-    const float unit = bits_float(abs_bits & kMdInfBits) * 9.5367431640625e-07f;          // 2^-20, exact or a denormal power of two
-    const float least = bits_float(8u);
-    return unit > least ? unit : least;
-}
-NPCD_HD float md_point_slack(const float* p) {
-    const MdCorner c = {p[0], p[1], p[2], 0.f};
-    return md_corner_counts(c) ? md_slack(md_abs_bits(c)) : bits_float(8u);
-}
-// the box of `n` corners (n a multiple of three, NaN corners do not count)
-NPCD_HD MdBox md_box_of(const MdCorner* corners, int64_t n) {
-    const float inf = bits_float(kMdInfBits);
-    MdBox box = {{inf, inf, inf}, 0.f, {-inf, -inf, -inf}, 0};
-    uint32_t top = 0;
-    for (int64_t j = 0; j < n; ++j) {
-        const MdCorner& c = corners[j];
-        if (!md_corner_counts(c)) continue;
-        const float x[3] = {c.x, c.y, c.z};
-        for (int k = 0; k < 3; ++k) box.lo[k] = x[k] < box.lo[k] ? x[k] : box.lo[k], box.hi[k] = x[k] > box.hi[k] ? x[k] : box.hi[k];
-        const uint32_t m = md_abs_bits(c);
-        top = m > top ? m : top;
-        box.count += 1;
-    }
-    box.slack = md_slack(top);
-    return box;
-}
-
 // ---- one (point, tile) of the query launch ----------------------------------------------------------------------------------------------
 NPCD_HD float md_bound(const float* p, float point_slack, const MdBox& box) {
     const float slack = box.slack > point_slack ? box.slack : point_slack;
@@ -165,5 +95,29 @@ NPCD_HD float md_bound(const float* p, float point_slack, const MdBox& box) {
     return md_dot(g[0], g[1], g[2], g[0], g[1], g[2]);
 }
 NPCD_HD bool md_needs(float bound, float best) { return !(bound > best) & (bound < bits_float(kMdInfBits)); }
+
+// ---- what the tile walk asks of a point (tile_walk.h on the device, host_lanes.h on the host) -----------------------
+struct MdQuery {
+    static constexpr int kLanes = kMdThreads, kScan = kMdScan;
+    typedef float Memo;          // the bound to a box: it does not depend on best, md_needs sees the best of the moment
+    float p[3], slack;
+    bool own;                    // the lane holds a point: one that does not ranks no box and needs no tile
+    NPCD_HD bool rank(const MdBox& box, float* value) const { return *value = md_bound(p, slack, box), own; }
+    NPCD_HD Memo recall(const MdBox& box, float) const { return md_bound(p, slack, box); }
+    NPCD_HD bool needs(Memo bound, float best) const { return own & md_needs(bound, best); }
+    // -> dist2 to the face of corners c [3]; q [3] the closest point
+    NPCD_HD float pair(const MdCorner* c, float* q) const {
+        const float fa[3] = {c[0].x, c[0].y, c[0].z}, fb[3] = {c[1].x, c[1].y, c[1].z}, fc[3] = {c[2].x, c[2].y, c[2].z};
+        return md_pair(p, fa, fb, fc, q);
+    }
+    NPCD_HD void face(const MdCorner* c, int32_t f, float* best, int32_t* best_face) const {
+        float q[3];
+        const float d = pair(c, q);
+        const bool better = md_better(d, f, *best, *best_face);
+        *best = better ? d : *best;
+        *best_face = better ? f : *best_face;
+    }
+};
+NPCD_HD MdQuery md_query(const float* p, bool own) { return MdQuery{{p[0], p[1], p[2]}, md_point_slack(p), own}; }
 
 }  // namespace npcd

@@ -12,15 +12,16 @@
 //             T = (U az + V bz) + W cz and t = float(T / det).  A hit iff t_min <= t <= t_max and t < +inf (rc_hit).
 //   Winner    the lexicographic minimum of (t, face) over the hits, t ordered as a signed float with -0 == +0: rc_better on two
 //             words, rc_key on one.  t_min may be negative.
-//   Reach     rc_reach: the slab test of the segment [from, to] of a ray against a tile's box (mesh_distance.h) enlarged by
+//   Reach     rc_reach: the slab test of the segment [from, to] of a ray against a tile's box (mesh_tiles.h) enlarged by
 //             kRcSlack times the larger of the box's and the origin's 8 ulp, at least kRcSlackFloor; DESIGN.md 5.19 derives why no
 //             hit of the pair rule lies outside it.  A ray that is not tame (|d[kz]| outside [2^-40, 2^40]) reaches every box.
+//   Query     RcQuery: a lane's ray and limits, and the answers of these functions to the tile walk (tile_walk.h).
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "bits.h"
-#include "mesh_distance.h"
+#include "mesh_tiles.h"
 
 namespace npcd {
 
@@ -148,5 +149,29 @@ NPCD_HD bool rc_reach(const RcRay& r, const MdBox& box, float from, float to, fl
     *enter = lo;
     return !beside & (lo <= hi);
 }
+
+// ---- what the tile walk asks of a ray (tile_walk.h on the device, host_lanes.h on the host) --------------------------
+struct RcQuery {
+    static constexpr int kLanes = kRcThreads, kScan = kRcScan;
+    typedef bool Memo;          // whether [t_min, min(best, t_max)] reaches a box, best of the scan group's start: one shrunk since asks for less
+    RcRay ray;                  // of a lane without a ray: not valid, ranks no box and needs no tile
+    float t_min, t_max;
+    NPCD_HD bool rank(const MdBox& box, float* enter) const { return rc_reach(ray, box, t_min, t_max, enter); }
+    NPCD_HD Memo recall(const MdBox& box, float best) const {
+        float enter;
+        return rc_reach(ray, box, t_min, best < t_max ? best : t_max, &enter);
+    }
+    NPCD_HD bool needs(Memo reach, float) const { return reach; }
+    NPCD_HD RcPair pair(const MdCorner* c) const {          // with the face of corners c [3]
+        const float fa[3] = {c[0].x, c[0].y, c[0].z}, fb[3] = {c[1].x, c[1].y, c[1].z}, fc[3] = {c[2].x, c[2].y, c[2].z};
+        return rc_pair(ray, fa, fb, fc);
+    }
+    NPCD_HD void face(const MdCorner* c, int32_t f, float* best, int32_t* best_face) const {
+        const RcPair p = pair(c);
+        const bool better = p.inside && rc_hit(p.t, t_min, t_max) && rc_better(p.t, f, *best, *best_face);
+        *best = better ? p.t : *best;
+        *best_face = better ? f : *best_face;
+    }
+};
 
 }  // namespace npcd

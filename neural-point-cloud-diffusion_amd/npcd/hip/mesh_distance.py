@@ -8,7 +8,7 @@ of (dist2, face): the outputs are the same bits whether tiles of faces are culle
 The call makes no host read: every size is known from the shapes.  There is no CPU fallback: a non-GPU tensor or a wrong dtype raises
 RuntimeError.
 """
-from typing import Dict
+from typing import Callable, Dict, List, Optional
 
 import torch
 
@@ -42,25 +42,37 @@ def sort_order(points: torch.Tensor, vertices: torch.Tensor) -> torch.Tensor:
     return torch.sort(key)[1]
 
 
+def _checked(who: str, tensors: Dict[str, torch.Tensor], sizes: Callable[[], None], boxes: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """The checks that mesh_boxes, closest_on_mesh and npcd.hip.raycast.cast_rays share, in their order.  tensors: name -> argument,
+    int32 for "faces" and fp32 for every other.  Each must be a [N, 3] tensor (ValueError); sizes() then raises ValueError for row
+    counts that the caller cannot take; then they must lie on the GPU, have these dtypes and share one device, with boxes where
+    given (RuntimeError).  -> the tensors, detached and contiguous."""
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a tensor")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{who}: {name} must be [N, 3]; got {tuple(t.shape)}")
+    sizes()
+    require_gpu(*tensors.values(), boxes)
+    if any(t.dtype != (torch.int32 if name == "faces" else torch.float32) for name, t in tensors.items()):
+        raise RuntimeError(f"{who}: faces must be int32 and the others fp32; got " + ", ".join(f"{name} {t.dtype}" for name, t in tensors.items()))
+    if len({t.device for t in (*tensors.values(), boxes) if t is not None}) != 1:
+        raise RuntimeError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t in tensors.items()))
+    return [t.detach().contiguous() for t in tensors.values()]
+
+
 def mesh_boxes(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """vertices [V, 3] fp32 and faces [F, 3] int32 on the GPU, F >= 1 -> the workspace that npcd_mesh_distance_boxes leaves (the
     corners of every face and the box of every tile of TILE_FACES faces) as an int64 tensor: what npcd.hip.raycast.cast_rays takes as
     boxes=, so that many calls on one mesh build it once.  It belongs to these vertices and faces.  One launch, no host read."""
     who = "mesh_boxes"
-    for name, t in (("vertices", vertices), ("faces", faces)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{who}: {name} must be a tensor")
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{who}: {name} must be [N, 3]; got {tuple(t.shape)}")
+
+    def sizes():
+        V, F = int(vertices.shape[0]), int(faces.shape[0])
+        if V >= MAX_VERTICES or not 1 <= F < MAX_FACES:
+            raise ValueError(f"{who}: {V} vertices and {F} faces; vertices must stay below 2^31 and faces in [1, 2^28 = {MAX_FACES})")
+    vertices, faces = _checked(who, {"vertices": vertices, "faces": faces}, sizes)
     V, F = int(vertices.shape[0]), int(faces.shape[0])
-    if V >= MAX_VERTICES or not 1 <= F < MAX_FACES:
-        raise ValueError(f"{who}: {V} vertices and {F} faces; vertices must stay below 2^31 and faces in [1, 2^28 = {MAX_FACES})")
-    require_gpu(vertices, faces)
-    if vertices.dtype != torch.float32 or faces.dtype != torch.int32:
-        raise RuntimeError(f"{who}: vertices must be fp32 and faces int32; got {vertices.dtype} and {faces.dtype}")
-    if faces.device != vertices.device:
-        raise RuntimeError(f"{who}: vertices on {vertices.device}, faces on {faces.device}")
-    vertices, faces = vertices.detach().contiguous(), faces.contiguous()
     L = lib()
     with torch.cuda.device(vertices.device):
         got = L.npcd_mesh_distance_ws_bytes(V, F)
@@ -82,21 +94,14 @@ def closest_on_mesh(points: torch.Tensor, vertices: torch.Tensor, faces: torch.T
     makes culling pay, and scatters the results back.  Neither changes a bit of the outputs.  stats=True adds "evaluated", an int64
     word on the GPU: the (wave, tile) pairs that were evaluated, of ceil(S / WAVE_POINTS) ceil(F / TILE_FACES).  No host read."""
     who = "closest_on_mesh"
-    for name, t in (("points", points), ("vertices", vertices), ("faces", faces)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{who}: {name} must be a tensor")
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{who}: {name} must be [N, 3]; got {tuple(t.shape)}")
+
+    def sizes():
+        S, V, F = int(points.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
+        if V >= MAX_VERTICES or F >= MAX_FACES or S >= MAX_POINTS:
+            raise ValueError(f"{who}: {S} points, {V} vertices and {F} faces; points and vertices must stay below 2^31 and faces below 2^28 = {MAX_FACES}")
+    points, vertices, faces = _checked(who, {"points": points, "vertices": vertices, "faces": faces}, sizes)
     S, V, F = int(points.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
-    if V >= MAX_VERTICES or F >= MAX_FACES or S >= MAX_POINTS:
-        raise ValueError(f"{who}: {S} points, {V} vertices and {F} faces; points and vertices must stay below 2^31 and faces below 2^28 = {MAX_FACES}")
-    require_gpu(points, vertices, faces)
-    if points.dtype != torch.float32 or vertices.dtype != torch.float32 or faces.dtype != torch.int32:
-        raise RuntimeError(f"{who}: points and vertices must be fp32 and faces int32; got {points.dtype}, {vertices.dtype} and {faces.dtype}")
     dev = points.device
-    if vertices.device != dev or faces.device != dev:
-        raise RuntimeError(f"{who}: points on {dev}, vertices on {vertices.device}, faces on {faces.device}")
-    points, vertices, faces = points.detach().contiguous(), vertices.detach().contiguous(), faces.contiguous()
     L = lib()
     with torch.cuda.device(dev):
         out = {"sqdist": torch.full((S,), float("inf"), dtype=torch.float32, device=dev),
@@ -107,10 +112,7 @@ def closest_on_mesh(points: torch.Tensor, vertices: torch.Tensor, faces: torch.T
             out["evaluated"] = evaluated
         if S == 0 or F == 0:
             return out
-        got = L.npcd_mesh_distance_ws_bytes(V, F)
-        check(min(got, 0), "npcd_mesh_distance_ws_bytes")
-        ws = torch.empty(got // 8 + 2, dtype=torch.int64, device=dev)          # a fresh allocation: aligned well beyond the 16 bytes asked for
-        check(L.npcd_mesh_distance_boxes(ptr(vertices), V, ptr(faces), F, ptr(ws), stream_ptr()), "npcd_mesh_distance_boxes")
+        ws = mesh_boxes(vertices, faces)
         order = sort_order(points, vertices) if sort_points and V > 0 and S > 1 else None
         queries = points if order is None else points[order].contiguous()
         res = out if order is None else {k: torch.empty_like(out[k]) for k in ("sqdist", "face", "closest")}

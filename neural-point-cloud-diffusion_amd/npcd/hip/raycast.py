@@ -12,8 +12,8 @@ from typing import Dict, Optional
 
 import torch
 
-from . import check, lib, ptr, require_gpu, stream_ptr
-from .mesh_distance import MAX_FACES, MAX_VERTICES, TILE_FACES, mesh_boxes
+from . import check, lib, ptr, stream_ptr
+from .mesh_distance import MAX_FACES, MAX_VERTICES, TILE_FACES, _checked, mesh_boxes
 
 # rays per wave (kRcThreads of csrc/raycast.h); the tiles are those of mesh_distance (kMdTile): culling decides per (wave, tile)
 WAVE_RAYS = 64
@@ -34,25 +34,17 @@ def cast_rays(origins: torch.Tensor, directions: torch.Tensor, vertices: torch.T
     stats=True adds "evaluated", an int64 word on the GPU: the (wave, tile) pairs that were evaluated, of ceil(R / WAVE_RAYS)
     ceil(F / TILE_FACES).  boxes= takes mesh_boxes(vertices, faces) from an earlier call.  No host read."""
     who = "cast_rays"
-    for name, t in (("origins", origins), ("directions", directions), ("vertices", vertices), ("faces", faces)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{who}: {name} must be a tensor")
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{who}: {name} must be [N, 3]; got {tuple(t.shape)}")
+
+    def sizes():
+        R, V, F = int(origins.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
+        if directions.shape[0] != R:
+            raise ValueError(f"{who}: {R} origins and {int(directions.shape[0])} directions")
+        if V >= MAX_VERTICES or F >= MAX_FACES or R >= MAX_RAYS:
+            raise ValueError(f"{who}: {R} rays, {V} vertices and {F} faces; rays and vertices must stay below 2^31 and faces below 2^28 = {MAX_FACES}")
+    origins, directions, vertices, faces = _checked(who, {"origins": origins, "directions": directions, "vertices": vertices, "faces": faces},
+                                                    sizes, boxes)
     R, V, F = int(origins.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
-    if directions.shape[0] != R:
-        raise ValueError(f"{who}: {R} origins and {int(directions.shape[0])} directions")
-    if V >= MAX_VERTICES or F >= MAX_FACES or R >= MAX_RAYS:
-        raise ValueError(f"{who}: {R} rays, {V} vertices and {F} faces; rays and vertices must stay below 2^31 and faces below 2^28 = {MAX_FACES}")
-    require_gpu(origins, directions, vertices, faces, boxes)
-    if any(t.dtype != torch.float32 for t in (origins, directions, vertices)) or faces.dtype != torch.int32:
-        raise RuntimeError(f"{who}: origins, directions and vertices must be fp32 and faces int32; got {origins.dtype}, {directions.dtype}, "
-                           f"{vertices.dtype} and {faces.dtype}")
     dev = origins.device
-    if any(t.device != dev for t in (directions, vertices, faces)) or (boxes is not None and boxes.device != dev):
-        raise RuntimeError(f"{who}: origins on {dev}, directions on {directions.device}, vertices on {vertices.device}, faces on {faces.device}")
-    origins, directions = origins.detach().contiguous(), directions.detach().contiguous()
-    vertices, faces = vertices.detach().contiguous(), faces.contiguous()
     L = lib()
     with torch.cuda.device(dev):
         out = {"t": torch.full((R,), float("inf"), dtype=torch.float32, device=dev),

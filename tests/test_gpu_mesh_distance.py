@@ -1,14 +1,15 @@
 """Point-to-mesh distance on the GPU: closest_on_mesh against point_mesh_distance_reference bit for bit on the cases
 of tests/test_mesh_distance_cpu.py -- tile and wave edges, the sphere plain, simplified, shifted and scaled, planted duplicates,
-invalid indices, NaN vertices and points -- for every combination of cull and sort_points, twice; culling that really culls; no host
-read; and mesh_deviation, cloud_mesh_distance and extract_mesh(deviation=) on the kernels."""
+invalid indices, NaN vertices and points -- for every combination of cull and sort_points, twice; culling that really culls, and
+the schedule of the walk held to the host's count; no host read; and mesh_deviation, cloud_mesh_distance and
+extract_mesh(deviation=) on the kernels."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from test_mesh_distance_cpu import CASES, K_ULP, KEYS, SAMPLE_ULP, TILE, WAVE, ball, case, hold, reference
+from test_mesh_distance_cpu import CASES, K_ULP, KEYS, SAMPLE_ULP, SCHEDULE, TILE, WAVE, ball, case, hold, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -63,6 +64,19 @@ def test_culling_really_culls():
     ulp = float(np.spacing(np.float32(v.abs().max().item())))
     print(f"the farthest sample lies {math.sqrt(float(first['sqdist'].max())) / ulp:.2f} ulp off its mesh")
     assert math.sqrt(float(first["sqdist"].max())) <= (SAMPLE_ULP + K_ULP) * ulp
+
+
+@pytest.mark.parametrize("name", sorted(SCHEDULE))
+def test_the_schedule_of_the_walk(name):
+    """The kernel's waves evaluate exactly the (wave, tile) pairs that the host's walk over the same policy evaluates (SCHEDULE of
+    tests/test_mesh_distance_cpu.py): points as given, so that a wave holds the host's 64 consecutive points; and every pair without
+    culling."""
+    count, pairs = SCHEDULE[name]
+    culled = run(name, cull=True, sort_points=False, stats=True)
+    every = run(name, cull=False, sort_points=False, stats=True)
+    print(f"{name}: evaluated {int(culled['evaluated'])} of {int(every['evaluated'])} (wave, tile) pairs; the host's walk {count} of {pairs}")
+    assert int(culled["evaluated"]) == count
+    assert int(every["evaluated"]) == pairs == -(-len(case(name)[0]) // WAVE) * -(-len(case(name)[2]) // TILE)
 
 
 def test_no_host_read():

@@ -1,8 +1,8 @@
 """Rays against meshes on the GPU: cast_rays against ray_mesh_reference bit for bit on the cases of
 tests/test_raycast_cpu.py -- tile and wave edges, the sphere plain, simplified, shifted and scaled, planted duplicates, invalid
-indices, NaN vertices, NaN and zero directions, limits on t -- culled and not, twice; culling that really culls; no host read;
-render_mesh of a sphere against the two spheres that enclose its facets; and mesh_render_agreement and extract_mesh(agreement=) on
-the kernels."""
+indices, NaN vertices, NaN and zero directions, limits on t -- culled and not, twice; culling that really culls, and the schedule
+of the walk held to the host's count; no host read; render_mesh of a sphere against the two spheres that enclose its facets; and
+mesh_render_agreement and extract_mesh(agreement=) on the kernels."""
 import math
 
 import numpy as np
@@ -11,7 +11,7 @@ import torch
 
 from npcd.eval.mesh import point_mesh_distance_reference
 from oracle import renderer as orr
-from test_raycast_cpu import CASES, CENTRE, KEYS, TILE, WAVE, ball, case, hold, reference
+from test_raycast_cpu import CASES, CENTRE, KEYS, SCHEDULE, TILE, WAVE, ball, case, hold, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -77,6 +77,17 @@ def test_culling_really_culls():
     print(f"evaluated (wave, tile) pairs of {waves * tiles}: culled {counts[True]} ({counts[True] / (waves * tiles):.3f})")
     assert 0 < counts[True] < waves * tiles == counts[False]
     assert int((first["face"] >= 0).sum()) > 100
+
+
+@pytest.mark.parametrize("name", sorted(SCHEDULE))
+def test_the_schedule_of_the_walk(name):
+    """The kernel's waves evaluate exactly the (wave, tile) pairs that the host's walk over the same policy evaluates (SCHEDULE of
+    tests/test_raycast_cpu.py): a wave holds the host's 64 consecutive rays; and every pair without culling."""
+    count, pairs = SCHEDULE[name]
+    culled, every = run(name, cull=True, stats=True), run(name, cull=False, stats=True)
+    print(f"{name}: evaluated {int(culled['evaluated'])} of {int(every['evaluated'])} (wave, tile) pairs; the host's walk {count} of {pairs}")
+    assert int(culled["evaluated"]) == count
+    assert int(every["evaluated"]) == pairs == -(-len(case(name)[0]) // WAVE) * -(-len(case(name)[3]) // TILE)
 
 
 def test_no_host_read():

@@ -2,8 +2,8 @@
 geometry and the exact cases of the specification, and against the same algorithm in float64; the per-lane code of
 csrc/mesh_distance.h, the code the kernels run, built for the host with sanitizers (csrc/mesh_distance_host.cpp) and held bit for bit to
 the reference on the cases of the GPU test (tests/test_gpu_mesh_distance.py, which imports them from here), with the box bound checked
-against every rounded distance; the kernels' resources from the compiler's own output, the entry points' refusals, the wrapper's
-argument errors, and mesh_deviation, cloud_mesh_distance and extract_mesh(deviation=) with stand-ins."""
+against every rounded distance, and the tiles that waves of 64 points evaluate held to a table; the kernels' resources from the
+compiler's own output, the entry points' refusals, the wrapper's argument errors, and mesh_deviation, cloud_mesh_distance and extract_mesh(deviation=) with stand-ins."""
 import ctypes
 import functools
 import os
@@ -22,7 +22,7 @@ from test_kernel_resources import CSRC, _compile
 from test_simplify_cpu import _Field, same_bits
 from test_smooth_cpu import ball, coarse_ball, soup
 
-TILE, WAVE = 256, 64          # kMdTile and kMdThreads of csrc/mesh_distance.h; test_the_wrapper_knows_the_constants holds them to the source
+TILE, WAVE = 256, 64          # kMdTile of csrc/mesh_tiles.h and kMdThreads of csrc/mesh_distance.h; test_the_wrapper_knows_the_constants holds them
 FACES = (1, 255, 256, 257, 513, 16387)          # one below, at and above a tile, two tiles and one face, 65 tiles
 POINTS = (1, 63, 64, 65, 257, 1024)             # one below, at and above a wave, five waves, sixteen
 KEYS = ("sqdist", "face", "closest")
@@ -274,14 +274,14 @@ def host_program(tmp_path_factory):
     return out
 
 
-def run_on_the_host(program, tmp_path, name, reverse):
+def run_on_the_host(program, tmp_path, name, reverse, wave=False):
     p, v, f = case(name)
     S = len(p)
     with open(tmp_path / "in.bin", "wb") as fh:
         fh.write(np.array([S, len(v), len(f)], dtype="<i4").tobytes())
         fh.write(np.ascontiguousarray(p).tobytes() + np.ascontiguousarray(v).tobytes() + np.ascontiguousarray(f, dtype="<i4").tobytes())
-    r = subprocess.run([program, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")] + (["reverse"] if reverse else []),
-                       capture_output=True, text=True)
+    r = subprocess.run([program, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")] + (["reverse"] if reverse else []) +
+                       (["wave"] if wave else []), capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     raw = open(tmp_path / "out.bin", "rb").read()
     assert len(raw) == 2 * 20 * S + 24
@@ -309,16 +309,36 @@ def test_the_lanes_on_the_host(host_program, tmp_path, name):
         assert evaluated < pairs // 2
 
 
+# The schedule of the culled walk, which no output bit shows: case -> the (wave, tile) pairs that the waves of WAVE
+# consecutive points evaluate, as given, and the waves times the tiles they are out of.  The host program with `wave` counted them;
+# test_the_schedule_of_a_wave holds the program to them and tests/test_gpu_mesh_distance.py the kernel.  The sphere's 257 points are
+# of four kinds in turn, far ones among them, so a wave of them spans the whole sphere and needs most tiles: a wave of one lane
+# evaluates 2141 of 9766
+SCHEDULE = {"ball": (153, 5 * 38), "soup:257x257": (9, 5 * 2)}
+
+
+def test_the_schedule_of_a_wave(host_program, tmp_path):
+    for name, (count, pairs) in SCHEDULE.items():
+        p, _, f = case(name)
+        waves, tiles = -(-len(p) // WAVE), -(-len(f) // TILE)
+        assert waves > 1 and tiles > 1 and pairs == waves * tiles and waves < count < pairs, name
+        every, culled, violations, evaluated, of = run_on_the_host(host_program, tmp_path, name, False, wave=True)
+        hold(every, name, f"{name} in waves, every face")
+        hold(culled, name, f"{name} in waves, culled")
+        print(f"{name}: waves of {WAVE} lanes evaluate {evaluated} of {of} (wave, tile) pairs")
+        assert (violations, evaluated, of) == (0, count, pairs), name
+
+
 # ---- plumbing ----------------------------------------------------------------------------------------------------------------------------
 def test_the_wrapper_knows_the_constants():
     from npcd import hip
     from npcd.eval import mesh
     from npcd.hip import mesh_distance
-    source = open(f"{CSRC}/mesh_distance.h").read()
-    assert int(re.search(r"constexpr int kMdTile = (\d+);", source).group(1)) == mesh_distance.TILE_FACES == TILE
+    source, tiles = open(f"{CSRC}/mesh_distance.h").read(), open(f"{CSRC}/mesh_tiles.h").read()
+    assert int(re.search(r"constexpr int kMdTile = (\d+);", tiles).group(1)) == mesh_distance.TILE_FACES == TILE
     assert int(re.search(r"constexpr int kMdThreads = (\d+);", source).group(1)) == mesh_distance.WAVE_POINTS == WAVE
-    assert "kMdMaxVertices = (int64_t)1 << 31" in source and mesh_distance.MAX_VERTICES == 2 ** 31
-    assert "kMdMaxFaces = (int64_t)1 << 28" in source and mesh_distance.MAX_FACES == mesh.MAX_DISTANCE_FACES == 2 ** 28
+    assert "kMdMaxVertices = (int64_t)1 << 31" in tiles and mesh_distance.MAX_VERTICES == 2 ** 31
+    assert "kMdMaxFaces = (int64_t)1 << 28" in tiles and mesh_distance.MAX_FACES == mesh.MAX_DISTANCE_FACES == 2 ** 28
     assert "kMdMaxPoints = (int64_t)1 << 31" in source and mesh_distance.MAX_POINTS == 2 ** 31
     assert hip.closest_on_mesh is mesh_distance.closest_on_mesh
     assert np.float32(1.0) - np.float32(2.0) ** -11 == np.float32(re.search(r"kMdShrink = ([0-9.]+)f;", source).group(1))

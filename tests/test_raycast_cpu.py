@@ -22,7 +22,7 @@ from test_kernel_resources import CSRC, _compile
 from test_simplify_cpu import _Field, same_bits
 from test_smooth_cpu import CENTRE, ball, coarse_ball, soup
 
-TILE, WAVE = 256, 64          # kMdTile of csrc/mesh_distance.h and kRcThreads of csrc/raycast.h; test_the_wrapper_knows_the_constants holds them
+TILE, WAVE = 256, 64          # kMdTile of csrc/mesh_tiles.h and kRcThreads of csrc/raycast.h; test_the_wrapper_knows_the_constants holds them
 FACES = (1, 255, 256, 257, 513)          # one below, at and above a tile, two tiles and one face
 RAYS = (1, 63, 64, 65, 257)              # one below, at and above a wave, five waves
 KEYS = ("t", "face", "bary", "front")
@@ -395,15 +395,15 @@ def host_program(tmp_path_factory):
     return out
 
 
-def run_on_the_host(program, tmp_path, name, reverse):
+def run_on_the_host(program, tmp_path, name, reverse, wave=False):
     o, d, v, f, t_min, t_max = case(name)
     R = len(o)
     with open(tmp_path / "in.bin", "wb") as fh:
         fh.write(np.array([R, len(v), len(f)], dtype="<i4").tobytes() + np.array([t_min, t_max], dtype="<f4").tobytes())
         fh.write(np.ascontiguousarray(o).tobytes() + np.ascontiguousarray(d).tobytes() + np.ascontiguousarray(v).tobytes() +
                  np.ascontiguousarray(f, dtype="<i4").tobytes())
-    r = subprocess.run([program, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")] + (["reverse"] if reverse else []),
-                       capture_output=True, text=True)
+    r = subprocess.run([program, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")] + (["reverse"] if reverse else []) +
+                       (["wave"] if wave else []), capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     raw = open(tmp_path / "out.bin", "rb").read()
     assert len(raw) == 2 * 21 * R + 24
@@ -433,6 +433,25 @@ def test_the_lanes_on_the_host(host_program, tmp_path, name):
     if name == "ball":
         print(f"{name}: a wave of one lane evaluates {evaluated} of {pairs} (ray, tile) pairs")
         assert evaluated < pairs // 2
+
+
+# The schedule of the culled walk, which no output bit shows: case -> the (wave, tile) pairs that the waves of WAVE
+# consecutive rays evaluate, as given, and the waves times the tiles they are out of.  The host program with `wave` counted them;
+# test_the_schedule_of_a_wave holds the program to them and tests/test_gpu_raycast.py the kernel.  The sphere's 257 rays are of
+# four kinds in turn, from all around it, so a wave of them reaches most tiles: a wave of one lane evaluates 1117 of 9766
+SCHEDULE = {"ball": (151, 5 * 38), "soup:257x257": (9, 5 * 2)}
+
+
+def test_the_schedule_of_a_wave(host_program, tmp_path):
+    for name, (count, pairs) in SCHEDULE.items():
+        o, _, _, f = case(name)[:4]
+        waves, tiles = -(-len(o) // WAVE), -(-len(f) // TILE)
+        assert waves > 1 and tiles > 1 and pairs == waves * tiles and waves < count < pairs, name
+        every, culled, violations, evaluated, of = run_on_the_host(host_program, tmp_path, name, False, wave=True)
+        hold(every, name, f"{name} in waves, every face")
+        hold(culled, name, f"{name} in waves, culled")
+        print(f"{name}: waves of {WAVE} lanes evaluate {evaluated} of {of} (wave, tile) pairs")
+        assert (violations, evaluated, of) == (0, count, pairs), name
 
 
 # ---- plumbing ----------------------------------------------------------------------------------------------------------------------------
