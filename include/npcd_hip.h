@@ -1038,6 +1038,20 @@ int npcd_raycast_query(const float* origins, const float* directions, int64_t R,
                        int64_t F, const void* ws, float t_min, float t_max, int cull, float* t, int32_t* face, float* bary, int8_t* front,
                        int64_t* evaluated, void* stream);
 
+/* ---- how often every ray crosses one mesh, per facing (added within ABI 10; csrc/crossings.hip, csrc/raycast.h).
+ * The arrays, their limits and ws are those of npcd_raycast_query.  The specification is restated by crossings_reference of
+ * npcd/eval/mesh.py, and the kernel is held to it bit for bit.
+ *   npcd_crossings_query: per ray the number of faces it crosses with t_min <= t <= t_max and t < +inf, front [R] int32 those with
+ *       det > 0 (the face's normal (B - A) x (C - A) points against the ray) and back [R] int32 those with det < 0.  The corners,
+ *       edge functions, det and t are those of npcd_raycast_query; a pair crosses iff each directed edge owns the origin by the
+ *       top-left rule, so an edge or a vertex that faces share is crossed once and a face of no projected area never.  A ray that
+ *       is not usable gets (0, 0).  cull = 1 skips a tile whose enlarged box no ray segment [t_min, t_max] of a wave reaches; cull
+ *       = 0 evaluates every tile.  The outputs are the same counts.  evaluated as for npcd_raycast_query.  One launch.
+ * Refusals as for npcd_raycast_query. */
+int npcd_crossings_query(const float* origins, const float* directions, int64_t R, const float* vertices, int64_t V, const int32_t* faces,
+                         int64_t F, const void* ws, float t_min, float t_max, int cull, int32_t* front, int32_t* back, int64_t* evaluated,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

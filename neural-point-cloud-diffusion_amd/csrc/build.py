@@ -90,6 +90,9 @@ SOURCES = {
     # the first hit of a ray is picked by comparing t = float(T / det) bit for bit with its numpy restatement: the fp32 shear of the
     # corners and the float64 edge functions, T and det are rounded as written.  Single operations, as above
     "raycast.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # the crossings of a ray are counted from the same corners, edge functions and t, compared bit for bit with their numpy
+    # restatement: the flags of raycast.hip
+    "crossings.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc", "-ffast-math" if False else "-fno-fast-math"]

@@ -1,6 +1,6 @@
 // What the stand-alone host programs (surface_host.cpp, simplify_host.cpp, smooth_host.cpp, components_host.cpp, mesh_distance_host.cpp,
-// raycast_host.cpp) share: whole-array file I/O, the order in which a loop stands in for the lanes of a launch, the prefix sums that
-// stand in for the kernels' scans and, for the two mesh query programs, the head and tail of their files, the boxes launch and the tile
+// raycast_host.cpp, crossings_host.cpp) share: whole-array file I/O, the order in which a loop stands in for the lanes of a launch, the prefix sums that
+// stand in for the kernels' scans and, for the mesh query programs, the head and tail of their files, the boxes launch and the tile
 // walk of csrc/tile_walk.h over the same Query policies.  Host only; not part of libnpcd_hip.so.
 #pragma once
 #include <cstdint>
@@ -45,7 +45,7 @@ T scan_in_place(T* x, int64_t n, bool reverse) {
     return total;
 }
 
-// ---- the two mesh query programs: PROGRAM IN OUT [reverse] [wave] ------------------------------------------------------------------------
+// ---- the mesh query programs: PROGRAM IN OUT [reverse] [wave] ----------------------------------------------------------------------------
 // the head of an input file: int32 N (queries), V, F
 inline bool read_head(FILE* in, int64_t* N, int64_t* V, int64_t* F) {
     int32_t head[3];
@@ -70,6 +70,13 @@ struct HostTiles {
     const MdCorner* face(int64_t f) const { return corners.data() + f * 3; }
 };
 
+// tile_eval (tile_walk.h): every lane of a wave takes the faces of tile t, those below F
+template <class Query>
+void host_tile_eval(const Query* q, int lanes, const HostTiles& m, int64_t t, typename Query::State* state) {
+    for (int l = 0; l < lanes; ++l)
+        for (int64_t f = t * kMdTile; f < m.F && f < (t + 1) * kMdTile; ++f) q[l].face(m.face(f), (int32_t)f, &state[l]);
+}
+
 // tile_walk<Query, true> (tile_walk.h) for all queries, in waves of W consecutive ones; `order` gives the tile of each step of the
 // walk, finish(i, best, best_face) stores what the kernel stores for query i.  A tile is evaluated, by every lane, if any lane asks
 // for it.  A wave of one lane scans one box at a time: it judges every box with its best of the moment, which is what these programs
@@ -82,16 +89,14 @@ int64_t host_tile_walk(const std::vector<Query>& queries, const HostTiles& m, La
     for (size_t i0 = 0; i0 < queries.size(); i0 += W) {
         const Query* q = queries.data() + i0;
         const int lanes = queries.size() - i0 < W ? (int)(queries.size() - i0) : W;
-        float best[W];
-        int32_t best_face[W];
+        TileWinner won[W];
         int64_t nearest[W];
         const auto evaluate = [&](int64_t t) {
-            for (int l = 0; l < lanes; ++l)
-                for (int64_t f = t * kMdTile; f < m.F && f < (t + 1) * kMdTile; ++f) q[l].face(m.face(f), (int32_t)f, &best[l], &best_face[l]);
+            host_tile_eval(q, lanes, m, t, won);
             evaluated += 1;
         };
         for (int l = 0; l < lanes; ++l) {
-            best[l] = inf, best_face[l] = -1, nearest[l] = -1;
+            won[l] = TileWinner{inf, -1}, nearest[l] = -1;
             float least = inf, value;
             for (int64_t t = 0; t < m.tiles; ++t)
                 if (q[l].rank(m.boxes[t], &value) && value < least) least = value, nearest[l] = t;
@@ -105,15 +110,37 @@ int64_t host_tile_walk(const std::vector<Query>& queries, const HostTiles& m, La
             typename Query::Memo memo[kScan][W];
             const int n = m.tiles - s0 < kScan ? (int)(m.tiles - s0) : kScan;
             for (int k = 0; k < n; ++k)
-                for (int l = 0; l < lanes; ++l) memo[k][l] = q[l].recall(m.boxes[order(s0 + k, m.tiles)], best[l]);
+                for (int l = 0; l < lanes; ++l) memo[k][l] = q[l].recall(m.boxes[order(s0 + k, m.tiles)], won[l].best);
             for (int k = 0; k < n; ++k) {
                 const int64_t t = order(s0 + k, m.tiles);
                 bool needed = false, before = false;
-                for (int l = 0; l < lanes; ++l) needed = needed || q[l].needs(memo[k][l], best[l]), before = before || nearest[l] == t;
+                for (int l = 0; l < lanes; ++l) needed = needed || q[l].needs(memo[k][l], won[l].best), before = before || nearest[l] == t;
                 if (needed && !before) evaluate(t);
             }
         }
-        for (int l = 0; l < lanes; ++l) finish(i0 + l, best[l], best_face[l]);
+        for (int l = 0; l < lanes; ++l) finish(i0 + l, won[l].best, won[l].face);
+    }
+    return evaluated;
+}
+
+// tile_sweep<Query, true> (tile_walk.h) the same way; finish(i, state) stores what the kernel stores for query i.  A lane's need of a
+// tile does not depend on what it has found, so the scan groups leave no trace and a wave of one lane evaluates what the lane reaches
+template <class Query, int W, class Finish>
+int64_t host_tile_sweep(const std::vector<Query>& queries, const HostTiles& m, LaneOrder order, Finish finish) {
+    int64_t evaluated = 0;
+    for (size_t i0 = 0; i0 < queries.size(); i0 += W) {
+        const Query* q = queries.data() + i0;
+        const int lanes = queries.size() - i0 < W ? (int)(queries.size() - i0) : W;
+        typename Query::State state[W] = {};
+        for (int64_t s = 0; s < m.tiles; ++s) {
+            const int64_t t = order(s, m.tiles);
+            bool needed = false;
+            for (int l = 0; l < lanes; ++l) needed = needed || q[l].reaches(m.boxes[t]);
+            if (!needed) continue;
+            host_tile_eval(q, lanes, m, t, state);
+            evaluated += 1;
+        }
+        for (int l = 0; l < lanes; ++l) finish(i0 + l, state[l]);
     }
     return evaluated;
 }

@@ -99,6 +99,7 @@ NPCD_HD bool md_needs(float bound, float best) { return !(bound > best) & (bound
 // ---- what the tile walk asks of a point (tile_walk.h on the device, host_lanes.h on the host) -----------------------
 struct MdQuery {
     static constexpr int kLanes = kMdThreads, kScan = kMdScan;
+    typedef TileWinner State;
     typedef float Memo;          // the bound to a box: it does not depend on best, md_needs sees the best of the moment
     float p[3], slack;
     bool own;                    // the lane holds a point: one that does not ranks no box and needs no tile
@@ -110,12 +111,12 @@ struct MdQuery {
         const float fa[3] = {c[0].x, c[0].y, c[0].z}, fb[3] = {c[1].x, c[1].y, c[1].z}, fc[3] = {c[2].x, c[2].y, c[2].z};
         return md_pair(p, fa, fb, fc, q);
     }
-    NPCD_HD void face(const MdCorner* c, int32_t f, float* best, int32_t* best_face) const {
+    NPCD_HD void face(const MdCorner* c, int32_t f, State* won) const {
         float q[3];
         const float d = pair(c, q);
-        const bool better = md_better(d, f, *best, *best_face);
-        *best = better ? d : *best;
-        *best_face = better ? f : *best_face;
+        const bool better = md_better(d, f, won->best, won->face);
+        won->best = better ? d : won->best;
+        won->face = better ? f : won->face;
     }
 };
 NPCD_HD MdQuery md_query(const float* p, bool own) { return MdQuery{{p[0], p[1], p[2]}, md_point_slack(p), own}; }

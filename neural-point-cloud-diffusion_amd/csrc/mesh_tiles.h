@@ -28,6 +28,11 @@ struct alignas(16) MdBox {          // one tile
 
 NPCD_HD int64_t md_tiles(int64_t F) { return (F + kMdTile - 1) / kMdTile; }
 
+struct TileWinner {          // what a lane of a nearest-face or first-hit query keeps while its wave walks the tiles (tile_walk.h)
+    float best;          // +inf: no face won
+    int32_t face;        // -1 then
+};
+
 struct MdWs {          // the workspace: 16-byte aligned base
     MdBox* boxes;              // [tiles]
     MdCorner* corners;         // [tiles * kMdTile, 3]

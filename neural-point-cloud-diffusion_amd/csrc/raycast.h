@@ -16,6 +16,9 @@
 //             kRcSlack times the larger of the box's and the origin's 8 ulp, at least kRcSlackFloor; DESIGN.md 5.19 derives why no
 //             hit of the pair rule lies outside it.  A ray that is not tame (|d[kz]| outside [2^-40, 2^40]) reaches every box.
 //   Query     RcQuery: a lane's ray and limits, and the answers of these functions to the tile walk (tile_walk.h).
+//   Crossing  rc_cross: the counting form of the pair on the same corners, U, V, W, det and t: a half-open rule in
+//             place of the inclusive one, so that every crossing of a closed surface is counted once.  CrQuery (csrc/crossings.hip)
+//             counts those with rc_hit per facing; every crossing is a hit of rc_pair, so rc_reach culls none.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -88,23 +91,53 @@ NPCD_HD void rc_project(const RcRay& r, const float* P, float* out) {
     out[2] = r.Sz * pz;
 }
 
-NPCD_HD RcPair rc_pair(const RcRay& r, const float* A, const float* B, const float* C) {
-    float a[3], b[3], c[3];
+// the sheared corners a, b, c [3] and the edge functions of a pair -> whether the ray is valid, none of them is a NaN and det != 0
+NPCD_HD bool rc_edges(const RcRay& r, const float* A, const float* B, const float* C, float* a, float* b, float* c, RcPair* p) {
     rc_project(r, A, a), rc_project(r, B, b), rc_project(r, C, c);
     const double ax = a[0], ay = a[1], bx = b[0], by = b[1], cx = c[0], cy = c[1];
-    RcPair p;
-    p.U = cx * by - cy * bx;
-    p.V = ax * cy - ay * cx;
-    p.W = bx * ay - by * ax;
-    p.det = (p.U + p.V) + p.W;
-    const bool below = (p.U < 0.0) | (p.V < 0.0) | (p.W < 0.0), above = (p.U > 0.0) | (p.V > 0.0) | (p.W > 0.0);
-    const bool numbers = (p.U == p.U) & (p.V == p.V) & (p.W == p.W);          // det is then a NaN only if it is inf - inf
-    p.inside = r.valid & numbers & !(below & above) & (p.det != 0.0) & (p.det == p.det);
-    p.t = bits_float(0x7fc00000u);
-    if (p.inside) {          // few pairs come here, and the float64 division costs as much as the edge functions: a branch, not a select
-        const double T = (p.U * (double)a[2] + p.V * (double)b[2]) + p.W * (double)c[2];
-        p.t = (float)(T / p.det);
+    p->U = cx * by - cy * bx;
+    p->V = ax * cy - ay * cx;
+    p->W = bx * ay - by * ax;
+    p->det = (p->U + p->V) + p->W;
+    const bool numbers = (p->U == p->U) & (p->V == p->V) & (p->W == p->W);          // det is then a NaN only if it is inf - inf
+    return r.valid & numbers & (p->det != 0.0) & (p->det == p->det);
+}
+// t of a pair that `inside` keeps, NaN for the others
+NPCD_HD void rc_depth(RcPair* p, bool inside, const float* a, const float* b, const float* c) {
+    p->inside = inside;
+    p->t = bits_float(0x7fc00000u);
+    if (inside) {          // few pairs come here, and the float64 division costs as much as the edge functions: a branch, not a select
+        const double T = (p->U * (double)a[2] + p->V * (double)b[2]) + p->W * (double)c[2];
+        p->t = (float)(T / p->det);
     }
+}
+
+NPCD_HD RcPair rc_pair(const RcRay& r, const float* A, const float* B, const float* C) {
+    float a[3], b[3], c[3];
+    RcPair p;
+    const bool sound = rc_edges(r, A, B, C, a, b, c, &p);
+    const bool below = (p.U < 0.0) | (p.V < 0.0) | (p.W < 0.0), above = (p.U > 0.0) | (p.V > 0.0) | (p.W > 0.0);
+    rc_depth(&p, sound & !(below & above), a, b, c);
+    return p;
+}
+
+// does the directed edge start -> end, whose edge function at the origin is E, own the origin?  `pos`: det > 0; otherwise E and the
+// edge are turned.  On the edge itself (E == 0) the top-left rule decides, from comparisons of the sheared coordinates
+NPCD_HD bool rc_owns(double E, bool pos, const float* start, const float* end) {
+    const bool strict = pos ? E > 0.0 : E < 0.0;
+    const bool up = pos ? end[1] > start[1] : end[1] < start[1];            // dy > 0
+    const bool left = pos ? end[0] < start[0] : end[0] > start[0];          // dx < 0
+    return strict | ((E == 0.0) & (up | ((end[1] == start[1]) & left)));
+}
+// the counting form of rc_pair: the same corners, edge functions, det and t; inside iff every edge owns the origin,
+// so that of the faces around a shared edge or vertex exactly one is crossed, and a face of no projected area never is
+NPCD_HD RcPair rc_cross(const RcRay& r, const float* A, const float* B, const float* C) {
+    float a[3], b[3], c[3];
+    RcPair p;
+    const bool sound = rc_edges(r, A, B, C, a, b, c, &p);
+    const bool pos = p.det > 0.0;
+    const bool u = rc_owns(p.U, pos, c, b), v = rc_owns(p.V, pos, a, c), w = rc_owns(p.W, pos, b, a);          // c -> b, a -> c, b -> a
+    rc_depth(&p, sound & u & v & w, a, b, c);
     return p;
 }
 NPCD_HD bool rc_hit(float t, float t_min, float t_max) { return (t >= t_min) & (t <= t_max) & (t < bits_float(kMdInfBits)); }
@@ -153,6 +186,7 @@ NPCD_HD bool rc_reach(const RcRay& r, const MdBox& box, float from, float to, fl
 // ---- what the tile walk asks of a ray (tile_walk.h on the device, host_lanes.h on the host) --------------------------
 struct RcQuery {
     static constexpr int kLanes = kRcThreads, kScan = kRcScan;
+    typedef TileWinner State;
     typedef bool Memo;          // whether [t_min, min(best, t_max)] reaches a box, best of the scan group's start: one shrunk since asks for less
     RcRay ray;                  // of a lane without a ray: not valid, ranks no box and needs no tile
     float t_min, t_max;
@@ -166,11 +200,36 @@ struct RcQuery {
         const float fa[3] = {c[0].x, c[0].y, c[0].z}, fb[3] = {c[1].x, c[1].y, c[1].z}, fc[3] = {c[2].x, c[2].y, c[2].z};
         return rc_pair(ray, fa, fb, fc);
     }
-    NPCD_HD void face(const MdCorner* c, int32_t f, float* best, int32_t* best_face) const {
+    NPCD_HD void face(const MdCorner* c, int32_t f, State* won) const {
         const RcPair p = pair(c);
-        const bool better = p.inside && rc_hit(p.t, t_min, t_max) && rc_better(p.t, f, *best, *best_face);
-        *best = better ? p.t : *best;
-        *best_face = better ? f : *best_face;
+        const bool better = p.inside && rc_hit(p.t, t_min, t_max) && rc_better(p.t, f, won->best, won->face);
+        won->best = better ? p.t : won->best;
+        won->face = better ? f : won->face;
+    }
+};
+
+// ---- counting crossings (crossings.hip): the need of a lane never shrinks, so the wave sweeps (tile_sweep) ---------------
+struct RcCrossings {
+    int32_t front, back;          // the counted crossings with det > 0 and with det < 0
+};
+struct CrQuery {
+    static constexpr int kLanes = kRcThreads, kScan = kRcScan;
+    typedef RcCrossings State;
+    RcRay ray;                  // of a lane without a ray: not valid, reaches no box
+    float t_min, t_max;
+    NPCD_HD bool reaches(const MdBox& box) const {
+        float enter;
+        return rc_reach(ray, box, t_min, t_max, &enter);
+    }
+    NPCD_HD RcPair pair(const MdCorner* c) const {
+        const float fa[3] = {c[0].x, c[0].y, c[0].z}, fb[3] = {c[1].x, c[1].y, c[1].z}, fc[3] = {c[2].x, c[2].y, c[2].z};
+        return rc_cross(ray, fa, fb, fc);
+    }
+    NPCD_HD void face(const MdCorner* c, int32_t, State* count) const {
+        const RcPair p = pair(c);
+        const bool counted = p.inside && rc_hit(p.t, t_min, t_max), pos = p.det > 0.0;          // an inside pair has det != 0
+        count->front += (counted & pos) ? 1 : 0;
+        count->back += (counted & !pos) ? 1 : 0;
     }
 };
 

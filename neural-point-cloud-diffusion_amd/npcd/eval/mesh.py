@@ -13,10 +13,13 @@ extract_mesh(smooth=n, topology=True) applies both.  How far two surfaces lie ap
 `point_mesh_distance_reference` restates npcd.hip.mesh_distance, `mesh_deviation` and `cloud_mesh_distance` report mean, rms and
 maximum distances, and extract_mesh(deviation=n) says what simplifying and smoothing cost.  Looking at a mesh likewise (DESIGN.md
 5.19): `ray_mesh_reference` restates npcd.hip.raycast, `render_mesh` gives mask, depth, face, normal and colour at the renderer's own
-rays, `mesh_render_agreement` compares them with the field's render, and extract_mesh(agreement=cameras) reports it.
+rays, `mesh_render_agreement` compares them with the field's render, and extract_mesh(agreement=cameras) reports it.  Telling
+inside from outside likewise: `crossings_reference` restates npcd.hip.crossings, `voxelize_mesh`,
+`mesh_signed_distance` and `mesh_volume_iou` rest on it, and extract_mesh(enclosure=True) reports whether the mesh encloses what the
+field calls solid (`mesh_enclosure`).
 
-This module imports without a GPU; only extract_mesh, sample_mesh_clouds, mesh_deviation, cloud_mesh_distance, render_mesh and
-mesh_render_agreement need one."""
+This module imports without a GPU; only extract_mesh, sample_mesh_clouds, mesh_deviation, cloud_mesh_distance, render_mesh,
+mesh_render_agreement, voxelize_mesh, mesh_signed_distance, mesh_volume_iou and mesh_enclosure need one."""
 import itertools
 import math
 from typing import Dict, List, Optional, Sequence
@@ -678,33 +681,23 @@ def ray_axes(directions: np.ndarray):
     return kx, ky, kz, usable
 
 
-def ray_mesh_reference(origins, directions, vertices, faces, t_min: float = 0.0, t_max: float = float("inf"), chunk: int = 256) -> Dict[str, np.ndarray]:
-    """The specification of npcd.hip.raycast.cast_rays (DESIGN.md 5.19) in numpy: brute force, `chunk` faces at a time.  origins,
-    directions [R, 3], vertices [V, 3], faces [F, 3] -> {"t" [R] float32, "face" [R] int32, "bary" [R, 3] float32, "front" [R] int8}.
-
-    A face takes part if its three indices lie in [0, V).  With the axes of ray_axes, Sx = d[kx] / d[kz], Sy = d[ky] / d[kz] and Sz =
-    1 / d[kz] in fp32; per corner p = P - o, px = p[kx] - Sx p[kz], py = p[ky] - Sy p[kz], pz = Sz p[kz] in fp32.  In float64 from those:
-    U = cx by - cy bx, V = ax cy - ay cx, W = bx ay - by ax, det = (U + V) + W; a pair misses if one of U, V, W is below 0 and another
-    above, if det == 0 or anything is NaN; T = (U az + V bz) + W cz, t = float32(T / det), a hit iff t_min <= t <= t_max and t < +inf.
-    The winner is the lexicographic minimum of (t, face), t as a signed float (-0 == +0); bary = float32(U / det, V / det, W / det),
-    front = det > 0.  A ray that is not usable (a component of o or d not finite, d[kz] == 0) or hits nothing keeps (+inf, -1, zeros,
-    0)."""
+def _ray_face_chunks(who: str, origins, directions, vertices, faces, chunk: int):
+    """Steps 1 to 3 of DESIGN.md 5.19, which ray_mesh_reference and crossings_reference share: checks the arrays and yields, per
+    `chunk` faces that hold a face that takes part, (index [n] of those faces, x, y, z [R, n, 3 corners] float64: the fp32 sheared
+    corners; U, V, W, det [R, n] float64; usable [R] bool: origin and direction finite, d[kz] != 0).  Run under np.errstate."""
     o = np.ascontiguousarray(np.asarray(origins, dtype=np.float32))
     d = np.ascontiguousarray(np.asarray(directions, dtype=np.float32))
     v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32))
     f = np.asarray(faces)
     if any(a.ndim != 2 or a.shape[1] != 3 for a in (o, d, v, f)) or len(o) != len(d):
-        raise ValueError(f"ray_mesh_reference: origins and directions must be [R, 3], vertices and faces [N, 3]; got {o.shape}, {d.shape}, "
+        raise ValueError(f"{who}: origins and directions must be [R, 3], vertices and faces [N, 3]; got {o.shape}, {d.shape}, "
                          f"{v.shape} and {f.shape}")
     if f.size and not np.issubdtype(f.dtype, np.integer):
-        raise ValueError("ray_mesh_reference: faces must hold integers")
+        raise ValueError(f"{who}: faces must hold integers")
     f = f.astype(np.int64)
     R, V, F = len(o), len(v), len(f)
     if F >= MAX_DISTANCE_FACES:
-        raise ValueError(f"ray_mesh_reference: {F} faces; they must stay below 2^28 = {MAX_DISTANCE_FACES}")
-    t_min, t_max = np.float32(t_min), np.float32(t_max)
-    out = {"t": np.full(R, np.inf, dtype=np.float32), "face": np.full(R, -1, dtype=np.int32), "bary": np.zeros((R, 3), dtype=np.float32),
-           "front": np.zeros(R, dtype=np.int8)}
+        raise ValueError(f"{who}: {F} faces; they must stay below 2^28 = {MAX_DISTANCE_FACES}")
     rows = np.arange(R)
     kx, ky, kz, usable = ray_axes(d)
     usable &= np.isfinite(o).all(axis=1)
@@ -719,7 +712,6 @@ def ray_mesh_reference(origins, directions, vertices, faces, t_min: float = 0.0,
             valid = ((part >= 0) & (part < V)).all(axis=1)
             if not valid.any():
                 continue
-            index = first + np.nonzero(valid)[0]
             p = v[part[valid]][None] - o[:, None, None, :]          # [R, n, 3 corners, 3] float32
             pz = pick(p, kz)
             x = (pick(p, kx) - Sx[:, None, None] * pz).astype(np.float64)
@@ -729,7 +721,27 @@ def ray_mesh_reference(origins, directions, vertices, faces, t_min: float = 0.0,
             U = x[..., 2] * y[..., 1] - y[..., 2] * x[..., 1]
             Vf = x[..., 0] * y[..., 2] - y[..., 0] * x[..., 2]
             W = x[..., 1] * y[..., 0] - y[..., 1] * x[..., 0]
-            det = (U + Vf) + W
+            yield first + np.nonzero(valid)[0], x, y, z, U, Vf, W, (U + Vf) + W, usable
+
+
+def ray_mesh_reference(origins, directions, vertices, faces, t_min: float = 0.0, t_max: float = float("inf"), chunk: int = 256) -> Dict[str, np.ndarray]:
+    """The specification of npcd.hip.raycast.cast_rays (DESIGN.md 5.19) in numpy: brute force, `chunk` faces at a time.  origins,
+    directions [R, 3], vertices [V, 3], faces [F, 3] -> {"t" [R] float32, "face" [R] int32, "bary" [R, 3] float32, "front" [R] int8}.
+
+    A face takes part if its three indices lie in [0, V).  With the axes of ray_axes, Sx = d[kx] / d[kz], Sy = d[ky] / d[kz] and Sz =
+    1 / d[kz] in fp32; per corner p = P - o, px = p[kx] - Sx p[kz], py = p[ky] - Sy p[kz], pz = Sz p[kz] in fp32.  In float64 from those:
+    U = cx by - cy bx, V = ax cy - ay cx, W = bx ay - by ax, det = (U + V) + W; a pair misses if one of U, V, W is below 0 and another
+    above, if det == 0 or anything is NaN; T = (U az + V bz) + W cz, t = float32(T / det), a hit iff t_min <= t <= t_max and t < +inf.
+    The winner is the lexicographic minimum of (t, face), t as a signed float (-0 == +0); bary = float32(U / det, V / det, W / det),
+    front = det > 0.  A ray that is not usable (a component of o or d not finite, d[kz] == 0) or hits nothing keeps (+inf, -1, zeros,
+    0)."""
+    t_min, t_max = np.float32(t_min), np.float32(t_max)
+    R = len(np.asarray(origins))
+    out = {"t": np.full(R, np.inf, dtype=np.float32), "face": np.full(R, -1, dtype=np.int32), "bary": np.zeros((R, 3), dtype=np.float32),
+           "front": np.zeros(R, dtype=np.int8)}
+    rows = np.arange(R)
+    with np.errstate(all="ignore"):
+        for index, x, y, z, U, Vf, W, det, usable in _ray_face_chunks("ray_mesh_reference", origins, directions, vertices, faces, chunk):
             below, above = (U < 0) | (Vf < 0) | (W < 0), (U > 0) | (Vf > 0) | (W > 0)
             inside = usable[:, None] & ~(below & above) & (det != 0) & ~(np.isnan(U) | np.isnan(Vf) | np.isnan(W) | np.isnan(det))
             T = (U * z[..., 0] + Vf * z[..., 1]) + W * z[..., 2]
@@ -743,6 +755,48 @@ def ray_mesh_reference(origins, directions, vertices, faces, t_min: float = 0.0,
             out["t"][w], out["face"][w] = least[wins], index[a].astype(np.int32)
             out["bary"][w] = np.stack([U[w, a] / det[w, a], Vf[w, a] / det[w, a], W[w, a] / det[w, a]], axis=1).astype(np.float32)
             out["front"][w] = (det[w, a] > 0).astype(np.int8)
+    return out
+
+
+def crossings_reference(origins, directions, vertices, faces, t_min: float = 0.0, t_max: float = float("inf"), chunk: int = 256,
+                        inclusive: bool = False) -> Dict[str, np.ndarray]:
+    """The specification of npcd.hip.crossings.count_crossings in numpy: brute force, `chunk` faces at a time.
+    origins, directions [R, 3], vertices [V, 3], faces [F, 3] -> {"front" [R], "back" [R] int32}: how many faces the ray crosses
+    with t in [t_min, t_max], those whose normal (B - A) x (C - A) points against the ray and those whose normal points along it.
+
+    The sheared corners, U, V, W, det, T and t = float32(T / det) are those of ray_mesh_reference.  With s = sign(det), a pair
+    crosses iff the ray is usable, nothing is NaN, det != 0 and each of the directed edges U: c -> b, V: a -> c, W: b -> a owns the
+    origin: s E > 0, or E == 0 and, with (dx, dy) = s (end - start) in the fp32 sheared coordinates, their signs decided by comparing
+    the coordinates, dy > 0 or (dy == 0 and dx < 0): the rasteriser's top-left rule.  An edge that two faces share from opposite
+    sides is owned by one of them, a fan around a vertex covers the origin once, a face of no projected area never counts.  A
+    crossing counts iff t_min <= t <= t_max and t < +inf; it is a front crossing if det > 0 and a back crossing if det < 0.  A ray
+    that is not usable gets (0, 0).  inclusive=True counts the hits of ray_mesh_reference's pair rule instead, which counts a ray
+    through a shared edge or a vertex once per face around it: what the rule above is there to avoid.
+
+    Unspecified: which side a point within rounding of the surface falls on (the fp32 shear moves a corner by a few ulp), and what
+    parity means for a mesh that is not closed."""
+    t_min, t_max = np.float32(t_min), np.float32(t_max)
+    R = len(np.asarray(origins))
+    out = {"front": np.zeros(R, dtype=np.int32), "back": np.zeros(R, dtype=np.int32)}
+    with np.errstate(all="ignore"):
+        for _, x, y, z, U, Vf, W, det, usable in _ray_face_chunks("crossings_reference", origins, directions, vertices, faces, chunk):
+            numbers = ~(np.isnan(U) | np.isnan(Vf) | np.isnan(W) | np.isnan(det))
+            if inclusive:
+                below, above = (U < 0) | (Vf < 0) | (W < 0), (U > 0) | (Vf > 0) | (W > 0)
+                inside = ~(below & above)
+            else:
+                pos = det > 0
+
+                def owns(E, start, end):
+                    up = np.where(pos, y[..., end] > y[..., start], y[..., end] < y[..., start])
+                    left = np.where(pos, x[..., end] < x[..., start], x[..., end] > x[..., start])
+                    return np.where(pos, E > 0, E < 0) | ((E == 0) & (up | ((y[..., end] == y[..., start]) & left)))
+                inside = owns(U, 2, 1) & owns(Vf, 0, 2) & owns(W, 1, 0)
+            T = (U * z[..., 0] + Vf * z[..., 1]) + W * z[..., 2]
+            t = (T / det).astype(np.float32)
+            counted = usable[:, None] & numbers & (det != 0) & inside & (t >= t_min) & (t <= t_max) & (t < np.float32(np.inf))
+            out["front"] += (counted & (det > 0)).sum(axis=1, dtype=np.int32)
+            out["back"] += (counted & (det < 0)).sum(axis=1, dtype=np.int32)
     return out
 
 
@@ -949,6 +1003,128 @@ def mesh_render_agreement(pointnerf, coords, feats, mesh, extrinsics: torch.Tens
     return out
 
 
+# the lattice nodes that one wave of voxelize_mesh holds, (z, y, x), for rays along +x: PATCH_ACROSS, an 8 x 8 patch across the rays,
+# or PATCH_BLOCK, a 4 x 4 x 4 block.  Which is faster, and whether an oblique direction beats +x, tools/probes/gpu_dev_crossings.py
+# measures; the defaults below are first guesses until it has run (docs/experiments.md R39.1)
+PATCH_ACROSS, PATCH_BLOCK = (8, 8, 1), (4, 4, 4)
+VOXEL_PATCH = PATCH_ACROSS
+VOXEL_DIRECTION = (1.0, 0.0, 0.0)
+
+
+def patch_order(nodes: Sequence[int], patch: Sequence[int], device) -> torch.Tensor:
+    """The row-major node numbers of a (Gz, Gy, Gx) lattice in the order of its patches of `patch` = (pz, py, px) nodes, row-major
+    within a patch and among the patches: with 64 nodes to a patch, the 64 rays of a wave of count_crossings start at neighbours.
+    int64 [Gz Gy Gx]; a patch that reaches past the lattice is shorter, so waves then straddle patches."""
+    (gz, gy, gx), (pz, py, px) = (int(g) for g in nodes), (int(p) for p in patch)
+    z, y, x = torch.meshgrid(torch.arange(gz, device=device), torch.arange(gy, device=device), torch.arange(gx, device=device), indexing="ij")
+    ay, ax = (gy + py - 1) // py, (gx + px - 1) // px
+    key = ((((z // pz * ay + y // py) * ax + x // px) * pz + z % pz) * py + y % py) * px + x % px
+    return torch.sort(key.reshape(-1))[1]
+
+
+def _on_device(triple, device) -> torch.Tensor:
+    """Three numbers, host values or a tensor, as fp32 [3] on the device without a copy from the host, which would wait for the stream."""
+    if isinstance(triple, torch.Tensor) and triple.device == device:
+        return triple.to(torch.float32).reshape(3)
+    values = triple.tolist() if isinstance(triple, torch.Tensor) else list(triple)
+    if len(values) != 3:
+        raise ValueError(f"voxelize_mesh: origin and spacing must hold three numbers; got {triple!r}")
+    return torch.stack([torch.full((), float(x), dtype=torch.float32, device=device) for x in values])
+
+
+@torch.no_grad()
+def voxelize_mesh(mesh, origin, spacing, nodes: Sequence[int], direction: Sequence[float] = VOXEL_DIRECTION,
+                  patch: Sequence[int] = VOXEL_PATCH, container=None) -> torch.Tensor:
+    """Which nodes of a lattice lie inside a closed mesh on the GPU, as isosurface or extract_mesh return it -> bool [Gz, Gy, Gx],
+    nodes = (Gz, Gy, Gx).  Node (x, y, z) lies at origin + spacing * (x, y, z) in fp32, as for npcd.hip.isosurface; origin and spacing
+    are (x, y, z) host values or tensors.  Inside by the parity of the crossings of the ray from the node along `direction`
+    (npcd.hip.crossings.mesh_contains); the nodes are cast in patches of `patch` = (pz, py, px) nodes (patch_order)
+    and scattered back, a permutation that changes no bit.  No host read.  `container` stands in for mesh_contains (tests of the
+    host logic).
+
+    Unspecified: a node within rounding of the surface, and a mesh that is not closed (parity then means nothing)."""
+    if container is None:
+        from ..hip.crossings import mesh_contains as container
+    vertices, faces, _ = _mesh_parts(mesh)
+    gz, gy, gx = (int(g) for g in nodes)
+    if min(gz, gy, gx) < 1:
+        raise ValueError(f"voxelize_mesh: every axis needs at least 1 node; got {(gz, gy, gx)}")
+    dev = vertices.device
+    o, s = (_on_device(a, dev) for a in (origin, spacing))
+    order = patch_order((gz, gy, gx), patch, dev)
+    row = order // gx
+    at = torch.stack([order - row * gx, row % gy, row // gy], dim=1).to(torch.float32)
+    inside = container((o + s * at).contiguous(), vertices, faces, direction=direction)
+    out = torch.empty(gz * gy * gx, dtype=torch.bool, device=dev)
+    out[order] = inside
+    return out.view(gz, gy, gx)
+
+
+@torch.no_grad()
+def mesh_signed_distance(points: torch.Tensor, mesh, closest=None, container=None) -> torch.Tensor:
+    """points [S, 3] fp32 on the GPU -> [S] fp32: sqrt of the squared distance to the closest face of a closed mesh
+    (npcd.hip.mesh_distance.closest_on_mesh), negative where the point lies inside (npcd.hip.crossings.mesh_contains,
+    DESIGN.md 5.20); +inf for a mesh without a face that takes part.  No host read.  `closest` and `container` stand in.
+
+    Unspecified: the sign of a point within rounding of the surface, where |d| is within rounding of 0, and every sign for a mesh
+    that is not closed."""
+    closest = _closest_operator(closest)
+    if container is None:
+        from ..hip.crossings import mesh_contains as container
+    vertices, faces, _ = _mesh_parts(mesh)
+    d = torch.sqrt(closest(points, vertices, faces)["sqdist"])
+    return torch.where(container(points, vertices, faces), -d, d)
+
+
+def _node_set_iou(a: torch.Tensor, b: torch.Tensor) -> List[torch.Tensor]:
+    """Two bool lattices -> [|a|, |b|, |a and b|, |a or b|] as float64 words on their device."""
+    return [x.sum().to(torch.float64) for x in (a, b, a & b, a | b)]
+
+
+@torch.no_grad()
+def mesh_volume_iou(a, b, resolution: int = 64, bound: Optional[float] = None, voxelizer=None) -> Dict[str, float]:
+    """The volumetric intersection over union of two closed meshes on the GPU -> {"iou", "volume_a", "volume_b", "intersection",
+    "union"}, Python floats.
+
+    Both are voxelised (voxelize_mesh) on one lattice of resolution^3 cells over the union of the boxes of their finite vertices, or
+    with `bound` over [-bound, bound]^3; a node sits at the centre of its cell, and a volume is a node count times the cell volume.
+    iou is the ratio of the two node counts, 1 where both are empty.  float64 on the device; one host read.  `voxelizer` stands in
+    for voxelize_mesh (tests of the host logic).  Unspecified for a mesh that is not closed."""
+    G = int(resolution)
+    if G < 1:
+        raise ValueError(f"mesh_volume_iou: resolution must be at least 1; got {resolution}")
+    voxelizer = voxelize_mesh if voxelizer is None else voxelizer
+    va, vb = _mesh_parts(a)[0], _mesh_parts(b)[0]
+    if bound is None:
+        v = torch.cat([va, vb]).to(torch.float64)
+        finite = torch.isfinite(v).all(dim=1, keepdim=True)
+        lo = torch.where(finite, v, torch.full_like(v, float("inf"))).amin(dim=0) if v.shape[0] else torch.zeros(3, dtype=torch.float64, device=v.device)
+        hi = torch.where(finite, v, torch.full_like(v, -float("inf"))).amax(dim=0) if v.shape[0] else torch.zeros(3, dtype=torch.float64, device=v.device)
+        lo, hi = torch.where(hi >= lo, lo, torch.zeros_like(lo)), torch.where(hi >= lo, hi, torch.zeros_like(hi))          # no finite vertex
+    else:
+        if not float(bound) > 0:
+            raise ValueError(f"mesh_volume_iou: bound must be positive; got {bound}")
+        lo, hi = (torch.full((3,), x, dtype=torch.float64, device=va.device) for x in (-float(bound), float(bound)))
+    cell = (hi - lo) / G
+    origin, spacing = (lo + 0.5 * cell).to(torch.float32), cell.to(torch.float32)
+    inside = [voxelizer(m, origin, spacing, (G, G, G)) for m in (a, b)]
+    flat = torch.stack(_node_set_iou(*inside) + [spacing.to(torch.float64).prod()]).cpu().tolist()          # the one host read
+    n_a, n_b, n_both, n_either, volume = flat
+    return {"iou": n_both / n_either if n_either else 1.0, "volume_a": n_a * volume, "volume_b": n_b * volume,
+            "intersection": n_both * volume, "union": n_either * volume}
+
+
+@torch.no_grad()
+def mesh_enclosure(mesh, origin, spacing, solid: torch.Tensor, voxelizer=None) -> Dict[str, object]:
+    """Does a mesh enclose what its field calls solid?  solid: bool [Gz, Gy, Gx] on the GPU, the nodes of the lattice (origin, spacing)
+    where the density lies above the level -> {"agree": the share of nodes where voxelize_mesh equals solid, "inside_nodes",
+    "solid_nodes": the two counts, "iou": of the two node sets, 1 where both are empty}.  One host read.  An interpolated vertex
+    can round onto a node, and such a node may fall on either side: agree may lie a few nodes below 1 for a correct mesh."""
+    inside = (voxelize_mesh if voxelizer is None else voxelizer)(mesh, origin, spacing, tuple(solid.shape))
+    n_in, n_solid, n_both, n_either, same = torch.stack(_node_set_iou(inside, solid) + [(inside == solid).sum().to(torch.float64)]).cpu().tolist()
+    return {"agree": same / solid.numel(), "inside_nodes": int(n_in), "solid_nodes": int(n_solid), "iou": n_both / n_either if n_either else 1.0}
+
+
 @torch.no_grad()
 def sample_mesh_clouds(meshes, num_points: int, generator: Optional[torch.Generator] = None, normals: bool = False, sampler=None):
     """Meshes on the GPU, as isosurface or extract_mesh return them -> clouds [B, num_points, 3] fp32 drawn uniformly by area from
@@ -985,7 +1161,7 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
                  min_component_nodes: Optional[int] = None, normals: bool = False, simplify: Optional[float] = None,
                  simplifier=None, smooth: Optional[int] = None, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
                  topology: bool = False, smoother=None, deviation: Optional[int] = None, deviator=None, agreement=None,
-                 agreer=None) -> List[Dict[str, torch.Tensor]]:
+                 agreer=None, enclosure: bool = False, encloser=None) -> List[Dict[str, torch.Tensor]]:
     """coords [B, N, 3], feats [B, N, F] on the GPU -> per cloud {"vertices" [V, 3] fp32, "faces" [F, 3] int32, "colors" [V, 3] fp32
     in [0, 1] (with colors=True)}, all on the GPU.
 
@@ -1018,7 +1194,12 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
     agreement=(extrinsics [T, 4, 4], intrinsics [T, 3, 3]) or (extrinsics, intrinsics, image resolution) adds "agreement":
     mesh_render_agreement(pointnerf, the cloud, the final mesh, the cameras), whether the mesh looks like the field from those cameras
     (one more host read per mesh; the image resolution defaults to mesh_render_agreement's).  `agreer` stands in for
-    mesh_render_agreement (tests of the host logic).  agreement=None: the mesh as before."""
+    mesh_render_agreement (tests of the host logic).  agreement=None: the mesh as before.
+
+    enclosure=True adds "enclosure": mesh_enclosure(the final mesh, the lattice, filtered density > level), whether the mesh encloses
+    exactly the nodes that the field calls solid (one more host read per mesh).  Simplifying and smoothing move the
+    surface, so the report then says by how much in nodes.  `encloser` stands in for mesh_enclosure (tests of the host logic).
+    enclosure=False: the mesh as before."""
     from ..hip.isosurface import isosurface
     if agreement is not None:
         if not (isinstance(agreement, (tuple, list)) and len(agreement) in (2, 3) and all(isinstance(t, torch.Tensor) for t in agreement[:2])
@@ -1066,6 +1247,8 @@ def extract_mesh(pointnerf, coords: torch.Tensor, feats: torch.Tensor, resolutio
             size = {} if len(agreement) == 2 else {"resolution": agreement[2]}
             mesh["agreement"] = (mesh_render_agreement if agreer is None else agreer)(pointnerf, coords[b:b + 1], feats[b:b + 1], dict(mesh),
                                                                                        agreement[0], agreement[1], **size)
+        if enclosure:
+            mesh["enclosure"] = (mesh_enclosure if encloser is None else encloser)(dict(mesh), origin, spacing, filtered[b] > level)
         out.append(mesh)
     return out
 

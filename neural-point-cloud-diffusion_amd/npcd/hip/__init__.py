@@ -181,6 +181,7 @@ SIGNATURES = {
     "npcd_mesh_distance_boxes": (c_int, [_P, c_int64, _P, c_int64, _P, _P]),
     "npcd_mesh_distance_query": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int] + [_P] * 4 + [_P]),
     "npcd_raycast_query": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_float, c_int] + [_P] * 5 + [_P]),
+    "npcd_crossings_query": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_float, c_int] + [_P] * 3 + [_P]),
 }
 
 _lib = None
@@ -251,3 +252,4 @@ from .simplify import simplify_mesh  # noqa: E402,F401  (after the binding it is
 from .smooth import mesh_edges, smooth_mesh  # noqa: E402,F401
 from .mesh_distance import closest_on_mesh, mesh_boxes  # noqa: E402,F401
 from .raycast import cast_rays  # noqa: E402,F401
+from .crossings import count_crossings, mesh_contains  # noqa: E402,F401

@@ -20,6 +20,29 @@ WAVE_RAYS = 64
 MAX_RAYS = 2 ** 31
 
 
+def checked_rays(who: str, origins, directions, vertices, faces, boxes):
+    """The argument checks of cast_rays, which npcd.hip.crossings.count_crossings shares -> the four tensors, detached and contiguous."""
+    def sizes():
+        R, V, F = int(origins.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
+        if directions.shape[0] != R:
+            raise ValueError(f"{who}: {R} origins and {int(directions.shape[0])} directions")
+        if V >= MAX_VERTICES or F >= MAX_FACES or R >= MAX_RAYS:
+            raise ValueError(f"{who}: {R} rays, {V} vertices and {F} faces; rays and vertices must stay below 2^31 and faces below 2^28 = {MAX_FACES}")
+    return _checked(who, {"origins": origins, "directions": directions, "vertices": vertices, "faces": faces}, sizes, boxes)
+
+
+def ray_workspace(who: str, vertices: torch.Tensor, faces: torch.Tensor, boxes: Optional[torch.Tensor]) -> torch.Tensor:
+    """boxes= of cast_rays and count_crossings: mesh_boxes(vertices, faces) where none is given, else the given one if it can be
+    that of this mesh (ValueError otherwise).  Inside torch.cuda.device of the mesh."""
+    if boxes is None:
+        return mesh_boxes(vertices, faces)
+    need = lib().npcd_mesh_distance_ws_bytes(int(vertices.shape[0]), int(faces.shape[0]))
+    check(min(need, 0), "npcd_mesh_distance_ws_bytes")
+    if boxes.dtype != torch.int64 or boxes.dim() != 1 or not boxes.is_contiguous() or boxes.numel() * 8 < need:
+        raise ValueError(f"{who}: boxes must be what mesh_boxes returned for these vertices and faces ({need} bytes as int64)")
+    return boxes
+
+
 def cast_rays(origins: torch.Tensor, directions: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, t_min: float = 0.0,
               t_max: float = float("inf"), cull: bool = True, stats: bool = False, boxes: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """origins, directions [R, 3], vertices [V, 3] fp32 and faces [F, 3] int32 on the GPU -> {"t" [R] fp32, "face" [R] int32, "bary"
@@ -34,15 +57,7 @@ def cast_rays(origins: torch.Tensor, directions: torch.Tensor, vertices: torch.T
     stats=True adds "evaluated", an int64 word on the GPU: the (wave, tile) pairs that were evaluated, of ceil(R / WAVE_RAYS)
     ceil(F / TILE_FACES).  boxes= takes mesh_boxes(vertices, faces) from an earlier call.  No host read."""
     who = "cast_rays"
-
-    def sizes():
-        R, V, F = int(origins.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
-        if directions.shape[0] != R:
-            raise ValueError(f"{who}: {R} origins and {int(directions.shape[0])} directions")
-        if V >= MAX_VERTICES or F >= MAX_FACES or R >= MAX_RAYS:
-            raise ValueError(f"{who}: {R} rays, {V} vertices and {F} faces; rays and vertices must stay below 2^31 and faces below 2^28 = {MAX_FACES}")
-    origins, directions, vertices, faces = _checked(who, {"origins": origins, "directions": directions, "vertices": vertices, "faces": faces},
-                                                    sizes, boxes)
+    origins, directions, vertices, faces = checked_rays(who, origins, directions, vertices, faces, boxes)
     R, V, F = int(origins.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
     dev = origins.device
     L = lib()
@@ -56,13 +71,7 @@ def cast_rays(origins: torch.Tensor, directions: torch.Tensor, vertices: torch.T
             out["evaluated"] = evaluated
         if R == 0 or F == 0:
             return out
-        if boxes is None:
-            boxes = mesh_boxes(vertices, faces)
-        else:
-            need = L.npcd_mesh_distance_ws_bytes(V, F)
-            check(min(need, 0), "npcd_mesh_distance_ws_bytes")
-            if boxes.dtype != torch.int64 or boxes.dim() != 1 or not boxes.is_contiguous() or boxes.numel() * 8 < need:
-                raise ValueError(f"{who}: boxes must be what mesh_boxes returned for these vertices and faces ({need} bytes as int64)")
+        boxes = ray_workspace(who, vertices, faces, boxes)
         check(L.npcd_raycast_query(ptr(origins), ptr(directions), R, ptr(vertices), V, ptr(faces), F, ptr(boxes), float(t_min), float(t_max),
                                    1 if cull else 0, ptr(out["t"]), ptr(out["face"]), ptr(out["bary"]), ptr(out["front"]), ptr(evaluated),
                                    stream_ptr()), "npcd_raycast_query")
